@@ -13,12 +13,20 @@ Workload = BASELINE.json configs[1]: PPO "breakout", 256 envs per GPU, horizon 5
 spec-1 CNN, minibatch 512 x 4 epochs  ->  1280 agent steps per GPU per step.
 Metric = the reference runner's SamplesPerSecond (accel_rl/runners/accel_rl.py:93-98).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, primes, warms up, times --steps
+steps and prints the contract fields (metric, value, unit, higher_is_better, dtype,
+ms_per_step = milliseconds of one timed step, ...).  With --full it also carries
+  "phases":       rollout-only and learner-only re-timings of the same workload,
+  "alt_routes":   the headline re-timed on the other arithmetic routes, + "accuracy",
   "roofline":     the GAE scan kernel at a bandwidth-bound sweep size (HIP events
-                  on the launch stream) + the at-config point, and
+                  on the launch stream) + the at-config point,
   "kernels":      event-timed averages of the hand-written HBM-bound kernels of the step,
   "mfma":         the policy's fp32-MFMA conv / dense kernels at the PPO minibatch vs the MFMA peak,
-  "cpu_baseline": the oracle's CPU sampler port timed on this box's host cores.
+  "cpu_baseline": the oracle's CPU sampler port timed on this box's host cores,
+  "multi_gpu":    (N > 1) the per-rank figures and checks of multi_gpu_diagnostics.
+--dump-outputs DIR writes what the last timed step computed (the rollout batch, the learner's
+outputs and the updated parameters) as DIR/<name>.npy, float32 or float64, 64 MB at most: the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -91,6 +99,59 @@ def build_workload(device, seed, rank, world, game, use_graph, quiet=True, kind=
 def one_step(itr, sampler, algo):
     samples, _ = sampler.obtain_samples(itr)
     algo.optimize_policy(itr, samples)
+
+
+DUMP_MAX_ELEMS = 1 << 22        # per array (16 MB of float32): larger arrays are dumped as a seeded sample of their rows
+DUMP_MAX_BYTES = 64 << 20       # all arrays of one dump
+
+
+def _dump_leaves(obj, prefix, out):
+    """(name, tensor) pairs of the arrays in a nest of dicts / lists / tuples; a list of same-shape tensors is one array,
+    the segment views of a sampler buffer (views of its rows) are left out."""
+    if isinstance(obj, torch.Tensor):
+        out.append((prefix, obj))
+    elif isinstance(obj, np.ndarray):
+        out.append((prefix, torch.from_numpy(obj)))
+    elif isinstance(obj, dict):
+        for k in sorted(obj):
+            if k != "segs_view":
+                _dump_leaves(obj[k], "%s.%s" % (prefix, k) if prefix else str(k), out)
+    elif isinstance(obj, (list, tuple)) and obj:
+        if all(isinstance(x, torch.Tensor) and x.shape == obj[0].shape for x in obj):
+            out.append((prefix, torch.stack(list(obj))))
+        else:
+            for i, x in enumerate(obj):
+                _dump_leaves(x, "%s.%d" % (prefix, i), out)
+
+
+def dump_outputs(path, outputs):
+    """Write the arrays of `outputs` ({name: nest of tensors}) to path/<name>.npy: float64 stays float64, everything
+    else becomes float32.  An array of more than DUMP_MAX_ELEMS elements is written as a fixed, seeded sample of its
+    rows (sorted row indices, the same on every run), so that the whole dump stays under DUMP_MAX_BYTES."""
+    os.makedirs(path, exist_ok=True)
+    leaves = []
+    for name in sorted(outputs):
+        _dump_leaves(outputs[name], name, leaves)
+    arrays = []
+    for name, t in leaves:
+        a = t.detach()
+        if a.dim() == 0:
+            a = a.reshape(1)
+        if a.numel() > DUMP_MAX_ELEMS:
+            rows = a.shape[0]
+            keep = max(1, min(rows, DUMP_MAX_ELEMS // max(1, a[0].numel())))
+            idx = np.sort(np.random.RandomState(1234).choice(rows, keep, replace=False))
+            a = a.index_select(0, torch.from_numpy(idx).to(a.device))
+        arrays.append((name, a.cpu().numpy().astype(np.float64 if a.dtype == torch.float64 else np.float32)))
+    total = sum(a.nbytes for _, a in arrays)
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %.1f MB, more than %d MB" % (total / 2.0 ** 20, DUMP_MAX_BYTES >> 20))
+    for name, a in arrays:
+        np.save(os.path.join(path, name + ".npy"), a)
+    if not os.path.exists(os.path.join(path, ".gitignore")):       # a dump inside a work tree stays out of git
+        with open(os.path.join(path, ".gitignore"), "w") as f:
+            f.write("*\n")
+    return total
 
 
 def graph_time_ms(fn, per_graph=20, replays=5):
@@ -823,11 +884,12 @@ def _catdqn_run(device, batch, steps, warmup):
     t0 = time.perf_counter()
     for _ in range(steps):
         samples, _ = sampler.obtain_samples(itr)
-        algo.optimize_policy(itr, samples)
+        opt = algo.optimize_policy(itr, samples)
         itr += 1
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
-    return runner, algo, round(steps * n_env * horizon / el, 1), round(el / steps * 1e3, 4)
+    last = dict(samples=samples, opt_data=opt[0], opt_info=opt[1], params=policy.flat_params)
+    return runner, algo, round(steps * n_env * horizon / el, 1), round(el / steps * 1e3, 4), last
 
 
 def catdqn_main(args):
@@ -842,7 +904,10 @@ def catdqn_main(args):
     device = torch.device("cuda", 0)
     torch.cuda.set_device(device)
     n_env, horizon = 256, 4
-    runner, algo, value, ms = _catdqn_run(device, args.dqn_batch, args.steps, args.warmup)
+    runner, algo, value, ms, last = _catdqn_run(device, args.dqn_batch, args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
+    del last
     line = {"metric": "env-steps/sec (whole node), Categorical-DQN Seaquest, 1M-transition replay (BASELINE config 5, "
                       "not the headline metric)",
             "value": value, "unit": "env-steps/s", "n_gpus": 1,
@@ -854,11 +919,11 @@ def catdqn_main(args):
                                    (n_env, horizon, algo.replay_buffer.env_replay_size * n_env,
                                     algo.replay_buffer.frames.numel() / 1e9, args.dqn_batch, algo._updates_per_optimize),
                        "minibatch": args.dqn_batch, "updates_per_step": algo._updates_per_optimize}}
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         line["roofline"] = replay_roofline(device, algo)
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = replay_cpu_baseline(n_env, horizon, 3, args.dqn_batch, algo._updates_per_optimize)
-    if not args.no_alt_routes:
+    if args.full and not args.no_alt_routes:
         other = 512 if args.dqn_batch != 512 else 32
         runner.shutdown()
         algo._graph = None
@@ -866,7 +931,7 @@ def catdqn_main(args):
         import gc
         gc.collect()
         torch.cuda.synchronize()
-        runner, algo, v2, ms2 = _catdqn_run(device, other, args.steps, args.warmup)
+        runner, algo, v2, ms2, _ = _catdqn_run(device, other, args.steps, args.warmup)
         line["alt"] = {"minibatch": other, "updates_per_step": algo._updates_per_optimize, "value": v2, "ms_per_step": ms2,
                        "note": "the same workload at another replay minibatch (same training intensity: rows trained per "
                                "sampled transition); the reference's own default is 32 (dqn.py:18)"}
@@ -1048,10 +1113,17 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can carry: phase split, alt routes + accuracy, "
+                         "roofline / kernel / MFMA tables, CPU baseline, multi-GPU diagnostics (the --no-* options "
+                         "below leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) no roofline / kernel / MFMA tables")
     ap.add_argument("--no-alt-routes", action="store_true",
-                    help="skip the re-timing of the headline on the six-product and fp32-MFMA routes and the accuracy table")
+                    help="(--full) skip the re-timing of the headline on the six-product and fp32-MFMA routes and the "
+                         "accuracy table")
     ap.add_argument("--roofline-log2", type=int, default=26)
     ap.add_argument("--roofline-only", action="store_true",
                     help="only the GAE-scan roofline leg (used for the rocprofv3 --pmc passes)")
@@ -1066,6 +1138,8 @@ def main():
                     help="ppo256 = BASELINE config 2 (the metric's config, default); a2c1024 = config 3 "
                          "(A2C, 1024 envs, 5-step returns, spec-0 CNN, one rmsprop step per batch)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     global N_ENVS, CNN_SPEC, MINIBATCH
     if args.workload == "a2c1024":
@@ -1089,7 +1163,7 @@ def main():
         MINIBATCH = 512 * 8 // world
         args.no_cpu_baseline = args.no_roofline = True
     cpu_pool = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.roofline_only:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.roofline_only:
         cpu_pool = start_cpu_pool()
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (the product has no CPU path)")
@@ -1183,7 +1257,7 @@ def main():
         if inject_hang and i == 2:
             tick("learner (injected capture hang)", i)
             time.sleep(1e6)
-        algo.optimize_policy(i, samples)
+        return samples, algo.optimize_policy(i, samples)
 
     itr = 0
     # Priming (untimed, whatever --warmup says): the sampler captures its hipGraph in its first batch and the learner in
@@ -1199,10 +1273,15 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_step(itr, sampler, algo)
+        last = one_step(itr, sampler, algo)
         itr += 1
     barrier()
     elapsed = elapsed_local = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        tick("dump outputs")
+        dump_outputs(args.dump_outputs, dict(samples=last[0], opt_data=last[1][0], opt_info=last[1][1],
+                                             params=policy.flat_params))
+    del last
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -1242,13 +1321,14 @@ def main():
         barrier()
         return (time.perf_counter() - t) / reps
     reps = max(10, min(50, args.steps))
-    t_roll = timed(lambda i: sampler.obtain_samples(itr + i), reps)
-    samples = sampler.samples_buf
-    t_learn = timed(lambda i: algo.optimize_policy(itr + i, samples), reps)
-    line["phases"] = {"rollout_ms": round(t_roll * 1e3, 4), "learner_ms": round(t_learn * 1e3, 4),
-                      "rollout_only_env_steps_per_s": round(N_ENVS * HORIZON / t_roll, 1)}
+    if args.full:
+        t_roll = timed(lambda i: sampler.obtain_samples(itr + i), reps)
+        samples = sampler.samples_buf
+        t_learn = timed(lambda i: algo.optimize_policy(itr + i, samples), reps)
+        line["phases"] = {"rollout_ms": round(t_roll * 1e3, 4), "learner_ms": round(t_learn * 1e3, 4),
+                          "rollout_only_env_steps_per_s": round(N_ENVS * HORIZON / t_roll, 1)}
     tick("diagnostics", itr)
-    if rank == 0 and world == 1 and args.workload == "ppo256" and not args.no_alt_routes and not args.no_graph:
+    if args.full and rank == 0 and world == 1 and args.workload == "ppo256" and not args.no_alt_routes and not args.no_graph:
         # (here, under the headline's own conditions -- the CPU baseline's worker pools still parked on their barriers --
         #  and not behind cpu_baseline(): the teardown of its 200-odd processes was seen to cost the leg that followed it
         #  15 % on one box, profiles/r06/bench_alt_after_cpu_baseline.json)
@@ -1256,13 +1336,17 @@ def main():
         line["alt_routes"] = alt_routes(device, args.steps, args.warmup, PRIMING)
         line["accuracy"] = route_accuracy(device)
     if world > 1:
-        line["multi_gpu"] = multi_gpu_diagnostics(device, world, rank, algo, policy, sampler, samples, timed, reps,
-                                                  itr + 2 * reps, elapsed_local / args.steps, t_roll, t_learn, tick)
+        if args.full:
+            line["multi_gpu"] = multi_gpu_diagnostics(device, world, rank, algo, policy, sampler, samples, timed, reps,
+                                                      itr + 2 * reps, elapsed_local / args.steps, t_roll, t_learn, tick)
+            captured = line["multi_gpu"].get("graph_captured")
+        else:
+            captured = getattr(algo, "_graph", None) is not None and algo.optimizer.graph_ready()
         if os.environ.get("ARL_BENCH_GRAPH_FALLBACK"):
             line["graph_fallback"] = os.environ["ARL_BENCH_GRAPH_FALLBACK"]
-        if rank == 0 and line["multi_gpu"].get("graph_captured"):
+        if rank == 0 and captured:
             clear_stall_marker()
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_roofline and args.workload == "a2c1024":
             # config 3 is sampler-bound (BASELINE.json): its HBM-bound kernels are the 5-step return scan and the env step
             line["roofline"] = roofline_nstep(device, args.roofline_log2, 30)

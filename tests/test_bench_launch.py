@@ -55,7 +55,7 @@ def test_no_retry_when_the_collectives_are_eager_already():
 
 @pytest.mark.gpu
 def test_two_ranks_spawned_in_development_mode():
-    out = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-graph", "--no-cpu-baseline", "--no-roofline"],
+    out = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-graph", "--full", "--no-cpu-baseline", "--no-roofline"],
                dict(ARL_BENCH_ONE_GPU="1", ARL_BENCH_BACKEND="gloo"))
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-2000:])
     d = _line(out)
@@ -81,7 +81,7 @@ def _check_multi_gpu_keys(d, world):
 def test_eight_ranks_spawned_in_development_mode():
     """The driver's 8-GPU launch shape, all eight ranks on GPU 0 over gloo: rendezvous, per-rank seeds, broadcast, eight
     contributions per all-reduce, the self-describing keys -- a launch-path check, never a measurement."""
-    out = _run(["--gpus", "8", "--steps", "2", "--warmup", "1", "--no-graph", "--no-cpu-baseline", "--no-roofline"],
+    out = _run(["--gpus", "8", "--steps", "2", "--warmup", "1", "--no-graph", "--full", "--no-cpu-baseline", "--no-roofline"],
                dict(ARL_BENCH_ONE_GPU="1", ARL_BENCH_BACKEND="gloo"), timeout=900)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-2000:])
     d = _line(out)
@@ -94,7 +94,7 @@ def test_eight_ranks_spawned_in_development_mode():
 def test_strong_scaling_mode_splits_the_job():
     """--scaling strong: --total-envs environments and one global minibatch of 512 x 8 rows per update in all; at N = 1
     the single rank owns all of it."""
-    out = _run(["--scaling", "strong", "--total-envs", "2048", "--steps", "2", "--warmup", "1"])
+    out = _run(["--scaling", "strong", "--total-envs", "2048", "--steps", "2", "--warmup", "1", "--full"])
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-2000:])
     d = _line(out)
     assert d["scaling"] == "strong" and d["n_gpus"] == 1 and d["config"]["total_envs"] == 2048
@@ -109,7 +109,7 @@ def test_a_hung_capture_still_yields_one_line_on_eager_collectives(tmp_path):
     attempt (exit 3), the supervisor re-runs once with ARL_SYNC_GRAPH=0, and ONE line comes out that says so.  The
     watchdog also leaves a note on the node, so that a run started by a LAUNCHER afterwards (the driver's N = 4, 8 after
     a failed N = 2: no supervising parent) takes the eager path by itself."""
-    out = _run(["--gpus", "2", "--steps", "2", "--warmup", "0", "--no-cpu-baseline", "--no-roofline"],
+    out = _run(["--gpus", "2", "--steps", "2", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-roofline"],
                dict(ARL_BENCH_ONE_GPU="1", ARL_BENCH_BACKEND="gloo", ARL_BENCH_INJECT="capture_hang",
                     ARL_BENCH_STALL_S="25", TMPDIR=str(tmp_path)), timeout=900)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-3000:])
@@ -129,7 +129,7 @@ def test_a_hung_capture_still_yields_one_line_on_eager_collectives(tmp_path):
         env.pop(k, None)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2",
-                          "--steps", "2", "--warmup", "0", "--no-cpu-baseline", "--no-roofline"], cwd=ROOT, env=env,
+                          "--steps", "2", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-roofline"], cwd=ROOT, env=env,
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-3000:])
     d = _line(out)
@@ -159,3 +159,61 @@ def test_the_stall_note_is_keyed_on_build_and_user_and_can_be_cleared(tmp_path, 
     finally:
         monkeypatch.undo()
         importlib.reload(bench)
+
+
+def test_dump_outputs_writes_a_bounded_float_copy_of_the_arrays(tmp_path):
+    """bench.py --dump-outputs: every array of the nest as <dotted name>.npy, float64 kept, everything else float32, the
+    segment views (views of the buffer's own rows) left out, a list of same-shape tensors as one array, and an array
+    above the per-array bound as the SAME seeded sample of its rows on every call."""
+    import numpy as np
+    import torch
+    import bench
+    gen = torch.Generator().manual_seed(0)
+    big = torch.randint(0, 256, (1280, 4, 104, 80), dtype=torch.uint8, generator=gen)
+    nest = dict(samples=dict(observations=big, dones=torch.tensor([True, False]), segs_view=[dict(observations=big)],
+                             agent_infos=dict(value=torch.randn(5, dtype=torch.float64, generator=gen))),
+                opt_info=dict(Loss=[torch.tensor(1.5), torch.tensor(2.5)]), params=torch.randn(7, generator=gen))
+    sizes = [bench.dump_outputs(str(tmp_path / d), nest) for d in ("a", "b")]
+    names = sorted(n for n in os.listdir(str(tmp_path / "a")) if n != ".gitignore")
+    assert open(str(tmp_path / "a" / ".gitignore")).read() == "*\n"          # a dump inside a work tree stays out of git
+    assert names == ["opt_info.Loss.npy", "params.npy", "samples.agent_infos.value.npy", "samples.dones.npy",
+                     "samples.observations.npy"]
+    for n in names:
+        a, b = np.load(str(tmp_path / "a" / n)), np.load(str(tmp_path / "b" / n))
+        assert a.dtype == (np.float64 if "value" in n else np.float32) and np.array_equal(a, b)
+    obs = np.load(str(tmp_path / "a" / "samples.observations.npy"))
+    assert obs.shape[1:] == (4, 104, 80) and 0 < obs.size <= bench.DUMP_MAX_ELEMS and obs.shape[0] < 1280
+    rows = [i for i in range(1280) if np.array_equal(big[i].numpy().astype(np.float32), obs[0])]
+    assert rows and all(np.array_equal(big[r].numpy(), obs[0]) for r in rows)        # rows of the array, unaltered
+    assert np.array_equal(np.load(str(tmp_path / "a" / "opt_info.Loss.npy")), [1.5, 2.5])
+    assert sizes[0] == sizes[1] <= bench.DUMP_MAX_BYTES
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_the_headline_and_dumps_its_last_step(tmp_path):
+    """Without --full the line carries the headline only; --steps sets the timed steps; --dump-outputs writes the last
+    timed step's rollout batch, learner outputs and parameters (<= 64 MB), the same on a second run of the same
+    arguments."""
+    import numpy as np
+    lines = []
+    for d in ("a", "b"):
+        out = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d)])
+        assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-2000:])
+        lines.append(_line(out))
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+    for k in ("phases", "alt_routes", "accuracy", "roofline", "kernels", "mfma", "cpu_baseline", "gpu_over_cpu"):
+        assert k not in d
+    names = sorted(n for n in os.listdir(str(tmp_path / "a")) if n.endswith(".npy"))
+    for n in ("params.npy", "samples.observations.npy", "samples.actions.npy", "samples.rewards.npy",
+              "samples.agent_infos.prob.npy", "opt_data.advantages.npy", "opt_data.returns.npy", "opt_info.GradNorm.npy"):
+        assert n in names
+    total = 0
+    for n in names:
+        a, b = np.load(str(tmp_path / "a" / n)), np.load(str(tmp_path / "b" / n))
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all()
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20

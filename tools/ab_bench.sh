@@ -3,7 +3,7 @@ O=$1; shift; mkdir -p $O
 for round in 1 2; do
   for L in "$@"; do
     n=$(basename $L .so)
-    python tools/ab_lib.py $L bench.py --no-cpu-baseline --steps 100 2>/dev/null | tail -n 1 > $O/ab_${n}_$round.json
+    python tools/ab_lib.py $L bench.py --full --no-cpu-baseline --steps 100 2>/dev/null | tail -n 1 > $O/ab_${n}_$round.json
     python - <<PY
 import json
 d = json.load(open("$O/ab_${n}_$round.json"))

@@ -6,7 +6,7 @@ for round in 1 2; do
   for E in "$@"; do
     i=$((i+1))
     if [ "$E" = "-" ]; then EV=""; else EV="$E"; fi
-    timeout 120 env $EV python bench.py --no-cpu-baseline --steps 100 2>/dev/null | tail -n 1 > $O/env_${i}_$round.json
+    timeout 120 env $EV python bench.py --full --no-cpu-baseline --steps 100 2>/dev/null | tail -n 1 > $O/env_${i}_$round.json
     python - <<PY
 import json
 try:

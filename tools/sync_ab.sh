@@ -2,7 +2,7 @@
 # captured in one hipGraph (default), eager minibatches, and captured with ONE blocking all-reduce per minibatch.
 # usage: bash tools/sync_ab.sh <out dir>
 O=${1:-gpurun_out/r04}; mkdir -p $O
-run() { tag=$1; shift; env "$@" timeout 600 python bench.py --no-cpu-baseline --no-roofline --steps 300 --warmup 30 2>/dev/null | tail -n 1 > $O/bench_$tag.json
+run() { tag=$1; shift; env "$@" timeout 600 python bench.py --full --no-cpu-baseline --no-roofline --steps 300 --warmup 30 2>/dev/null | tail -n 1 > $O/bench_$tag.json
   python - <<PY
 import json
 d = json.load(open("$O/bench_$tag.json"))
