@@ -93,6 +93,14 @@ class ArlServeConv1(C.Structure):
                 ("relu", _i32)]
 
 
+class ArlNoisyLayer(C.Structure):
+    _fields_ = [("fein", _vp), ("feout", _vp), ("x", _vp), ("xs", _vp), ("fan_in", _i32), ("units", _i32),
+                ("out_stride", _i32), ("layer", _i32)]
+
+
+NOISY_MAX_LAYERS = 8
+
+
 class ArlReplay(C.Structure):
     _fields_ = [("n_env", _i64), ("size", _i32), ("n_stack", _i32), ("frame_bytes", _i32),
                 ("reward_horizon", _i32), ("frames", _vp), ("n_blanks", _vp), ("acts", _vp),
@@ -188,6 +196,12 @@ _SIGNATURES = {
     "arl_corun_job_init": (_i32, [C.POINTER(ArlCorunJob), C.POINTER(ArlOptState), _i32, _f32, _f32, _f32, _f32, _f32,
                                   _i32, _vp, _vp, _i64, _i64]),
     "arl_corun_job_run": (_i32, [C.POINTER(ArlCorunJob), _vp]),
+    "arl_noisy_normals": (_i32, [_i64, _i64, _i32, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "arl_noisy_noise": (_i32, [_vp, C.POINTER(ArlNoisyLayer), _i32, _i64, _i32, _vp]),
+    "arl_noisy_dense_combine": (_i32, [C.POINTER(ArlFoldItem), _vp, C.POINTER(ArlFoldItem), _vp, _vp, _i64, _i32, _i32,
+                                       _vp, _vp, _vp, _vp, _vp]),
+    "arl_noisy_dense_bwd_prep": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "arl_noisy_dense_bwd_dx": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
 }
 
 # include/accel_rl_hip_dev.h: development hooks (tests / tools), not part of the drop-in boundary
@@ -998,3 +1012,58 @@ def rnn_cell_bwd(dh, dh_rec, h_out, dpre, stream=None):
     (pdh, sdh), (ph, sh), (pd, sd) = _rows(dh), _rows(h_out), _rows(dpre)
     _check(load().arl_rnn_cell_bwd(pdh, sdh, ptr(dh_rec), ph, sh, batch, hidden, pd, sd, stream_ptr(stream)),
            "arl_rnn_cell_bwd")
+
+
+# ---------------------------------------------------------------------------
+# noisy dense layers (csrc/noisy.hip)
+# ---------------------------------------------------------------------------
+
+def noisy_normals(seed, counter, layer, which, rows, width, rows_per_draw=1, e=None, f=None, words=None, stream=None):
+    """One noisy layer's e_in (which 0) or e_out (which 1) draw, exactly as a forward pass makes it (arl_noisy_normals):
+    e, f = f(e) f32[rows][width], words int32[rows][width] (the Philox word each element used, as raw bits)."""
+    for t, dt, n in ((e, torch.float32, "e"), (f, torch.float32, "f"), (words, torch.int32, "words")):
+        if t is not None:
+            _want(t, dt, n)
+            assert t.numel() == rows * width, "%s size" % n
+    _check(load().arl_noisy_normals(int(seed), int(counter), int(layer), int(which), int(rows), int(width),
+                                    int(rows_per_draw), ptr(e), ptr(f), ptr(words), stream_ptr(stream)),
+           "arl_noisy_normals")
+
+
+def noisy_noise(state, layers, rows, rows_per_draw, stream=None):
+    """layers: [(fein, feout, x or None, xs or None, fan_in, units, out_stride, layer)] -> one arl_noisy_noise launch."""
+    _want(state, torch.int64, "state")
+    assert 0 < len(layers) <= NOISY_MAX_LAYERS
+    arr = (ArlNoisyLayer * len(layers))()
+    for it, (fein, feout, x, xs, fan_in, units, out_stride, layer) in zip(arr, layers):
+        assert fein.numel() == rows * fan_in and feout.numel() == rows * out_stride, "noise buffer sizes"
+        assert x is None or (x.numel() == xs.numel() == rows * fan_in), "x / xs size"
+        it.fein, it.feout, it.x, it.xs = ptr(fein), ptr(feout), ptr(x), ptr(xs)
+        it.fan_in, it.units, it.out_stride, it.layer = fan_in, units, out_stride, layer
+    _check(load().arl_noisy_noise(ptr(state), arr, len(layers), rows, rows_per_draw, stream_ptr(stream)),
+           "arl_noisy_noise")
+
+
+def noisy_dense_combine(w_item, bias, s_item, b_sigma, feout, y, relu, fein_next=None, xs_next=None, state=None,
+                        stream=None):
+    """y[rows, units] = relu?(P_w + f(e_out) * P_sigma) from the two arl_conv2d_fwd_parts items (arl_noisy_dense_combine)."""
+    rows, units = y.shape
+    assert feout.numel() == y.numel(), "feout size"
+    assert fein_next is None or (fein_next.numel() == xs_next.numel() == y.numel()), "fein_next / xs_next size"
+    _check(load().arl_noisy_dense_combine(C.byref(w_item), ptr(bias), C.byref(s_item), ptr(b_sigma), ptr(feout), rows,
+                                          units, int(bool(relu)), ptr(y), ptr(fein_next), ptr(xs_next), ptr(state),
+                                          stream_ptr(stream)), "arl_noisy_dense_combine")
+
+
+def noisy_dense_bwd_prep(g, feout, g2, db, db_sigma, stream=None):
+    rows, units = g.shape
+    assert feout.numel() == g2.numel() == g.numel() and db.numel() == db_sigma.numel() == units, "sizes"
+    _check(load().arl_noisy_dense_bwd_prep(ptr(g), ptr(feout), rows, units, ptr(g2), ptr(db), ptr(db_sigma),
+                                           stream_ptr(stream)), "arl_noisy_dense_bwd_prep")
+
+
+def noisy_dense_bwd_dx(dx_w, dx_sigma, fein, dx, stream=None):
+    rows, fan_in = dx.shape[0], dx.numel() // dx.shape[0]
+    assert dx_w.numel() == dx_sigma.numel() == fein.numel() == dx.numel(), "sizes"
+    _check(load().arl_noisy_dense_bwd_dx(ptr(dx_w), ptr(dx_sigma), ptr(fein), rows, fan_in, ptr(dx),
+                                         stream_ptr(stream)), "arl_noisy_dense_bwd_dx")

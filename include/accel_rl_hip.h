@@ -858,6 +858,74 @@ int arl_corun_job_init(arl_corun_job* job, const arl_opt_state* opt, int32_t met
                        double* norm_parts, int64_t hole_first, int64_t hole_count);
 int arl_corun_job_run(const arl_corun_job* job, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Noisy dense layers (NoisyNets, factorized Gaussian noise; csrc/noisy.hip)
+ * ------------------------------------------------------------------------- */
+
+/* NoisyDenseLayer.get_output_for with factorized=True, accel_rl/policies/dqn/layers/noisy_layer.py:100-147 (the noise
+ * draws of :83-88 / :125-139, f of :10-11), for AtariNoisyNetDqnPolicy (policies/dqn/atari_noisy_net_dqn_policy.py:20-148):
+ *   y = x W + b + f(e_out) * ((x * f(e_in)) W_sigma + b_sigma),   f(e) = sgn(e) sqrt(|e|)
+ * which equals x (W + W_sigma * f(e_in) f(e_out)^T) + b + b_sigma * f(e_out) without a per-row weight matrix.
+ *
+ * Generator.  Element j of the e_in (which = 0) or e_out (which = 1) draw of noisy layer `layer` for the row group
+ * g = row / rows_per_draw (rows_per_draw = 1: every row draws its own noise, common_noise=False; = rows of a call:
+ * one draw per call, common_noise=True) at call counter n, with seed s:
+ *   words w[0..3] = Philox4x32-10(counter = (j / 4, g, n mod 2^32, n >> 32), key = (s mod 2^32, 2 layer + which))
+ *     (Random123's Philox4x32 with 10 rounds: multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9,
+ *      0xBB67AE85; per round (hi0, lo0) = M0 c0, (hi1, lo1) = M1 c2, c = (hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0),
+ *      the key incremented before rounds 2..10)
+ *   for the pair p = (j % 4) / 2: u1 = ((w[2p] >> 8) + 0.5) / 2^24, u2 = ((w[2p+1] >> 8) + 0.5) / 2^24 (in (0, 1)),
+ *   r = sqrt(-2 ln u1) in double, e = r cos(2 pi u2) for even j, r sin(2 pi u2) for odd j, rounded to float once.
+ * Factorized noise (noisy_layer.py:83-88,125-139): e_in has fan_in elements, e_out `units`.
+ *   e_or_null / f_or_null f32[rows][width] (e, f(e)), words_or_null u32[rows][width] (the word element j used,
+ *   w[j % 4]); at least one of them.                                                                                */
+int arl_noisy_normals(int64_t seed, int64_t counter, int32_t layer, int32_t which, int64_t rows, int32_t width,
+                      int32_t rows_per_draw, float* e_or_null, float* f_or_null, uint32_t* words_or_null,
+                      void* stream);
+
+/* One noisy layer of a forward pass for arl_noisy_noise. */
+typedef struct arl_noisy_layer {
+    float* fein;                /* f32[rows][fan_in]: f(e_in) of each row                                           */
+    float* feout;               /* f32[rows][out_stride]: f(e_out) of each row; columns units .. out_stride-1 = 0    */
+    const float* x;             /* f32[rows][fan_in]: the layer's input if it exists already, else NULL             */
+    float* xs;                  /* f32[rows][fan_in]: x * f(e_in) (written when x is given)                         */
+    int32_t fan_in;             /* multiple of 4                                                                    */
+    int32_t units;              /* width of e_out                                                                   */
+    int32_t out_stride;         /* stored columns of the layer's output: multiple of 4, >= units                    */
+    int32_t layer;              /* the generator's layer index                                                      */
+} arl_noisy_layer;
+#define ARL_NOISY_MAX_LAYERS 8
+
+/* The noise of every noisy layer of one forward pass of `rows` rows in ONE launch: the draws of the generator above at
+ * seed state[0] and call counter state[1] (int64[2] in device memory -- the policy's noise state; a replayed hipGraph
+ * reads the current value), f(e_in), f(e_out) and x * f(e_in) where x is given.  This launch does not advance the
+ * counter: a later launch of the same pass does (arl_noisy_dense_combine's state_or_null), so eager and captured runs
+ * draw the same sequence.  Replaces the rng.normal draws of noisy_layer.py:83-88,125-139.                          */
+int arl_noisy_noise(const int64_t* state, const arl_noisy_layer* layers, int32_t n_layers, int64_t rows,
+                    int32_t rows_per_draw, void* stream);
+
+/* The layer's output from its two products as arl_conv2d_fwd_parts left them (relu 0; W product with bias b, W_sigma
+ * product with bias b_sigma: splits == 0 means finished, bias applied; splits > 0: folded here in arl_fold_many's order,
+ * then the bias): y = relu?(P_w + f(e_out) * P_sigma), f32[rows][units] (noisy_layer.py:120-147, a hidden layer's
+ * rectifier: noisy_net_dqn_cnn.py:64-76).  fein_next / xs_next (both or neither): xs_next = y * fein_next, the next
+ * noisy layer's input times its f(e_in).  state_or_null: state[1] += 1 (the pass's last launch advances the counter).  */
+int arl_noisy_dense_combine(const arl_fold_item* w_prod, const float* bias_or_null, const arl_fold_item* sigma_prod,
+                            const float* b_sigma_or_null, const float* feout, int64_t rows, int32_t units, int32_t relu,
+                            float* y, const float* fein_next_or_null, float* xs_next_or_null, int64_t* state_or_null,
+                            void* stream);
+
+/* Backward of the noise terms, given g = dL/dy f32[rows][units] with the layer's rectifier mask applied (T.grad of
+ * noisy_layer.py:141-147): g2 = g * f(e_out); db[u] = sum_rows g, db_sigma[u] = sum_rows g2, rows summed in order
+ * (no atomics).  dW = g^T x and dW_sigma = g2^T (x * f(e_in)) are arl_conv2d_bwd_pair's.                           */
+int arl_noisy_dense_bwd_prep(const float* g, const float* feout, int64_t rows, int32_t units, float* g2, float* db,
+                             float* db_sigma, void* stream);
+
+/* dx = dx_w + f(e_in) * dx_sigma, f32[rows][fan_in]: the data gradient of a noisy layer from its two data products
+ * (g W and g2 W_sigma, both already multiplied by the rectifier mask of the layer below by arl_conv2d_bwd_pair).
+ * dx may alias dx_w.  fan_in % 4 == 0, 16-byte aligned pointers.                                                   */
+int arl_noisy_dense_bwd_dx(const float* dx_w, const float* dx_sigma, const float* fein, int64_t rows, int32_t fan_in,
+                           float* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
