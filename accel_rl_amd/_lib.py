@@ -101,6 +101,19 @@ class ArlNoisyLayer(C.Structure):
 NOISY_MAX_LAYERS = 8
 
 
+class ArlNoisyDraw(C.Structure):
+    _fields_ = [("f", _vp), ("x", _vp), ("xs", _vp), ("width", _i32), ("pitch", _i32), ("layer", _i32),
+                ("which", _i32)]
+
+
+NOISY_MAX_DRAWS = 16
+
+
+class ArlNoisyLogitSrc(C.Structure):
+    _fields_ = [("w_part", _vp), ("bias_or_null", _vp), ("s_part", _vp), ("b_sigma_or_null", _vp), ("feout", _vp),
+                ("w_split_stride", _i64), ("s_split_stride", _i64), ("w_splits", _i32), ("s_splits", _i32)]
+
+
 class ArlReplay(C.Structure):
     _fields_ = [("n_env", _i64), ("size", _i32), ("n_stack", _i32), ("frame_bytes", _i32),
                 ("reward_horizon", _i32), ("frames", _vp), ("n_blanks", _vp), ("acts", _vp),
@@ -202,6 +215,15 @@ _SIGNATURES = {
                                        _vp, _vp, _vp, _vp, _vp]),
     "arl_noisy_dense_bwd_prep": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "arl_noisy_dense_bwd_dx": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "arl_noisy_draws": (_i32, [_vp, C.POINTER(ArlNoisyDraw), _i32, _i64, _i32, _vp]),
+    "arl_noisy_duel_combine": (_i32, [C.POINTER(ArlFoldItem), _vp, C.POINTER(ArlFoldItem), C.POINTER(ArlFoldItem), _vp,
+                                      _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "arl_noisy_duel_bwd_prep": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "arl_noisy_duel_bwd_dx": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "arl_noisy_catdqn_loss_limits": (_i32, [C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "arl_noisy_catdqn_loss_parts": (_i32, [C.POINTER(ArlNoisyLogitSrc), C.POINTER(ArlNoisyLogitSrc),
+                                           C.POINTER(ArlNoisyLogitSrc), _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32,
+                                           _i32, _f32, _f32, _f32, _vp, _vp, _vp, C.POINTER(ArlDgradWt), _i32, _vp]),
 }
 
 # include/accel_rl_hip_dev.h: development hooks (tests / tools), not part of the drop-in boundary
@@ -1067,3 +1089,83 @@ def noisy_dense_bwd_dx(dx_w, dx_sigma, fein, dx, stream=None):
     assert dx_w.numel() == dx_sigma.numel() == fein.numel() == dx.numel(), "sizes"
     _check(load().arl_noisy_dense_bwd_dx(ptr(dx_w), ptr(dx_sigma), ptr(fein), rows, fan_in, ptr(dx),
                                          stream_ptr(stream)), "arl_noisy_dense_bwd_dx")
+
+
+def noisy_draws(state, draws, rows, rows_per_draw, stream=None):
+    """draws: [(f, x or None, xs or None, width, pitch, layer, which)] -> one arl_noisy_draws launch.  f / x / xs may be
+    column slices of wider buffers (pitch floats per row)."""
+    _want(state, torch.int64, "state")
+    assert 0 < len(draws) <= NOISY_MAX_DRAWS
+    arr = (ArlNoisyDraw * len(draws))()
+    for it, (f, x, xs, width, pitch, layer, which) in zip(arr, draws):
+        for t in (f, x, xs):                # (column slices: not contiguous, rows `pitch` floats apart)
+            assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == rows and
+                                 t.shape[1] >= width and t.stride() == (pitch, 1)), "draw buffer shape / pitch"
+        it.f, it.x, it.xs = (None if t is None else t.data_ptr() for t in (f, x, xs))
+        it.width, it.pitch, it.layer, it.which = width, pitch, layer, which
+    _check(load().arl_noisy_draws(ptr(state), arr, len(draws), rows, rows_per_draw, stream_ptr(stream)),
+           "arl_noisy_draws")
+
+
+def noisy_duel_combine(w_item, bias, s_lo, s_hi, b_sigma, feout, y, split, relu, fein_next=None, xs_next=None,
+                       state=None, stream=None):
+    """y[rows, units] = relu?(P_w + f(e_out) * P_sigma), P_sigma from s_lo (columns < split) / s_hi (the rest)."""
+    rows, units = y.shape
+    assert feout.numel() == y.numel(), "feout size"
+    assert fein_next is None or (fein_next.numel() == xs_next.numel() == y.numel()), "fein_next / xs_next size"
+    _check(load().arl_noisy_duel_combine(C.byref(w_item), ptr(bias), C.byref(s_lo), C.byref(s_hi), ptr(b_sigma),
+                                         ptr(feout), rows, units, split, int(bool(relu)), ptr(y), ptr(fein_next),
+                                         ptr(xs_next), ptr(state), stream_ptr(stream)), "arl_noisy_duel_combine")
+
+
+def noisy_duel_bwd_prep(g, feout, split, g2_lo, g2_hi, db, db_sigma, stream=None):
+    rows, units = g.shape
+    assert feout.numel() == g.numel() and db.numel() == db_sigma.numel() == units, "sizes"
+    assert g2_lo.numel() == rows * split and g2_hi.numel() == rows * (units - split), "g2 sizes"
+    _check(load().arl_noisy_duel_bwd_prep(ptr(g), ptr(feout), rows, units, split, ptr(g2_lo), ptr(g2_hi), ptr(db),
+                                          ptr(db_sigma), stream_ptr(stream)), "arl_noisy_duel_bwd_prep")
+
+
+def noisy_duel_bwd_dx(dx_w, dxs_lo, fein_lo, dxs_hi, fein_hi, dx, stream=None):
+    rows, fan_in = dx.shape[0], dx.numel() // dx.shape[0]
+    assert all(t.numel() == dx.numel() for t in (dx_w, dxs_lo, fein_lo, dxs_hi, fein_hi)), "sizes"
+    _check(load().arl_noisy_duel_bwd_dx(ptr(dx_w), ptr(dxs_lo), ptr(fein_lo), ptr(dxs_hi), ptr(fein_hi), rows, fan_in,
+                                        ptr(dx), stream_ptr(stream)), "arl_noisy_duel_bwd_dx")
+
+
+def noisy_catdqn_loss_limits():
+    """(max splits per product, max actions, max atoms) of arl_noisy_catdqn_loss_parts."""
+    v = [C.c_int32() for _ in range(3)]
+    _check(load().arl_noisy_catdqn_loss_limits(*(C.byref(x) for x in v)), "arl_noisy_catdqn_loss_limits")
+    return tuple(x.value for x in v)
+
+
+def noisy_logit_src(w_item, bias, s_item, b_sigma, feout, row0=0, row_floats=0):
+    """ArlNoisyLogitSrc from the output layer's two conv2d_fwd_parts items, its biases and f(e_out), rows from row0 on."""
+    src = ArlNoisyLogitSrc()
+    off = 4 * row0 * row_floats
+    src.w_part, src.s_part = w_item.part + off, s_item.part + off
+    src.bias_or_null, src.b_sigma_or_null = ptr(bias), ptr(b_sigma)
+    src.feout = feout.data_ptr() + off
+    src.w_split_stride, src.s_split_stride = w_item.total, s_item.total
+    src.w_splits, src.s_splits = w_item.splits, s_item.splits
+    return src
+
+
+def noisy_catdqn_loss_parts(pred, tgt_next, pol_next, z, actions, returns, terminals, is_weights, n_actions, n_atoms,
+                            atom_stride, v_min, v_max, gamma_n, dlogits, loss_rows, kl, dueling=False, stream=None,
+                            dgrad_weights=None):
+    """arl_catdqn_loss on a noisy output layer's two products (ArlNoisyLogitSrc each; pol_next None: not double DQN)."""
+    wt_items, n_wt = None, 0
+    if dgrad_weights:
+        n_wt = len(dgrad_weights)
+        assert n_wt <= DGRAD_WT_MAX
+        wt_items = (ArlDgradWt * n_wt)()
+        for it, (w, wt, geom) in zip(wt_items, dgrad_weights):
+            it.w, it.wt, it.geom = ptr(w), ptr(wt), C.pointer(geom)
+    _check(load().arl_noisy_catdqn_loss_parts(C.byref(pred), C.byref(tgt_next),
+                                              None if pol_next is None else C.byref(pol_next), ptr(z), ptr(actions),
+                                              ptr(returns), ptr(terminals), ptr(is_weights), actions.numel(), n_actions,
+                                              n_atoms, atom_stride, int(dueling), float(v_min), float(v_max),
+                                              float(gamma_n), ptr(dlogits), ptr(loss_rows), ptr(kl), wt_items, n_wt,
+                                              stream_ptr(stream)), "arl_noisy_catdqn_loss_parts")

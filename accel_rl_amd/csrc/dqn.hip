@@ -9,6 +9,9 @@
 //                     loss, KL priorities, and d loss / d logits in one pass
 //                     (algos/dqn/cat_dqn.py:40-109)
 //
+//   arl_noisy_catdqn_loss_parts  arl_catdqn_loss reading a noisy output layer's two products' split partial sums,
+//                     folding them and applying the noise as arl_noisy_dense_combine does (csrc/noisy.hip)
+//
 //   arl_dqn_act       plain Q-learning twin of arl_catdqn_act: greedy action = first maximum of the Q row
 //                     (policies/dqn/atari_dqn_policy.py:61-63,118-130)
 //   arl_dqn_loss      one-step / n-step Q-learning target (max or double-DQN selection), squared or
@@ -22,6 +25,10 @@
 #include "arl_common.h"
 #include "dgrad_wt_dev.h"
 #include <type_traits>
+
+namespace arlc {
+int fold_wide_from();           // mfma_conv.hip: the split count from which a fold sums 64-way
+}
 
 namespace {
 
@@ -77,6 +84,36 @@ struct Parts {
             }
             return bias ? tot + bias[off] : tot;
         }
+    }
+};
+
+// NoisyParts: a noisy output layer's logits from its two products' split partial sums (AtariNoisyNetCatDqnPolicy) --
+// logit = [x W + b] + f(e_out) * ([(x f(e_in)) W_sigma + b_sigma], each product folded as noisy.hip's combine_kernel folds
+// it (zgn groups: 16, or 64 from arlc::fold_wide_from() splits; splits == 0: finished, bias already applied), operation
+// for operation, so that the loss launch can take the place of the combine launch without moving a bit.
+struct NoisySrc {
+    const float* pw; const float* bias; const float* ps; const float* b_sigma; const float* feout;
+    long long ssw, sss;         // floats between consecutive splits
+    int nw, ns, zw, zs;         // splits (0: finished), fold groups
+};
+__device__ __forceinline__ float noisy_fold(const float* p, long long ss, int splits, int zgn, int off,
+                                            const float* bias) {
+    if (splits <= 0) return p[off];
+    float s = 0.f;
+    for (int k = 0; k < zgn; ++k) {
+        float sk = 0.f;
+        for (int z = k; z < splits; z += zgn) sk += p[(long long)z * ss + off];
+        s = k == 0 ? sk : s + sk;
+    }
+    if (bias) s += bias[off];
+    return s;
+}
+struct NoisyParts {
+    NoisySrc q;                 // pointers at this sample's block
+    __device__ __forceinline__ float operator()(int off) const {
+        const float a = noisy_fold(q.pw, q.ssw, q.nw, q.zw, off, q.bias);
+        const float s = noisy_fold(q.ps, q.sss, q.ns, q.zs, off, q.b_sigma);
+        return a + q.feout[off] * s;
     }
 };
 
@@ -142,6 +179,7 @@ struct CatLossArgs {
     const float* tgt_next_logits;   // target net on next_obs         [B][A][S]
     const float* pol_next_logits;   // policy net on next_obs (double DQN) or null
     LogitSrc src[3];                // PARTS: the same three (pred, tgt_next, pol_next), as split partial sums
+    NoisySrc nsrc[3];               // NOISY: the same three, as a noisy layer's two products (block 0 of the batch)
     const float* z;                 // [n_atoms] support
     const uint8_t* actions;         // [B]
     const float* returns;           // [B] n-step discounted return
@@ -161,10 +199,10 @@ struct CatLossArgs {
 // projection, loss and gradient (lane i = atom i).
 // wt (PARTS): the workgroups behind the samples' own (blockIdx.x >= batch) write the data gradients' k-contiguous weight
 // copies (dgrad_wt_dev.h) for the backward pass that follows -- as the policy-gradient head's launch does (learner.hip)
-template <int NS>                  // -1: finished logits; >= 0: split partial sums (Parts<NS>)
+template <int NS>                  // -1: finished logits; >= 0: split partial sums (Parts<NS>); -2: NoisyParts
 __global__ __launch_bounds__(256) void catdqn_loss_kernel(const CatLossArgs a, const arlw::DgradWtArgs wt) {
-    constexpr bool PARTS = NS >= 0;
-    if (PARTS && (int64_t)blockIdx.x >= a.batch) {
+    constexpr bool PARTS = NS >= 0, NOISY = NS == -2;
+    if ((PARTS || NOISY) && (int64_t)blockIdx.x >= a.batch) {
         arlw::dgrad_wt_block(wt, (int)(blockIdx.x - a.batch), (int)threadIdx.x);
         return;
     }
@@ -175,9 +213,14 @@ __global__ __launch_bounds__(256) void catdqn_loss_kernel(const CatLossArgs a, c
     const bool duel = a.dueling != 0;
     const int64_t R = (int64_t)(A + a.dueling) * S;      // floats per sample
     const float z_lane = lane < n ? a.z[lane] : 0.f;
-    using L = typename std::conditional<PARTS, Parts<(NS > 0 ? NS : 0)>, Plain>::type;
+    using L = typename std::conditional<NOISY, NoisyParts,
+                                        typename std::conditional<PARTS, Parts<(NS > 0 ? NS : 0)>, Plain>::type>::type;
     auto block_of = [&](int which, const float* plain) -> L {
-        if constexpr (PARTS) {
+        if constexpr (NOISY) {
+            NoisySrc q = a.nsrc[which];
+            q.pw += b * R; q.ps += b * R; q.feout += b * R;
+            return L{q};
+        } else if constexpr (PARTS) {
             const LogitSrc& q = a.src[which];
             return L{q.p + b * R, q.bias, q.ss, q.splits};
         } else {
@@ -187,7 +230,7 @@ __global__ __launch_bounds__(256) void catdqn_loss_kernel(const CatLossArgs a, c
     const L tgt = block_of(1, a.tgt_next_logits);
     // greedy next action: under the policy net (double DQN) or the target net (cat_dqn.py:77-81), first maximum
     {
-        const bool dbl = PARTS ? a.src[2].p != nullptr : a.pol_next_logits != nullptr;
+        const bool dbl = NOISY ? a.nsrc[2].pw != nullptr : PARTS ? a.src[2].p != nullptr : a.pol_next_logits != nullptr;
         const L sel = dbl ? block_of(2, a.pol_next_logits) : tgt;
         const Duel d = duel_terms(sel, lane, A, n, S, duel);
         // this wave's actions (k = wave, wave + 4, ...; at most 16 of the <= 64): every logit requested before the first
@@ -475,4 +518,56 @@ extern "C" int arl_catdqn_loss_parts(const arl_logit_src* pred, const arl_logit_
     default: hipLaunchKernelGGL(catdqn_loss_kernel<0>, grid, dim3(256), 0, st, a, wt);
     }
     return arl::check_launch("catdqn_loss_kernel (parts)");
+}
+
+extern "C" int arl_noisy_catdqn_loss_limits(int32_t* max_splits, int32_t* max_actions, int32_t* max_atoms) {
+    ARL_REQUIRE(max_splits && max_actions && max_atoms, ARL_E_ARG, "null pointer");
+    *max_splits = ARL_NOISY_CATDQN_MAX_SPLITS;
+    *max_actions = 64;
+    *max_atoms = 64;
+    return 0;
+}
+
+extern "C" int arl_noisy_catdqn_loss_parts(const arl_noisy_logit_src* pred, const arl_noisy_logit_src* tgt_next,
+                                           const arl_noisy_logit_src* pol_next_or_null, const float* z,
+                                           const uint8_t* actions, const float* returns, const uint8_t* terminals,
+                                           const float* is_weights_or_null, int64_t batch, int32_t n_actions,
+                                           int32_t n_atoms, int32_t atom_stride, int32_t dueling, float v_min,
+                                           float v_max, float gamma_n, float* dlogits, float* loss_rows, float* kl,
+                                           const arl_dgrad_wt* wt_items_or_null, int32_t n_wt, void* stream) {
+    ARL_REQUIRE(pred && tgt_next && z && actions && returns && terminals && dlogits && loss_rows && kl, ARL_E_ARG,
+                "null pointer");
+    int rc = check_cat(batch, n_actions, n_atoms, atom_stride);
+    if (rc) return rc;
+    ARL_REQUIRE(v_max > v_min, ARL_E_ARG, "v_max must exceed v_min");
+    const arl_noisy_logit_src* in[3] = {pred, tgt_next, pol_next_or_null};
+    const int wide = arlc::fold_wide_from();
+    CatLossArgs a = {};
+    for (int i = 0; i < 3; ++i) {
+        if (!in[i]) continue;
+        const arl_noisy_logit_src& q = *in[i];
+        ARL_REQUIRE(q.w_part && q.s_part && q.feout, ARL_E_ARG, "null pointer in a logit source");
+        ARL_REQUIRE(q.w_splits >= 0 && q.s_splits >= 0 && (q.w_splits == 0 || q.w_split_stride > 0) &&
+                    (q.s_splits == 0 || q.s_split_stride > 0), ARL_E_ARG, "logit source: negative splits or stride");
+        ARL_REQUIRE(q.w_splits <= ARL_NOISY_CATDQN_MAX_SPLITS && q.s_splits <= ARL_NOISY_CATDQN_MAX_SPLITS, ARL_E_RANGE,
+                    "logit source: more than ARL_NOISY_CATDQN_MAX_SPLITS splits (fold them first: "
+                    "arl_noisy_dense_combine + arl_catdqn_loss)");
+        NoisySrc& d = a.nsrc[i];
+        d.pw = q.w_part; d.bias = q.bias_or_null; d.ps = q.s_part; d.b_sigma = q.b_sigma_or_null; d.feout = q.feout;
+        d.ssw = q.w_split_stride; d.sss = q.s_split_stride; d.nw = q.w_splits; d.ns = q.s_splits;
+        d.zw = q.w_splits >= wide ? 64 : 16; d.zs = q.s_splits >= wide ? 64 : 16;
+    }
+    a.z = z; a.actions = actions; a.returns = returns; a.terminals = terminals; a.is_weights = is_weights_or_null;
+    a.dlogits = dlogits; a.loss_rows = loss_rows; a.kl = kl; a.batch = batch;
+    a.n_actions = n_actions; a.n_atoms = n_atoms; a.stride = atom_stride; a.dueling = dueling != 0;
+    a.v_min = v_min; a.v_max = v_max; a.gamma_n = gamma_n;
+    arlw::DgradWtArgs wt = {};
+    int wt_blocks = 0;
+    if (wt_items_or_null && n_wt > 0) {
+        rc = arlw::dgrad_wt_plan(wt_items_or_null, n_wt, &wt, &wt_blocks);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(catdqn_loss_kernel<-2>, dim3((unsigned)(batch + wt_blocks)), dim3(256), 0, (hipStream_t)stream,
+                       a, wt);
+    return arl::check_launch("catdqn_loss_kernel (noisy parts)");
 }

@@ -926,6 +926,98 @@ int arl_noisy_dense_bwd_prep(const float* g, const float* feout, int64_t rows, i
 int arl_noisy_dense_bwd_dx(const float* dx_w, const float* dx_sigma, const float* fein, int64_t rows, int32_t fan_in,
                            float* dx, void* stream);
 
+/* ---- AtariNoisyNetCatDqnPolicy: CatDqnCnn (accel_rl/policies/dqn/networks/catdqn_cnn.py:40-99) with every DenseLayer a
+ * factorized NoisyDenseLayer (noisy_layer.py:15-147).  Its noise, with the generator above (seed s, call counter n of
+ * the pass, rows_per_draw as above), H = hidden units, A = actions, N = atoms, S = atom_stride, x_c = the conv output in
+ * the internal (h, w, c) order:
+ *   not dueling, hidden layers j = 0 .. J-1 and the output layer "action_atoms" = layer J:
+ *     hidden j   e_in  = (layer j, which 0, elements 0 .. fan_in-1)  e_out = (layer j, which 1, elements 0 .. units-1)
+ *     output     e_in  = (layer J, which 0, elements 0 .. H_last-1)  e_out of reference unit a N + i (action a, atom i)
+ *                                                                    = (layer J, which 1, element a S + i) of a draw of
+ *                                                                      A S elements (the stored, atom-padded layout)
+ *   dueling (one hidden layer; layers numbered in CatDqnCnn's construction order hidden_0, action_atoms, hidden_Val_0,
+ *   Val):
+ *     hidden_0     e_in = (layer 0, which 0, 0 .. F-1)   e_out = (layer 0, which 1, 0 .. H-1)
+ *     action_atoms e_in = (layer 1, which 0, 0 .. H-1)   e_out of unit a N + i = (layer 1, which 1, element a S + i)
+ *     hidden_Val_0 e_in = (layer 2, which 0, 0 .. F-1)   e_out = (layer 2, which 1, 0 .. H-1)
+ *     Val          e_in = (layer 3, which 0, 0 .. H-1)   e_out of atom i = (layer 3, which 1, element i) of S elements
+ *   (F = fan_in of the first hidden layer, element k of a conv-output draw = x_c element k).  Every e_in / e_out of
+ *   the network is its own (layer, which) stream.  One pass = one call counter; the pass's last combine (or, with the
+ *   fused loss below, its last hidden layer's combine) advances it by one.                                        */
+
+/* One (layer, which) draw of arl_noisy_draws: row r gets f(e_j) of elements j = 0 .. width-1 at f[r pitch + j]; with x
+ * (which 0 only) also xs[r pitch + j] = x[r pitch + j] f(e_j).  width, pitch multiples of 4, pointers 16-byte aligned. */
+typedef struct arl_noisy_draw {
+    float* f;
+    const float* x;             /* or NULL                                                                          */
+    float* xs;                  /* written when x is given                                                          */
+    int32_t width;
+    int32_t pitch;              /* floats between rows of f, x and xs (>= width)                                   */
+    int32_t layer;              /* the generator's layer index                                                      */
+    int32_t which;              /* 0: e_in, 1: e_out                                                                */
+} arl_noisy_draw;
+#define ARL_NOISY_MAX_DRAWS 16
+
+/* The noise of one forward pass as a list of draws in ONE launch (arl_noisy_noise's generalisation: a draw may fill a
+ * column range of a wider buffer -- the two streams' halves of a dueling network's stacked layers).  Reads seed
+ * state[0] and call counter state[1]; does not advance it.  Replaces the rng.normal draws of noisy_layer.py:83-88,
+ * 125-139 for every noisy layer of catdqn_cnn.py:58-99.                                                            */
+int arl_noisy_draws(const int64_t* state, const arl_noisy_draw* draws, int32_t n_draws, int64_t rows,
+                    int32_t rows_per_draw, void* stream);
+
+/* The stacked 2H hidden layer of the dueling network (units 0 .. split-1: hidden_0, split .. units-1: hidden_Val_0,
+ * catdqn_cnn.py:58-66,77-86 as NoisyDenseLayers): y = relu?(P_w + f(e_out) * P_sigma) with P_w the one x W product
+ * over all units (bias b) and P_sigma, per stream, its own (x f(e_in_stream)) W_sigma_stream product (b_sigma):
+ * sigma_lo total rows x split, sigma_hi rows x (units - split).  Every item folded in arl_fold_many's order, then its
+ * bias, as arl_noisy_dense_combine; fein_next / xs_next and state_or_null as there.                                */
+int arl_noisy_duel_combine(const arl_fold_item* w_prod, const float* bias_or_null, const arl_fold_item* sigma_lo,
+                           const arl_fold_item* sigma_hi, const float* b_sigma_or_null, const float* feout, int64_t rows,
+                           int32_t units, int32_t split, int32_t relu, float* y, const float* fein_next_or_null,
+                           float* xs_next_or_null, int64_t* state_or_null, void* stream);
+
+/* arl_noisy_dense_bwd_prep for that layer: g2 = g * f(e_out) written as two contiguous blocks, g2_lo f32[rows][split]
+ * and g2_hi f32[rows][units - split] (the per-stream sigma products' dy); db, db_sigma f32[units] (rows in order). */
+int arl_noisy_duel_bwd_prep(const float* g, const float* feout, int64_t rows, int32_t units, int32_t split,
+                            float* g2_lo, float* g2_hi, float* db, float* db_sigma, void* stream);
+
+/* dx = (dx_w + f(e_in_lo) * dx_sigma_lo) + f(e_in_hi) * dx_sigma_hi, f32[rows][fan_in]: that layer's data gradient
+ * (g W, g2_lo W_sigma_lo, g2_hi W_sigma_hi, each already masked by the rectifier below).  dx may alias dx_w.
+ * fan_in % 4 == 0, 16-byte aligned pointers.                                                                       */
+int arl_noisy_duel_bwd_dx(const float* dx_w, const float* dx_sigma_lo, const float* fein_lo, const float* dx_sigma_hi,
+                          const float* fein_hi, int64_t rows, int32_t fan_in, float* dx, void* stream);
+
+/* A noisy output layer's logits as its two arl_conv2d_fwd_parts products left them, from the source's first row on
+ * (row = (n_actions + dueling) atom_stride floats): logit = [x W + b] + f(e_out) ([x f(e_in) W_sigma] + b_sigma). */
+typedef struct arl_noisy_logit_src {
+    const float* w_part;        /* x W: f32[w_splits][..] partial sums, or (w_splits == 0) finished values (bias in) */
+    const float* bias_or_null;  /* b, added after the fold (w_splits > 0)                                           */
+    const float* s_part;        /* (x f(e_in)) W_sigma, likewise                                                    */
+    const float* b_sigma_or_null;
+    const float* feout;         /* f32[rows][row]: f(e_out)                                                         */
+    int64_t w_split_stride;     /* floats between splits (the fold item's total)                                    */
+    int64_t s_split_stride;
+    int32_t w_splits;           /* 0 .. ARL_NOISY_CATDQN_MAX_SPLITS                                                 */
+    int32_t s_splits;
+} arl_noisy_logit_src;
+#define ARL_NOISY_CATDQN_MAX_SPLITS 128
+
+/* The fused loss launch's limits: splits per product, actions, atoms.  A caller past them runs the unfused pair
+ * (arl_noisy_dense_combine per pass, then arl_catdqn_loss), which takes any split count.                          */
+int arl_noisy_catdqn_loss_limits(int32_t* max_splits, int32_t* max_actions, int32_t* max_atoms);
+
+/* arl_catdqn_loss_parts for a noisy output layer (AtariNoisyNetCatDqnPolicy; cat_dqn.py:40-109 on the logits of
+ * catdqn_cnn.py:67-99 with NoisyDenseLayers): every logit is folded and noised exactly as arl_noisy_dense_combine
+ * (relu 0) computes it, operation for operation, then the dueling merge, softmax, double-DQN selection, projection,
+ * loss, KL and dlogits as arl_catdqn_loss -- the same bits as that pair, in one launch instead of three.  It does
+ * not touch the noise state: a caller that uses it advances each pass's counter in the pass's last hidden combine.
+ * wt_items_or_null / n_wt as arl_catdqn_loss_parts.  ARL_E_RANGE past arl_noisy_catdqn_loss_limits.                 */
+int arl_noisy_catdqn_loss_parts(const arl_noisy_logit_src* pred, const arl_noisy_logit_src* tgt_next,
+                                const arl_noisy_logit_src* pol_next_or_null, const float* z, const uint8_t* actions,
+                                const float* returns, const uint8_t* terminals, const float* is_weights_or_null,
+                                int64_t batch, int32_t n_actions, int32_t n_atoms, int32_t atom_stride, int32_t dueling,
+                                float v_min, float v_max, float gamma_n, float* dlogits, float* loss_rows, float* kl,
+                                const struct arl_dgrad_wt* wt_items_or_null, int32_t n_wt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

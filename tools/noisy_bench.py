@@ -1,8 +1,11 @@
 """Noisy-net DQN against plain DQN on the device: one double-DQN update (forward of the three passes, loss, backward,
 folds; no optimiser step) at batch 32 with the spec-1 CNN, and one served rollout step (the Q network + arl_dqn_act) at
 256 environments, each captured in a hipGraph and replayed.  Prints one JSON line per case.
+--net cat: the same for the categorical networks, dueling, 51 atoms -- AtariNoisyNetCatDqnPolicy (Rainbow's network;
+its update through the fused loss launch, --unfused: through the combines and arl_catdqn_loss, the policy's default)
+against AtariCatDqnPolicy (EpsRainbow's).
 
-    python tools/noisy_bench.py [--iters 200] [--only update|serve]
+    python tools/noisy_bench.py [--iters 200] [--only update|serve] [--net q|cat] [--unfused]
 
 Launches per update: run the update case under `rocprofv3 --kernel-trace --stats -- python tools/noisy_bench.py
 --only update --iters N` and divide the kernel count by the replays (N + warm-up, printed as "replays")."""
@@ -19,15 +22,29 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 DEV = "cuda:0"
 
 
+NET = "q"
+UNFUSED = False
+
+
 def _policy(noisy, n_act=6):
     from accel_rl_amd.policies.atari_cnn_specs import cnn_specs
+    from accel_rl_amd.policies.dqn.atari_cat_dqn_policy import AtariCatDqnPolicy
     from accel_rl_amd.policies.dqn.atari_dqn_policy import AtariDqnPolicy
+    from accel_rl_amd.policies.dqn.atari_noisy_net_cat_dqn_policy import AtariNoisyNetCatDqnPolicy
     from accel_rl_amd.policies.dqn.atari_noisy_net_dqn_policy import AtariNoisyNetDqnPolicy
     from accel_rl_amd.spaces import Discrete, UintBox, EnvSpec
     from accel_rl_amd.util.seed import set_seed
     set_seed(1)
-    p = AtariNoisyNetDqnPolicy(**cnn_specs[1]) if noisy else AtariDqnPolicy(epsilon=0.1, **cnn_specs[1])
+    if NET == "cat":
+        p = (AtariNoisyNetCatDqnPolicy(n_atoms=51, dueling=True, **cnn_specs[1]) if noisy else
+             AtariCatDqnPolicy(epsilon=0.1, n_atoms=51, dueling=True, **cnn_specs[1]))
+    else:
+        p = AtariNoisyNetDqnPolicy(**cnn_specs[1]) if noisy else AtariDqnPolicy(epsilon=0.1, **cnn_specs[1])
     p.initialize(EnvSpec(UintBox((4, 104, 80)), Discrete(n_act)), device=DEV)
+    if NET == "cat":
+        p.incorporate_z(np.linspace(-10, 10, 51, dtype=np.float32))
+        if noisy:
+            p.loss_folds_heads = not UNFUSED
     return p
 
 
@@ -63,9 +80,14 @@ def bench_update(noisy, iters):
     ret = torch.from_numpy(rs.randn(b).astype(np.float32)).to(DEV)
     term = torch.zeros(b, dtype=torch.uint8, device=DEV)
     isw = torch.ones(b, dtype=torch.float32, device=DEV)
-    us, replays = _time_graph(lambda: p.q_loss_and_grads(obs, nxt, act, ret, term, isw, 0.99, 1.0, double_dqn=True),
-                              iters)
-    return dict(case="update", policy="noisy" if noisy else "plain", batch=b, us=round(us, 2), replays=replays)
+    if NET == "cat":
+        def step():
+            return p.cat_loss_and_grads(obs, nxt, act, ret, term, isw, -10., 10., 0.97, double_dqn=True)
+    else:
+        def step():
+            return p.q_loss_and_grads(obs, nxt, act, ret, term, isw, 0.99, 1.0, double_dqn=True)
+    us, replays = _time_graph(step, iters)
+    return dict(case="update", net=NET, policy=_name(noisy), batch=b, us=round(us, 2), replays=replays)
 
 
 def bench_serve(noisy, iters, n_envs=256):
@@ -75,7 +97,11 @@ def bench_serve(noisy, iters, n_envs=256):
     p.host_draws(1, n_envs)
     p.set_step(0)
     us, replays = _time_graph(lambda: p.prob_value(obs), iters)
-    return dict(case="serve", policy="noisy" if noisy else "plain", envs=n_envs, us=round(us, 2), replays=replays)
+    return dict(case="serve", net=NET, policy=_name(noisy), envs=n_envs, us=round(us, 2), replays=replays)
+
+
+def _name(noisy):
+    return ("noisy" + (("-unfused" if UNFUSED else "-fused") if NET == "cat" else "")) if noisy else "plain"
 
 
 def main():
@@ -83,7 +109,11 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--only", choices=["update", "serve"], default=None)
     ap.add_argument("--policy", choices=["noisy", "plain", "both"], default="both")
+    ap.add_argument("--net", choices=["q", "cat"], default="q")
+    ap.add_argument("--unfused", action="store_true")
     a = ap.parse_args()
+    global NET, UNFUSED
+    NET, UNFUSED = a.net, a.unfused
     from accel_rl_amd import _lib
     _lib.load()
     kinds = [True, False] if a.policy == "both" else [a.policy == "noisy"]
