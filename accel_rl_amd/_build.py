@@ -29,7 +29,9 @@ def _stale():
     if os.path.exists(stamp) and open(stamp).read().split("||")[-1] != extra:
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
+    # the sources only: not csrc/_obj, whose directory time moves when the build writes its flags stamp there AFTER
+    # linking (a fresh build would otherwise read as stale, and every later build() would try to rebuild)
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))]
     deps += [os.path.join(ROOT, "include", h) for h in ("accel_rl_hip.h", "accel_rl_hip_dev.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
@@ -40,7 +42,13 @@ def build_extension(force=False, verbose=False):
     if not force and not _stale():
         return LIB_PATH
     import fcntl
-    with open(os.path.join(PKG_DIR, ".build.lock"), "w") as lock:
+    lock_path = os.path.join(PKG_DIR, ".build.lock")
+    try:
+        lock = open(lock_path, "w")
+    except PermissionError as e:
+        raise RuntimeError("libaccel_rl_hip.so is missing or older than its sources, and %s is not writable: build it "
+                           "where the tree can be written (python accel_rl_amd/_build.py)" % PKG_DIR) from e
+    with lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
             if not force and not _stale():          # another rank built it while we waited

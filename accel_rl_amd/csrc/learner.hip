@@ -152,12 +152,13 @@ struct HeadLossArgs {
     float* dout;             // [B][K] gradient wrt (logits, value)
     float* dh;               // [B][hid] gradient wrt h (before the relu mask)
     float* loss_partials;    // [gridDim][4] = pi, v, ent, their sum
-    float* wpart;            // [gridDim][K][hid] this workgroup's share of dW_head = sum_b dout[b] x h[b], or null
+    float* wpart;            // [gridDim][wstride] this workgroup's share of dW_head[K][hid] = sum_b dout[b] x h[b], or null
     float* bpart;            // [gridDim][Kp]     ... of db_head = sum_b dout[b]                (with wpart)
     int batch, hid, n_act, kind, tie_rule;
     float clip_param, v_coeff, ent_coeff;
     int mask_dh;             // dh *= (h > 0): h is a rectifier's output and the caller wants the gradient before it
     int head_blocks;         // workgroups of the head itself (the launch may carry more: see head_kernel)
+    int64_t wstride;         // floats between workgroups' wpart: K * hid rounded up to 4 (arl_fold_many folds float4s)
 };
 
 // one wave per row (looping); lanes split the hidden dimension.  Every per-action
@@ -344,7 +345,7 @@ __global__ __launch_bounds__(256) void head_kernel(HeadLossArgs a, float* __rest
         if (fused_wgrad) {                                               // (the barrier above covers the slices too)
             s_db[wave][lane] = db_lane;
             const float* s0 = s_w + K * hid;
-            float* out = a.wpart + (int64_t)blockIdx.x * K * hid;
+            float* out = a.wpart + (int64_t)blockIdx.x * a.wstride;
             for (int i = threadIdx.x; i < K * hid; i += blockDim.x)
                 out[i] = ((s0[i] + s0[K * hid + i]) + s0[2 * K * hid + i]) + s0[3 * K * hid + i];
             __syncthreads();
@@ -356,55 +357,60 @@ __global__ __launch_bounds__(256) void head_kernel(HeadLossArgs a, float* __rest
     }
 }
 
-// Partial head weight gradient: part[rs][k][c] = sum_{b in row split rs} dout[b][k] h[b][c],
+// Partial head weight gradient: part[rs][k][c] = sum_{b in row split rs} dout[b][k] h[b][c] (splits part_stride apart),
 // k == K holds the bias gradient (h := 1).  grid = (hid/64 column tiles, row splits); the
-// 4 waves of a block take rows b = wave, wave+4, ... of the split; dout rows sit in LDS.
+// 4 waves of a block take rows b = wave, wave+4, ... of the split; dout rows pass through LDS
+// WG_CHUNK at a time (a multiple of the 4 waves: every wave walks its rows in the same order
+// whatever the chunking), so the kernel's LDS does not grow with the batch.
 // Folded over row splits by arl_fold_many (fixed order) => deterministic.
 constexpr int WG_SPLITS = 16;
+constexpr int WG_CHUNK = 256;
 // the head kernel sums the head's weight gradient itself while its four LDS slices [4][K][hid] (next to the staged
 // weights [K][hid]) fit 64 KB: K * hid <= 3 072, e.g. 5 x 512, 19 x 128
 constexpr int FUSED_WGRAD_MAX = 3072;
 
 __global__ __launch_bounds__(256) void head_wgrad_kernel(const float* __restrict__ dout,
                                                          const float* __restrict__ h, int batch,
-                                                         int hid, int K, int Kp, float* __restrict__ part,
-                                                         float* __restrict__ part_b) {
+                                                         int hid, int K, int Kp, int64_t part_stride,
+                                                         float* __restrict__ part, float* __restrict__ part_b) {
     __shared__ float lds[4][K_MAX][64];
-    extern __shared__ __attribute__((aligned(16))) float s_dout[];   // [rows_in_split][K]
+    __shared__ __attribute__((aligned(16))) float s_dout[WG_CHUNK * K_MAX];     // [rows of this chunk][K]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + lane;
     const int rows_per = (batch + WG_SPLITS - 1) / WG_SPLITS;
     const int b0 = blockIdx.y * rows_per;
     const int b1 = (b0 + rows_per < batch) ? b0 + rows_per : batch;
     const int n_rows = b1 > b0 ? b1 - b0 : 0;
-    for (int i = threadIdx.x; i < n_rows * K; i += blockDim.x) s_dout[i] = dout[(int64_t)b0 * K + i];
-    __syncthreads();
     float acc[K_MAX];
 #pragma unroll
     for (int k = 0; k < K_MAX; ++k) acc[k] = 0.f;
-    if (c < hid) {
-        for (int r = wave; r < n_rows; r += 4) {
-            const float hv = h[(int64_t)(b0 + r) * hid + c];
+    float sb = 0.f;                                                    // bias column `lane` (block 0, wave 1)
+    for (int r0 = 0; r0 < n_rows; r0 += WG_CHUNK) {
+        const int nr = n_rows - r0 < WG_CHUNK ? n_rows - r0 : WG_CHUNK;
+        if (r0) __syncthreads();                                       // the previous chunk is read
+        for (int i = threadIdx.x; i < nr * K; i += blockDim.x) s_dout[i] = dout[(int64_t)(b0 + r0) * K + i];
+        __syncthreads();
+        if (c < hid) {
+            for (int r = wave; r < nr; r += 4) {
+                const float hv = h[(int64_t)(b0 + r0 + r) * hid + c];
 #pragma unroll
-            for (int k = 0; k < K_MAX; ++k)
-                if (k < K) acc[k] += s_dout[r * K + k] * hv;
+                for (int k = 0; k < K_MAX; ++k)
+                    if (k < K) acc[k] += s_dout[r * K + k] * hv;
+            }
         }
+        if (blockIdx.x == 0 && wave == 1 && lane < K)
+            for (int r = 0; r < nr; ++r) sb += s_dout[r * K + lane];
     }
 #pragma unroll
     for (int k = 0; k < K_MAX; ++k) lds[wave][k][lane] = acc[k];
     __syncthreads();
     if (wave == 0 && c < hid) {
         for (int k = 0; k < K; ++k)
-            part[((int64_t)blockIdx.y * K + k) * hid + c] =
+            part[(int64_t)blockIdx.y * part_stride + (int64_t)k * hid + c] =
                 ((lds[0][k][lane] + lds[1][k][lane]) + lds[2][k][lane]) + lds[3][k][lane];
     }
     // bias gradient: part_b[split][Kp], column c < K holds sum_b dout[b][c] (Kp = K rounded up to 4, padding zero)
-    if (blockIdx.x == 0 && wave == 1 && lane < Kp) {
-        float sb = 0.f;
-        if (lane < K)
-            for (int r = 0; r < n_rows; ++r) sb += s_dout[r * K + lane];
-        part_b[(int64_t)blockIdx.y * Kp + lane] = sb;
-    }
+    if (blockIdx.x == 0 && wave == 1 && lane < Kp) part_b[(int64_t)blockIdx.y * Kp + lane] = sb;
 }
 
 }  // namespace
@@ -478,10 +484,24 @@ extern "C" int arl_relu_bwd_bias_parts(float* dy, const float* y, int64_t rows, 
 }
 
 static int check_head(int64_t batch, int32_t hid, int32_t n_act) {
-    if (batch <= 0 || hid <= 0 || hid > HID_MAX || n_act <= 0 || n_act > ARL_MAX_ACTIONS) {
-        arl::set_error("head: bad batch/hidden/n_actions");
+    if (batch <= 0 || batch > INT32_MAX || hid <= 0 || hid > HID_MAX || n_act <= 0 || n_act > ARL_MAX_ACTIONS) {
+        arl::set_error("head: need 1 <= batch <= 2^31 - 1, 1 <= hid <= %d, 1 <= n_actions <= %d (ARL_MAX_ACTIONS)",
+                       HID_MAX, ARL_MAX_ACTIONS);
         return ARL_E_RANGE;
     }
+    return 0;
+}
+
+// head_kernel's dynamic LDS ([K][hid] staged weights, + [4][K][hid] slices when fused) reaches (ARL_MAX_ACTIONS + 1) *
+// HID_MAX * 4 = 77 824 B: past 64 KiB the launch opts in explicitly, per launch (the attribute belongs to the CURRENT
+// device's copy of the kernel); sizes up to 64 KiB launch exactly as before
+template <typename Kern>
+static int head_allow_lds(Kern kernel, size_t lds) {
+    static_assert((size_t)K_MAX * HID_MAX * 4 + 2048 <= 160 * 1024, "head_kernel LDS must fit a CU");
+    if (lds <= 65536) return 0;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) { arl::set_error("hipFuncSetAttribute(head_kernel, LDS %zu): %s", lds, hipGetErrorString(e)); return (int)e; }
     return 0;
 }
 
@@ -495,7 +515,13 @@ extern "C" int arl_pg_head_infer(const float* h, const float* w_head, const floa
     a.h = h; a.w_head = w_head; a.b_head = b_head; a.batch = (int)batch; a.hid = hid; a.n_act = n_actions;
     const int grid = (int)((batch + 3) / 4 < 1024 ? (batch + 3) / 4 : 1024);
     const size_t lds = (size_t)(n_actions + 1) * hid * 4;
-#define ARL_HEAD_INFER(HVT_) hipLaunchKernelGGL((head_kernel<false, HVT_>), dim3(grid), dim3(256), lds, (hipStream_t)stream, a, prob, value, arlw::DgradWtArgs{})
+#define ARL_HEAD_INFER(HVT_)                                                                                         \
+    do {                                                                                                             \
+        rc = head_allow_lds(head_kernel<false, HVT_>, lds);                                                          \
+        if (rc) return rc;                                                                                           \
+        hipLaunchKernelGGL((head_kernel<false, HVT_>), dim3(grid), dim3(256), lds, (hipStream_t)stream, a, prob,    \
+                           value, arlw::DgradWtArgs{});                                                              \
+    } while (0)
     if (hid == 512) ARL_HEAD_INFER(8);
     else if (hid == 256) ARL_HEAD_INFER(4);
     else if (hid == 1024) ARL_HEAD_INFER(16);
@@ -535,8 +561,12 @@ extern "C" int arl_pg_head_loss_parts(const float* h, const float* w_head, const
     float* ws = (float*)workspace;
     float* part = ws + 256 * 4;
     const bool fused = K * hid <= FUSED_WGRAD_MAX;
-    float* part_b = part + (fused ? (int64_t)grid : (int64_t)WG_SPLITS) * K * hid;
+    // one split's weight partials [K][hid], padded to a multiple of 4 floats (the fold reads float4s; the padding is
+    // folded but not stored: items3[0].valid)
+    const int64_t kh = (int64_t)K * hid, kh4 = (kh + 3) & ~(int64_t)3;
+    float* part_b = part + (fused ? (int64_t)grid : (int64_t)WG_SPLITS) * kh4;
     if (fused) { a.wpart = part; a.bpart = part_b; }
+    a.wstride = kh4;
     const size_t head_lds = (size_t)(fused ? 5 : 1) * K * hid * 4;
     arlw::DgradWtArgs wt = {};
     int wt_blocks = 0;
@@ -545,7 +575,13 @@ extern "C" int arl_pg_head_loss_parts(const float* h, const float* w_head, const
         if (rc) return rc;
     }
     a.head_blocks = grid;
-#define ARL_HEAD_TRAIN(HVT_) hipLaunchKernelGGL((head_kernel<true, HVT_>), dim3(grid + wt_blocks), dim3(256), head_lds, s, a, (float*)nullptr, (float*)nullptr, wt)
+#define ARL_HEAD_TRAIN(HVT_)                                                                                         \
+    do {                                                                                                             \
+        rc = head_allow_lds(head_kernel<true, HVT_>, head_lds);                                                      \
+        if (rc) return rc;                                                                                           \
+        hipLaunchKernelGGL((head_kernel<true, HVT_>), dim3(grid + wt_blocks), dim3(256), head_lds, s, a,             \
+                           (float*)nullptr, (float*)nullptr, wt);                                                    \
+    } while (0)
     if (hid == 512) ARL_HEAD_TRAIN(8);
     else if (hid == 256) ARL_HEAD_TRAIN(4);
     else if (hid == 1024) ARL_HEAD_TRAIN(16);
@@ -557,17 +593,17 @@ extern "C" int arl_pg_head_loss_parts(const float* h, const float* w_head, const
     // head weight / bias gradient: row-split partials [WG_SPLITS][K][hid] and [WG_SPLITS][Kp]; their folds and the
     // fold of the per-workgroup loss partials [grid][4] are left to arl_fold_many (one launch per backward pass)
     if (!fused) {
-        const int rows_per = ((int)batch + WG_SPLITS - 1) / WG_SPLITS;
-        hipLaunchKernelGGL(head_wgrad_kernel, dim3((hid + 63) / 64, WG_SPLITS), dim3(256),
-                           (size_t)rows_per * K * 4, s, dout, h, (int)batch, (int)hid, K, Kp, part, part_b);
+        hipLaunchKernelGGL(head_wgrad_kernel, dim3((hid + 63) / 64, WG_SPLITS), dim3(256), 0, s, dout, h,
+                           (int)batch, (int)hid, K, Kp, kh4, part, part_b);
         rc = arl::check_launch("head_wgrad_kernel");
         if (rc) return rc;
     }
     const int n_parts = fused ? grid : WG_SPLITS;
-    items3[0].part = part; items3[0].out = dw_head; items3[0].total = (int64_t)K * hid; items3[0].splits = n_parts;
+    items3[0].part = part; items3[0].out = dw_head; items3[0].total = kh4; items3[0].splits = n_parts;
     items3[1].part = part_b; items3[1].out = db_head; items3[1].total = Kp; items3[1].splits = n_parts;
     items3[2].part = ws; items3[2].out = loss4; items3[2].total = 4; items3[2].splits = grid;
-    items3[0].valid = items3[2].valid = 0;
+    items3[0].valid = kh4 != kh ? kh : 0;              // dw_head holds K * hid floats
+    items3[2].valid = 0;
     items3[1].valid = K;                                // db_head holds K floats, the partials are padded to Kp
     return 0;
 }

@@ -329,7 +329,9 @@ int arl_relu_bwd_bias_parts(float* dy, const float* y, int64_t rows, int32_t cha
  * value = h w_v + b_v.  Replaces the output layers of _f_prob_value,
  * accel_rl/policies/pg/atari_cnn_policy.py:63-67 (pg_cnn.py:70-86).
  *   h f32[batch][hid]; w_head f32[n_actions+1][hid] (rows 0..A-1 pi, row A value);
- *   b_head f32[n_actions+1]; prob f32[batch][A]; value f32[batch]               */
+ *   b_head f32[n_actions+1]; prob f32[batch][A]; value f32[batch]
+ * Limits (else ARL_E_RANGE, nothing launched): 1 <= n_actions <= ARL_MAX_ACTIONS (18), 1 <= hid <= 1024,
+ * 1 <= batch <= 2^31 - 1.  Any hid in range (64, 256, 512 and 1024 have specialised kernels).                  */
 int arl_pg_head_infer(const float* h, const float* w_head, const float* b_head, int64_t batch,
                       int32_t hid, int32_t n_actions, float* prob, float* value, void* stream);
 
@@ -361,7 +363,12 @@ int arl_pg_head_infer(const float* h, const float* w_head, const float* b_head, 
  *                       2 adv inside the clip range, bounds included; for comparing against runs of that vintage.
  *   out: dout f32[batch][A+1], dh f32[batch][hid] (before the hidden relu mask),
  *        dw_head f32[A+1][hid], db_head f32[A+1], loss4 f32[4] = pi, v, ent, pi+v+ent
- *   workspace >= arl_pg_head_workspace_bytes()                                  */
+ *        (dw_head, db_head, loss4 16-byte aligned: arl_fold_many writes them)
+ *   workspace >= arl_pg_head_workspace_bytes()
+ * Limits as arl_pg_head_infer (n_actions <= 18, hid <= 1024, 1 <= batch <= 2^31 - 1; else ARL_E_RANGE before any
+ * launch).  The head kernel's LDS holds w_head ((A+1) hid floats, up to 76 KiB) and, while (A+1) hid <= 3 072,
+ * four slices of the weight gradient; past 64 KiB it opts in to the larger size per launch.  The separate weight
+ * gradient kernel (larger (A+1) hid) stages dout in fixed row chunks: its LDS does not grow with the batch.       */
 #define ARL_PPO_TIE_THEANO 0
 #define ARL_PPO_TIE_MATH   1
 #define ARL_PPO_TIE_BOTH   2
@@ -376,8 +383,9 @@ int arl_pg_head_loss(const float* h, const float* w_head, const float* b_head,
                      float* loss4, void* workspace, void* stream);
 /* Same, stopping before the three small folds (dw_head, db_head, loss4): they are described in items3[0..2] for
  * arl_fold_many, so that a backward pass ends in ONE fold launch.  The bias partials are n_actions + 1 rounded
- * up to a multiple of 4 floats in the partials only (items3[1].valid = n_actions + 1); workspace stays live until the
- * fold has run.
+ * up to a multiple of 4 floats in the partials only (items3[1].valid = n_actions + 1), and so are the weight partials,
+ * (n_actions + 1) * hid of them per split (items3[0].valid = (n_actions + 1) * hid where that is not a multiple of 4,
+ * else 0); workspace stays live until the fold has run.
  * wt_items_or_null / n_wt (ABI 4): the same launch also writes these layers' k-contiguous weight copies
  * (arl_conv2d_dgrad_weights below) in extra workgroups -- the backward pass that follows reads them, and this launch is
  * where a minibatch's parameters are final and the CUs are idle: one launch less per minibatch.                     */
