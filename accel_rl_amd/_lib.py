@@ -149,6 +149,7 @@ _SIGNATURES = {
     "arl_ring_append": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp]),
     "arl_gather_scale_obs": (_i32, [_vp, _vp, _i64, _i64, _f32, _vp, _vp]),
     "arl_gather_scale_obs_nhwc": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp]),
+    "arl_traj_minibatch": (_i32, [_vp, _i32, _i32, _i64, C.POINTER(_vp), _i32, _i32, _vp, _vp, C.POINTER(_vp), _vp, _vp]),
     "arl_bias_relu": (_i32, [_vp, _vp, _i64, _i32, _vp]),
     "arl_relu_bwd_workspace_bytes": (_i64, []),
     "arl_relu_bwd_bias_grad": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
@@ -545,6 +546,40 @@ def gather_scale_obs_nhwc(obs, idx, out, scale, stream=None):
     _check(load().arl_gather_scale_obs_nhwc(ptr(obs), ptr(idx), batch, channels, plane, float(scale),
                                             out.data_ptr(), stream_ptr(stream)),
            "arl_gather_scale_obs_nhwc")
+
+
+def traj_minibatch(seg, horizon, state_in, valids, idx, state_out, inv_count=None, stream=None):
+    """One launch (arl_traj_minibatch): idx <- the rows of segments `seg` in time order, state_out[s] <- the rows of
+    state_in[s] stored before step 0 of each chosen segment, inv_count <- 1 / (valid rows of the minibatch).
+    seg i32[n_seg]; state_in: f32 [n_traj * horizon][H] tensors (0 .. 2 of them); valids i8 [n_traj * horizon] or
+    None; idx i32[n_seg * horizon]; state_out: f32 [n_seg][H] tensors.  The caller guarantees seg < n_traj."""
+    _want(seg, torch.int32, "seg")
+    _want(idx, torch.int32, "idx")
+    n_seg, n_state = seg.numel(), len(state_in)
+    if len(state_out) != n_state:
+        raise ValueError("traj_minibatch: %d states in, %d out" % (n_state, len(state_out)))
+    if idx.numel() != n_seg * horizon:
+        raise ValueError("traj_minibatch: idx holds %d rows, not %d segments x %d" % (idx.numel(), n_seg, horizon))
+    hidden, total = 0, None
+    for a, b in zip(state_in, state_out):
+        _want(a, torch.float32, "state_in")
+        _want(b, torch.float32, "state_out")
+        hidden = a.shape[-1]
+        if b.numel() != n_seg * hidden or a.numel() % (hidden * horizon) or total not in (None, a.numel() // hidden):
+            raise ValueError("traj_minibatch: state shapes %s -> %s" % (tuple(a.shape), tuple(b.shape)))
+        total = a.numel() // hidden
+    if valids is not None:
+        _want(valids, torch.int8, "valids")
+        if valids.numel() % horizon or total not in (None, valids.numel()):
+            raise ValueError("traj_minibatch: valids holds %d rows" % valids.numel())
+        total = valids.numel()
+    if inv_count is not None:
+        _want(inv_count, torch.float32, "inv_count")
+    n_traj = (total // horizon) if total is not None else 2 ** 31 // max(horizon, 1) - 1       # (nothing indexed by it)
+    arr = C.c_void_p * max(n_state, 1)
+    sin, sout = arr(*[ptr(a) for a in state_in]), arr(*[ptr(b) for b in state_out])
+    _check(load().arl_traj_minibatch(ptr(seg), n_seg, horizon, n_traj, sin, n_state, hidden, ptr(valids), ptr(idx), sout,
+                                     ptr(inv_count), stream_ptr(stream)), "arl_traj_minibatch")
 
 
 def bias_relu(x, bias, rows, channels, stream=None):

@@ -54,11 +54,17 @@ class AdvActorCriticBase(RLAlgorithm):
         input_names += ["old_%s" % k for k in self._dist_info_keys]
         self._state_info_keys = list(policy.state_info_keys)             # aac_base.py:45-46
         input_names += self._state_info_keys
-        if self._state_info_keys and hasattr(self.optimizer, "prepare_host") and \
+        traj_opt = getattr(self.optimizer, "trajectory_minibatches", False)
+        if self._state_info_keys and not traj_opt and hasattr(self.optimizer, "prepare_host") and \
                 getattr(self.optimizer, "_minibatch_size", None) is not None:
             # the reference's PpoOptimizer slices rows, not trajectories (ppo_optimizer.py:67-75): recurrent
-            # policies are trained with the whole-batch optimizers only
-            raise NotImplementedError("recurrent policies need a whole-batch optimizer (A2C) (INTEGRATION.md, section E)")
+            # policies are trained with the whole-batch optimizers, or with one that draws whole trajectories
+            raise NotImplementedError("recurrent policies need a whole-batch optimizer (A2C) or trajectory minibatches "
+                                      "(TrajPpoOptimizer) (INTEGRATION.md, section E)")
+        if traj_opt and not self._state_info_keys:
+            raise NotImplementedError("%s draws whole-trajectory minibatches for recurrent policies; a feed-forward "
+                                      "policy trains with PpoOptimizer (INTEGRATION.md, section E)"
+                                      % type(self.optimizer).__name__)
         opt_examples = dict(advantages=np.float32(1), returns=np.float32(1))
         if self._use_valids:
             input_names.append("valids")
@@ -66,8 +72,9 @@ class AdvActorCriticBase(RLAlgorithm):
         if not hasattr(policy, "loss_and_grads"):
             raise TypeError("the policy must provide loss_and_grads (HIP forward / backward into its flat "
                             "gradient bucket); got {}".format(type(policy).__name__))
+        extra = dict(horizon=horizon, data_length=sample_size) if traj_opt else dict()
         self.optimizer.initialize(inputs=input_names, losses=self._losses, constraints=None, target=policy,
-                                  lr_mult=self._lr_mult)
+                                  lr_mult=self._lr_mult, **extra)
         self._opt_buf = buffer_with_segs_view(opt_examples, sample_size, horizon, dev)
         self._batch_size = sample_size
         self._mid_batch_reset = mid_batch_reset
@@ -235,7 +242,9 @@ class AdvActorCriticBase(RLAlgorithm):
         every gradient into flat_grads."""
         inv_count = None
         valids = mb.get("valids")
-        if valids is not None:
+        if valids is not None and mb.get("traj") is not None:
+            inv_count = mb["inv_count"]         # of this trajectory minibatch (arl_traj_minibatch)
+        elif valids is not None:
             v = valids if mb.get("idx") is None else valids.index_select(0, mb["idx"].long())
             inv_count = (1. / v.sum(dtype=torch.float32)).reshape(1)
         if self._state_info_keys:

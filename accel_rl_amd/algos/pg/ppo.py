@@ -12,7 +12,7 @@ import torch
 
 from accel_rl_amd.algos.pg.aac_base import AdvActorCriticBase, valids_mean
 from accel_rl_amd.optimizers import update_methods
-from accel_rl_amd.optimizers.single import PpoOptimizer
+from accel_rl_amd.optimizers.single import PpoOptimizer, TrajPpoOptimizer
 from accel_rl_amd.optimizers.sync import SyncPpoOptimizer
 from accel_rl_amd.util import theano_ops
 
@@ -52,6 +52,13 @@ class PPO(BasePPO):
     """Single GPU"""
 
     def __init__(self, OptimizerCls=PpoOptimizer, **kwargs):
+        super().__init__(OptimizerCls=OptimizerCls, **kwargs)
+
+
+class RecurrentPPO(BasePPO):
+    """Single GPU, recurrent policies: minibatches of whole trajectory segments"""
+
+    def __init__(self, OptimizerCls=TrajPpoOptimizer, **kwargs):
         super().__init__(OptimizerCls=OptimizerCls, **kwargs)
 
 

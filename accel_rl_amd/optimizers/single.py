@@ -5,7 +5,7 @@ import torch
 
 from accel_rl_amd import _lib
 
-from accel_rl_amd.optimizers.base import BaseOptimizer, iterate_mb_idxs
+from accel_rl_amd.optimizers.base import BaseOptimizer, iterate_mb_idxs, iterate_traj_idxs
 
 
 class A2cOptimizer(BaseOptimizer):
@@ -155,3 +155,63 @@ class PpoOptimizer(BaseOptimizer):
     @property
     def parallelism_tag(self):
         return "single"
+
+
+class TrajPpoOptimizer(PpoOptimizer):
+    """PPO for recurrent policies: epochs x minibatches of WHOLE trajectory segments (optimizers/util.py:21-32,
+    iterate_traj_idxs; the reference's own PpoOptimizer slices rows and cuts trajectories apart).  `minibatch_size`
+    keeps the reference's meaning -- rows -- so a minibatch is `minibatch_size // horizon` segments.  The host draws
+    the segment numbers (one np.random.shuffle of the segments per epoch); per minibatch one arl_traj_minibatch launch
+    builds the row indices, the segments' stored initial states and 1 / sum(valids) on the device, and the policy's
+    forward / BPTT runs on those rows.  Static shapes, no host synchronisation: captured like PpoOptimizer's call."""
+
+    trajectory_minibatches = True       # AdvActorCriticBase.initialize lets a recurrent policy through
+    corun_update = False                # (a feed-forward-policy feature: the recurrent backward pass offers no hole)
+    _overlap_allreduce = False
+
+    def initialize(self, inputs, losses, constraints, target, givens=None, lr_mult=1, horizon=None, data_length=None):
+        if horizon is None or data_length is None:
+            raise TypeError("TrajPpoOptimizer.initialize needs horizon and data_length (the algorithm passes them)")
+        self._horizon, bs = int(horizon), self._minibatch_size
+        self.check_sizes(bs, int(data_length), self._horizon)
+        super().initialize(inputs, losses, constraints, target, givens=givens, lr_mult=lr_mult)
+        self._seg_host = self._seg_dev = None
+
+    @staticmethod
+    def check_sizes(minibatch_size, data_length, horizon):
+        """iterate_traj_idxs' own condition, checked before the first update, with the numbers."""
+        if horizon < 1 or minibatch_size < horizon or data_length % horizon or minibatch_size % horizon or \
+                data_length % minibatch_size:
+            raise ValueError("trajectory minibatches: minibatch_size (%d) and the batch (%d rows) must be multiples of "
+                             "horizon (%d), and the batch a multiple of minibatch_size" %
+                             (minibatch_size, data_length, horizon))
+
+    def prepare_host(self, data_length):
+        """Segment numbers of every minibatch of ALL epochs into one (pinned) int32 buffer: the same RNG consumption
+        as the reference function (np.random.shuffle of the segments once per epoch, nothing else)."""
+        per = self._minibatch_size // self._horizon
+        flat = [segs for _ in range(self._epochs)
+                for _, segs in iterate_traj_idxs(self._minibatch_size, data_length, self._horizon, self._shuffle)]
+        if getattr(self, "_seg_host", None) is None:
+            self._seg_host = torch.zeros((len(flat), per), dtype=torch.int32)
+            if torch.cuda.is_available():
+                self._seg_host = self._seg_host.pin_memory()
+        self._n_minibatches = len(flat)
+        self._set_updates_per_call(len(flat))
+        self._seg_host.copy_(torch.from_numpy(np.stack(flat).astype(np.int32)))
+
+    def device_updates(self, inputs):
+        data = dict(zip(self._input_names, inputs))
+        if self._seg_dev is None:
+            self._seg_dev = torch.zeros(tuple(self._seg_host.shape), dtype=torch.int32, device=self._target.device)
+        _lib.copy_bytes(self._seg_dev, self._seg_host)
+        losses = []
+        for k in range(self._n_minibatches):
+            losses.append(self._backward(self._losses, self._minibatch(data, self._seg_dev[k])))
+            self._share_grad()
+            self._apply_update(self._avg_factor())
+        return losses, self._recent_grad_norms(self._n_minibatches)
+
+    def _minibatch(self, data, seg):
+        """One arl_traj_minibatch launch: traj_idx, traj_state and inv_count of the chosen segments."""
+        return self._target.traj_minibatch(dict(data, idx=None, traj=seg, horizon=self._horizon))

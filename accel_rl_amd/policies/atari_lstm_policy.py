@@ -150,15 +150,37 @@ class RecurrentCnnPolicy(AtariCnnPolicy):
         return action, infos
 
     # ---- training: BPTT over each environment's segment ----------------------------
+    def traj_minibatch(self, mb):
+        """mb with `traj` (i32[n_seg] segment numbers) and `horizon` -> mb plus what one arl_traj_minibatch launch
+        derives from them: `traj_idx` (the segments' rows in time order), `traj_state` (the stored state before each
+        segment's step 0, one [n_seg, H] tensor per state key) and, with `valids`, `inv_count` (1 / valid rows)."""
+        traj, t_len = mb["traj"], int(mb["horizon"])
+        n_seg = traj.numel()
+        idx = self._buffer(("traj_idx", n_seg, t_len), (n_seg * t_len,), dtype=torch.int32)
+        state = [self._buffer(("traj_state%d" % i, n_seg), (n_seg, self._H)) for i in range(len(self._state_keys))]
+        valids = mb.get("valids")
+        inv = self._buffer(("traj_inv", n_seg, t_len), (1,)) if valids is not None else None
+        _lib.traj_minibatch(traj, t_len, [mb[key] for key in self._state_keys], valids, idx, state, inv)
+        return dict(mb, traj_idx=idx, traj_state=state, inv_count=inv)
+
     def loss_and_grads(self, mb, kind, clip_param, v_loss_coeff, ent_loss_coeff, lr_mult, inv_count=None,
                        tie_rule=_lib.PPO_TIE_THEANO):
         """Whole-batch update (rows env-major = [trajectory][time]); mb additionally carries
-        `horizon` and the stored previous states (only the rows of t = 0 are used)."""
+        `horizon` and the stored previous states (only the rows of t = 0 are used).  With `traj` (i32[n_seg] device
+        tensor of segment numbers) the update runs on those segments only, in that order: a trajectory minibatch
+        (`traj_minibatch`); `inv_count` then defaults to that minibatch's own 1 / sum(valids)."""
         if mb.get("idx") is not None:
             raise NotImplementedError("recurrent training takes whole trajectories: no row minibatches")
         with torch.no_grad():
             t_len, hh, gm, n_state = int(mb["horizon"]), self._H, self._gate_mult, len(self._state_keys)
-            x = self._scaled(mb["observations"])
+            idx = traj_state = None
+            if mb.get("traj") is not None:
+                if "traj_idx" not in mb:
+                    mb = self.traj_minibatch(mb)
+                idx, traj_state = mb["traj_idx"], mb["traj_state"]
+                if inv_count is None and mb.get("valids") is not None:
+                    inv_count = mb["inv_count"]
+            x = self._scaled(mb["observations"]) if idx is None else self._scaled(mb["observations"], idx)
             rows = x.shape[0]
             nb = rows // t_len
             assert nb * t_len == rows
@@ -173,7 +195,7 @@ class RecurrentCnnPolicy(AtariCnnPolicy):
             g_xh = self._geom(rows, self._rec_fan, gm * hh)
             _lib.conv2d_fwd(xf, w[k], w[k + 2], gx, g_xh, False, self._conv_ws)
             sl = lambda a, t: a.view(nb, t_len, -1)[:, t]                                 # noqa: E731  time slice, strided rows
-            init = [sl(mb[key], 0) for key in self._state_keys]
+            init = [sl(mb[key], 0) for key in self._state_keys] if traj_state is None else traj_state
             prev_at = lambda t: init if t == 0 else [sl(s, t - 1) for s in st_all]        # noqa: E731
             hp = self._buffer(("hp", nb), (nb, hh))
             gh = self._buffer(("gh", nb), (nb, gm * hh))
@@ -189,7 +211,7 @@ class RecurrentCnnPolicy(AtariCnnPolicy):
             dh_all = buf("dh_all", hh)
             loss4 = self._buffer(("loss", rows), (4,))
             _lib.pg_head_loss(st_all[0], self.params[kh], self.params[kh + 1], mb["actions"], mb["advantages"],
-                              mb["returns"], mb.get("old_prob"), mb.get("valids"), None, lr_mult, inv_count,
+                              mb["returns"], mb.get("old_prob"), mb.get("valids"), idx, lr_mult, inv_count,
                               self.n_act, kind, clip_param, v_loss_coeff, ent_loss_coeff, dout, dh_all, g[kh],
                               g[kh + 1], loss4, self._loss_ws, tie_rule=tie_rule)
             # ---- backward scan

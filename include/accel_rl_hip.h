@@ -297,6 +297,29 @@ int arl_gather_scale_obs_nhwc(const uint8_t* obs, const int32_t* idx_or_null, in
                               int32_t channels, int32_t plane_bytes, float scale, float* out,
                               void* stream);
 
+/* A minibatch of whole trajectory segments for a recurrent policy, prepared in ONE launch from the segment numbers
+ * (the second value of iterate_traj_idxs, accel_rl/optimizers/util.py:21-32).  The batch is [n_traj_total][horizon]
+ * rows, segment-major.
+ *   idx[j * horizon + t]  = seg[j] * horizon + t                  the chosen segments' rows in time order
+ *   state_out[s][j][:]    = state_in[s][seg[j] * horizon][:]      the stored state BEFORE step 0 of each chosen
+ *                                                                 segment (aac_base.py:157-161: only s[::horizon])
+ *   inv_count[0]          = 1 / #{rows r of idx : valids[r] != 0} as f32; the count is an integer sum, so the result
+ *                           has the same bits every run.  No valid row at all gives 0 (never inf / NaN).  Without
+ *                           valids every row counts: 1 / (n_seg * horizon).
+ *   seg i32[n_seg]; state_in / state_out: HOST arrays of n_state (0 .. 2) device pointers, f32
+ *   [n_traj_total * horizon][hidden] and f32 [n_seg][hidden], 16-byte aligned (else ARL_E_ALIGN; both may be NULL
+ *   with n_state == 0); valids i8[n_traj_total * horizon] or NULL; idx i32[n_seg * horizon]; inv_count f32[1] or
+ *   NULL (not computed).  Segment numbers may repeat.
+ * The CALLER guarantees 0 <= seg[j] < n_traj_total: the numbers live on the device, the host cannot check them and
+ * the kernel clamps nothing (and asserts nothing).
+ * Null pointers: ARL_E_ARG.  ARL_E_RANGE, nothing launched and no output written: n_seg < 1, horizon < 1,
+ * n_traj_total < 1, n_state outside 0 .. 2, hidden % 4 != 0, hidden > 1024, n_seg * horizon > 2^31 - 1 or
+ * n_traj_total * horizon > 2^31 - 1 (row numbers are int32).  One workgroup per segment: a latency-bound launch.  */
+int arl_traj_minibatch(const int32_t* seg, int32_t n_seg, int32_t horizon, int64_t n_traj_total,
+                       const float* const* state_in, int32_t n_state, int32_t hidden,
+                       const int8_t* valids_or_null, int32_t* idx, float* const* state_out,
+                       float* inv_count_or_null, void* stream);
+
 /* x[rows][channels] = relu(x + bias[c]) in place: the bias + rectify of Lasagne's
  * Conv2DLayer / DenseLayer (accel_rl/policies/pg/networks/pg_cnn.py:47-68) on a
  * channels-last activation.  channels % 4 == 0.                                 */
