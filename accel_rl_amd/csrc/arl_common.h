@@ -43,3 +43,15 @@ inline unsigned stream_grid(int64_t work_items, int per_block) {
             return (code);                      \
         }                                       \
     } while (0)
+
+// Limits shared by the six recurrent-cell entry points (csrc/lstm.hip, csrc/gru.hip; stated in accel_rl_hip.h):
+// host-side comparisons before the launch, no device work.
+#define ARL_CELL_SIZES(batch, hidden)                                                                          \
+    do {                                                                                                       \
+        ARL_REQUIRE((batch) >= 1 && (batch) <= ARL_CELL_MAX_BATCH, ARL_E_RANGE, "1 <= batch <= 2^24");         \
+        ARL_REQUIRE((hidden) >= 1 && (hidden) <= ARL_CELL_MAX_HIDDEN, ARL_E_RANGE, "1 <= hidden <= 2^20");     \
+    } while (0)
+// the row stride of a non-null strided array of more than one row: width <= stride <= 2^28
+#define ARL_CELL_STRIDE(p, stride, width, batch)                                                               \
+    ARL_REQUIRE(!(p) || (batch) == 1 || ((stride) >= (int64_t)(width) && (stride) <= ARL_CELL_MAX_STRIDE),    \
+                ARL_E_RANGE, #stride ": row width <= stride <= 2^28")

@@ -8,7 +8,7 @@
 //   r = s(gx_r + gh_r); u = s(gx_u + gh_u); c = tanh(gx_c + r * gh_c); h = (1 - u) h_prev + u c
 //   saved[B][4H] = r, u, c, gh_c
 //   bwd: du = dh (c - h_prev); dc = dh u; dpc = dc (1 - c^2); dpu = du u (1 - u);
-//        dpr = dpc gh_c r (1 - r);  dgx = [dpr, dpu, dpc];  dgh = [dpr, dpu, dpc r];
+//        dpr = dpc (gh_c (r (1 - r)));  dgx = [dpr, dpu, dpc];  dgh = [dpr, dpu, dpc r];
 //        dh_prev (direct part) = dh (1 - u)        (+ dgh W_h^T, the caller's dense product)
 // RNN: h = tanh(gx + gh); bwd: dpre = dh (1 - h^2)
 
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(const GruBwdArgs a) {
         const float hp = a.h_prev[b * a.hprev_stride + j];
         const float dpc = dh * u * (1.f - c * c);
         const float dpu = dh * (c - hp) * u * (1.f - u);
-        const float dpr = dpc * ghc * r * (1.f - r);
+        const float dpr = dpc * (ghc * (r * (1.f - r)));     // r (1 - r) == 0 first: dpc ghc may overflow
         float* dgx = a.dgx + b * a.dgx_stride;
         float* dgh = a.dgh + b * a.dgh_stride;
         dgx[j] = dpr; dgx[H + j] = dpu; dgx[2 * H + j] = dpc;
@@ -137,7 +137,11 @@ extern "C" int arl_gru_cell_fwd(const float* gx, int64_t gx_stride, const float*
                                 int64_t hprev_stride, int64_t batch, int32_t hidden, float* h_out, int64_t h_stride,
                                 float* saved_or_null, int64_t saved_stride, void* stream) {
     ARL_REQUIRE(gx && gh && h_prev && h_out, ARL_E_ARG, "null pointer");
-    ARL_REQUIRE(batch > 0 && hidden > 0, ARL_E_RANGE, "bad batch / hidden");
+    ARL_CELL_SIZES(batch, hidden);
+    ARL_CELL_STRIDE(gx, gx_stride, 3 * (int64_t)hidden, batch);
+    ARL_CELL_STRIDE(h_prev, hprev_stride, hidden, batch);
+    ARL_CELL_STRIDE(h_out, h_stride, hidden, batch);
+    ARL_CELL_STRIDE(saved_or_null, saved_stride, 4 * (int64_t)hidden, batch);
     GruArgs a = {gx, gh, h_prev, h_out, saved_or_null, batch, hidden, gx_stride, hprev_stride, h_stride, saved_stride};
     hipLaunchKernelGGL(gru_fwd_kernel, dim3(arl::stream_grid(batch * hidden, 256)), dim3(256), 0, (hipStream_t)stream, a);
     return arl::check_launch("gru_fwd_kernel");
@@ -149,7 +153,12 @@ extern "C" int arl_gru_cell_bwd(const float* dh_or_null, int64_t dh_stride, cons
                                 float* dgx, int64_t dgx_stride, float* dgh, int64_t dgh_stride, float* dh_prev,
                                 void* stream) {
     ARL_REQUIRE(saved && h_prev && dgx && dgh && dh_prev, ARL_E_ARG, "null pointer");
-    ARL_REQUIRE(batch > 0 && hidden > 0, ARL_E_RANGE, "bad batch / hidden");
+    ARL_CELL_SIZES(batch, hidden);
+    ARL_CELL_STRIDE(dh_or_null, dh_stride, hidden, batch);
+    ARL_CELL_STRIDE(saved, saved_stride, 4 * (int64_t)hidden, batch);
+    ARL_CELL_STRIDE(h_prev, hprev_stride, hidden, batch);
+    ARL_CELL_STRIDE(dgx, dgx_stride, 3 * (int64_t)hidden, batch);
+    ARL_CELL_STRIDE(dgh, dgh_stride, 3 * (int64_t)hidden, batch);
     GruBwdArgs a = {dh_or_null, dh_rec_or_null, dh_dir_or_null, saved, h_prev, dgx, dgh, dh_prev, batch, hidden,
                     dh_stride, saved_stride, hprev_stride, dgx_stride, dgh_stride};
     hipLaunchKernelGGL(gru_bwd_kernel, dim3(arl::stream_grid(batch * hidden, 256)), dim3(256), 0, (hipStream_t)stream, a);
@@ -159,7 +168,9 @@ extern "C" int arl_gru_cell_bwd(const float* dh_or_null, int64_t dh_stride, cons
 extern "C" int arl_rnn_cell_fwd(const float* gx, int64_t gx_stride, const float* gh, int64_t batch, int32_t hidden,
                                 float* h_out, int64_t h_stride, void* stream) {
     ARL_REQUIRE(gx && gh && h_out, ARL_E_ARG, "null pointer");
-    ARL_REQUIRE(batch > 0 && hidden > 0, ARL_E_RANGE, "bad batch / hidden");
+    ARL_CELL_SIZES(batch, hidden);
+    ARL_CELL_STRIDE(gx, gx_stride, hidden, batch);
+    ARL_CELL_STRIDE(h_out, h_stride, hidden, batch);
     RnnArgs a = {gx, gh, h_out, batch, hidden, gx_stride, h_stride};
     hipLaunchKernelGGL(rnn_fwd_kernel, dim3(arl::stream_grid(batch * hidden, 256)), dim3(256), 0, (hipStream_t)stream, a);
     return arl::check_launch("rnn_fwd_kernel");
@@ -169,7 +180,10 @@ extern "C" int arl_rnn_cell_bwd(const float* dh_or_null, int64_t dh_stride, cons
                                 const float* h_out, int64_t h_stride, int64_t batch, int32_t hidden, float* dpre,
                                 int64_t dpre_stride, void* stream) {
     ARL_REQUIRE(h_out && dpre, ARL_E_ARG, "null pointer");
-    ARL_REQUIRE(batch > 0 && hidden > 0, ARL_E_RANGE, "bad batch / hidden");
+    ARL_CELL_SIZES(batch, hidden);
+    ARL_CELL_STRIDE(dh_or_null, dh_stride, hidden, batch);
+    ARL_CELL_STRIDE(h_out, h_stride, hidden, batch);
+    ARL_CELL_STRIDE(dpre, dpre_stride, hidden, batch);
     RnnBwdArgs a = {dh_or_null, dh_rec_or_null, h_out, dpre, batch, hidden, dh_stride, h_stride, dpre_stride};
     hipLaunchKernelGGL(rnn_bwd_kernel, dim3(arl::stream_grid(batch * hidden, 256)), dim3(256), 0, (hipStream_t)stream, a);
     return arl::check_launch("rnn_bwd_kernel");

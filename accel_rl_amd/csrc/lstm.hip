@@ -93,7 +93,12 @@ extern "C" int arl_lstm_cell_fwd(const float* gx, int64_t gx_stride, const float
                                  float* c_out, int64_t c_stride, float* gates_or_null, int64_t gates_stride,
                                  void* stream) {
     ARL_REQUIRE(gx && c_prev && h_out && c_out, ARL_E_ARG, "null pointer");
-    ARL_REQUIRE(batch > 0 && hidden > 0, ARL_E_RANGE, "bad batch / hidden");
+    ARL_CELL_SIZES(batch, hidden);
+    ARL_CELL_STRIDE(gx, gx_stride, 4 * (int64_t)hidden, batch);
+    ARL_CELL_STRIDE(c_prev, cprev_stride, hidden, batch);
+    ARL_CELL_STRIDE(h_out, h_stride, hidden, batch);
+    ARL_CELL_STRIDE(c_out, c_stride, hidden, batch);
+    ARL_CELL_STRIDE(gates_or_null, gates_stride, 4 * (int64_t)hidden, batch);
     LstmArgs a = {gx, gh_or_null, c_prev, h_out, c_out, gates_or_null, batch, hidden,
                   gx_stride, cprev_stride, h_stride, c_stride, gates_stride};
     hipLaunchKernelGGL(lstm_fwd_kernel, dim3(arl::stream_grid(batch * hidden, 256)), dim3(256), 0, (hipStream_t)stream, a);
@@ -106,7 +111,12 @@ extern "C" int arl_lstm_cell_bwd(const float* dh_or_null, int64_t dh_stride, con
                                  int64_t batch, int32_t hidden, float* dgates, int64_t dgates_stride,
                                  float* dc_prev, void* stream) {
     ARL_REQUIRE(gates && c_prev && c_out && dgates && dc_prev, ARL_E_ARG, "null pointer");
-    ARL_REQUIRE(batch > 0 && hidden > 0, ARL_E_RANGE, "bad batch / hidden");
+    ARL_CELL_SIZES(batch, hidden);
+    ARL_CELL_STRIDE(dh_or_null, dh_stride, hidden, batch);
+    ARL_CELL_STRIDE(gates, gates_stride, 4 * (int64_t)hidden, batch);
+    ARL_CELL_STRIDE(c_prev, cprev_stride, hidden, batch);
+    ARL_CELL_STRIDE(c_out, c_stride, hidden, batch);
+    ARL_CELL_STRIDE(dgates, dgates_stride, 4 * (int64_t)hidden, batch);
     LstmBwdArgs a = {dh_or_null, dh_rec_or_null, dc_next_or_null, gates, c_prev, c_out, dgates, dc_prev, batch, hidden,
                      dh_stride, gates_stride, cprev_stride, c_stride, dgates_stride};
     hipLaunchKernelGGL(lstm_bwd_kernel, dim3(arl::stream_grid(batch * hidden, 256)), dim3(256), 0, (hipStream_t)stream, a);

@@ -44,8 +44,8 @@ class RecurrentCnnPolicy(AtariCnnPolicy):
         super().__init__(conv_filters, conv_filter_sizes, conv_strides, conv_pads, hidden_sizes=hidden_sizes,
                          pixel_scale=pixel_scale, initial_param_values=initial_param_values)
         self._H = int(hidden_sizes[0])
-        if self._H % 4 or self._H > 1024:
-            raise NotImplementedError("recurrent width must be a multiple of 4 and <= 1024")
+        if self._H < 4 or self._H % 4 or self._H > 1024:
+            raise NotImplementedError("recurrent width must be a multiple of 4 and <= 1024 (4 .. 1024), got %d" % self._H)
 
     recurrent = property(lambda self: True)
     state_info_keys = property(lambda self: list(self._state_keys))

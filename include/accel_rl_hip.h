@@ -779,17 +779,39 @@ int arl_dqn_loss(const float* q, const float* tgt_next_q, const float* pol_next_
  * LSTM cell of the recurrent policies
  * ------------------------------------------------------------------------- */
 
+/* Limits of the six cell entry points below (arl_{lstm,gru,rnn}_cell_{fwd,bwd}), checked on the host before any launch;
+ * a refused call launches nothing and writes no output:
+ *   - a mandatory pointer NULL: ARL_E_ARG;
+ *   - 1 <= batch <= ARL_CELL_MAX_BATCH (2^24) and 1 <= hidden <= ARL_CELL_MAX_HIDDEN (2^20), else ARL_E_RANGE.  The
+ *     kernels index a row with int (at most 4 hidden - 1 < 2^22) and rows / elements with int64_t
+ *     (batch * hidden <= 2^44, batch * stride <= 2^52): no index of an accepted call overflows;
+ *   - every *_stride is the element distance between consecutive rows of its array.  With batch > 1 the stride of
+ *     every non-NULL strided array must be at least the row it addresses (4 hidden, 3 hidden or hidden, named per
+ *     argument below) and at most ARL_CELL_MAX_STRIDE (2^28), else ARL_E_RANGE: rows may be padded, never overlap.
+ *     With batch == 1 no stride is used and none is checked (a one-row tensor's row stride is arbitrary); the stride
+ *     of a NULL optional array is ignored.
+ *   - arrays without a stride argument are contiguous ([batch][row width]).
+ * Every thread reads and writes only its own element (b, j) of every array, so an output may be the same buffer as an
+ * input of the same shape and stride; the policies rely on dc_prev == dc_next (LSTM) and dh_prev == dh_dir (GRU).
+ * Saturated gates give finite results: a sigmoid of exactly 0 or 1 and a tanh of exactly +-1 have zero gradient.   */
+#define ARL_CELL_MAX_BATCH  ((int64_t)1 << 24)
+#define ARL_CELL_MAX_HIDDEN (1 << 20)
+#define ARL_CELL_MAX_STRIDE ((int64_t)1 << 28)
+
 /* Elementwise part of FastLstmLayer.step, accel_rl/policies/layers.py:331-346: gate order
  * f, i, c~, o; f, i, o = sigmoid, c~ = tanh; c = f c_prev + i c~; h = o tanh(c).  gx = x W_x + b and
- * gh = h_prev W_h are the callers' dense products (gh may be NULL = zero).  Every *_stride is the
- * element distance between consecutive rows, so a time slice of a [trajectory][time] batch can be
- * addressed in place.  gates (optional) receives the activated gates for the backward pass. */
+ * gh = h_prev W_h are the callers' dense products (gh may be NULL = zero; contiguous [batch][4 hidden]).  Every
+ * *_stride is the element distance between consecutive rows, so a time slice of a [trajectory][time] batch can be
+ * addressed in place.  gates (optional) receives the activated gates for the backward pass.
+ * Rows: gx, gates 4 hidden; c_prev, h_out, c_out hidden.  Limits: see above. */
 int arl_lstm_cell_fwd(const float* gx, int64_t gx_stride, const float* gh_or_null, const float* c_prev,
                       int64_t cprev_stride, int64_t batch, int32_t hidden, float* h_out, int64_t h_stride,
                       float* c_out, int64_t c_stride, float* gates_or_null, int64_t gates_stride, void* stream);
 
 /* Backward of the above for one time step: dh (from the layers above, strided) + dh_rec (from step
- * t+1, contiguous) and dc_next -> pre-activation gate gradients dgates[B][4H] and dc_prev. */
+ * t+1, contiguous) and dc_next (contiguous) -> pre-activation gate gradients dgates[B][4H] and dc_prev (contiguous).
+ * Each of dh, dh_rec, dc_next may be NULL (= zero); with all three NULL dgates and dc_prev are all zero.  dc_prev may
+ * be dc_next.  Rows: gates, dgates 4 hidden; dh, c_prev, c_out hidden.  Limits: see above. */
 int arl_lstm_cell_bwd(const float* dh_or_null, int64_t dh_stride, const float* dh_rec_or_null,
                       const float* dc_next_or_null, const float* gates, int64_t gates_stride,
                       const float* c_prev, int64_t cprev_stride, const float* c_out, int64_t c_stride,
@@ -798,23 +820,27 @@ int arl_lstm_cell_bwd(const float* dh_or_null, int64_t dh_stride, const float* d
 
 /* GRU cell (GruLayer.step, accel_rl/policies/layers.py:163-168), gate order r, u, c in the 3H-wide
  * arrays: r = s(gx_r + gh_r); u = s(gx_u + gh_u); c = tanh(gx_c + r gh_c); h = (1 - u) h_prev + u c.
- * gx = x [W_xr W_xu W_xc] + b, gh = h_prev [W_hr W_hu W_hc] are the callers' dense products.
- * saved (optional, [B][4H]) receives r, u, c, gh_c for the backward pass. */
+ * gx = x [W_xr W_xu W_xc] + b, gh = h_prev [W_hr W_hu W_hc] (contiguous [batch][3 hidden]) are the callers' dense
+ * products.  saved (optional, [B][4H]) receives r, u, c, gh_c for the backward pass.
+ * Rows: gx 3 hidden; saved 4 hidden; h_prev, h_out hidden.  Limits: see above. */
 int arl_gru_cell_fwd(const float* gx, int64_t gx_stride, const float* gh, const float* h_prev,
                      int64_t hprev_stride, int64_t batch, int32_t hidden, float* h_out, int64_t h_stride,
                      float* saved_or_null, int64_t saved_stride, void* stream);
 
 /* Backward of one GRU step: dh (layers above, strided) + dh_rec + dh_dir (both contiguous, from
- * step t+1) -> dgx[B][3H] (gradient wrt gx), dgh[B][3H] (wrt gh; its c block carries the factor r)
- * and dh_prev[B][H] = the direct part dh (1 - u); the caller adds dgh W_h^T. */
+ * step t+1; each of the three may be NULL = zero) -> dgx[B][3H] (gradient wrt gx), dgh[B][3H] (wrt gh; its c block
+ * carries the factor r) and dh_prev[B][H] (contiguous) = the direct part dh (1 - u); the caller adds dgh W_h^T.
+ * dh_prev may be dh_dir.  The r column is dpc (gh_c (r (1 - r))): a saturated r gives 0 whatever gh_c is.
+ * Rows: saved 4 hidden; dgx, dgh 3 hidden; dh, h_prev hidden.  Limits: see above. */
 int arl_gru_cell_bwd(const float* dh_or_null, int64_t dh_stride, const float* dh_rec_or_null,
                      const float* dh_dir_or_null, const float* saved, int64_t saved_stride,
                      const float* h_prev, int64_t hprev_stride, int64_t batch, int32_t hidden,
                      float* dgx, int64_t dgx_stride, float* dgh, int64_t dgh_stride, float* dh_prev,
                      void* stream);
 
-/* Plain recurrent cell (RecurrentLayer.step, layers.py:80-82): h = tanh(gx + gh), and its backward
- * dpre = (dh + dh_rec) (1 - h^2). */
+/* Plain recurrent cell (RecurrentLayer.step, layers.py:80-82): h = tanh(gx + gh) (gh contiguous), and its backward
+ * dpre = (dh + dh_rec) (1 - h^2) (dh strided, dh_rec contiguous, either may be NULL = zero).  Every row is hidden
+ * wide.  Limits: see above. */
 int arl_rnn_cell_fwd(const float* gx, int64_t gx_stride, const float* gh, int64_t batch, int32_t hidden,
                      float* h_out, int64_t h_stride, void* stream);
 int arl_rnn_cell_bwd(const float* dh_or_null, int64_t dh_stride, const float* dh_rec_or_null,
