@@ -201,6 +201,12 @@ _SIGNATURES = {
     "arl_gru_cell_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp]),
     "arl_rnn_cell_fwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp]),
     "arl_rnn_cell_bwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp]),
+    "arl_seq_handover": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "arl_lstm_cell_bwd_reset": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp,
+                                       _vp, _vp, _i64, _i64, _vp]),
+    "arl_gru_cell_bwd_reset": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp,
+                                      _vp, _vp, _i64, _i64, _vp]),
+    "arl_rnn_cell_bwd_reset": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _vp]),
     "arl_opt_step": (_i32, [C.POINTER(ArlOptState), _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
     "arl_opt_step_noclip": (_i32, [C.POINTER(ArlOptState), _i32, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp]),
     "arl_opt_finish": (_i32, [C.POINTER(ArlOptState), _i32, _f32, _vp, _vp, _vp]),
@@ -1069,6 +1075,64 @@ def rnn_cell_bwd(dh, dh_rec, h_out, dpre, stream=None):
     (pdh, sdh), (ph, sh), (pd, sd) = _rows(dh), _rows(h_out), _rows(dpre)
     _check(load().arl_rnn_cell_bwd(pdh, sdh, ptr(dh_rec), ph, sh, batch, hidden, pd, sd, stream_ptr(stream)),
            "arl_rnn_cell_bwd")
+
+
+# ---------------------------------------------------------------------------
+# reset-aware BPTT (csrc/handover.hip and the *_cell_bwd_reset entry points of csrc/lstm.hip, csrc/gru.hip).
+# flags = (reset u8[rows of the full batch], idx i32 row map or None, row0, row_step): launch row b reads the flag of
+# compact row row0 + b * row_step (include/accel_rl_hip.h).
+# ---------------------------------------------------------------------------
+
+def _flags(flags, batch):
+    reset, idx, row0, row_step = flags
+    if reset.dtype == torch.bool:
+        reset = reset.view(torch.uint8)
+    _want(reset, torch.uint8, "reset")
+    last = row0 + (batch - 1) * row_step
+    if idx is not None:
+        _want(idx, torch.int32, "idx")
+        if not 0 <= row0 <= last < idx.numel():
+            raise ValueError("flag rows %d .. %d outside the row map's %d rows" % (row0, last, idx.numel()))
+    elif not 0 <= row0 <= last < reset.numel():
+        raise ValueError("flag rows %d .. %d outside the %d flags" % (row0, last, reset.numel()))
+    return ptr(reset), ptr(idx), row0, row_step
+
+
+def seq_handover(h_prev, c_prev, flags, hp, hprev_out, cprev_out=None, stream=None):
+    """hp, hprev_out <- h_prev and cprev_out <- c_prev where the row's flag is clear, zero where it is set
+    (arl_seq_handover: the state of step t-1 handed to step t; flags address the rows of step t-1)."""
+    batch, hidden = h_prev.shape
+    (ph, sh), (pc, sc), (po, so), (pco, sco) = _rows(h_prev), _rows(c_prev), _rows(hprev_out), _rows(cprev_out)
+    assert tuple(hp.shape) == (batch, hidden) and hp.dtype == torch.float32
+    pr, pi, row0, step = _flags(flags, batch)
+    _check(load().arl_seq_handover(ph, sh, pc, sc, pr, pi, row0, step, batch, hidden, ptr(hp), po, so, pco, sco,
+                                   stream_ptr(stream)), "arl_seq_handover")
+
+
+def lstm_cell_bwd_reset(dh, dh_rec, dc_next, gates, c_prev, c_out, dgates, dc_prev, flags, stream=None):
+    batch, hidden = c_prev.shape
+    (pdh, sdh), (pg, sg), (pcp, scp), (pc, sc), (pdg, sdg) = _rows(dh), _rows(gates), _rows(c_prev), _rows(c_out), _rows(dgates)
+    pr, pi, row0, step = _flags(flags, batch)
+    _check(load().arl_lstm_cell_bwd_reset(pdh, sdh, ptr(dh_rec), ptr(dc_next), pg, sg, pcp, scp, pc, sc, batch, hidden,
+                                          pdg, sdg, ptr(dc_prev), pr, pi, row0, step, stream_ptr(stream)),
+           "arl_lstm_cell_bwd_reset")
+
+
+def gru_cell_bwd_reset(dh, dh_rec, dh_dir, saved, h_prev, dgx, dgh, dh_prev, flags, stream=None):
+    batch, hidden = h_prev.shape
+    (pdh, sdh), (ps, ss), (php, shp), (pgx, sgx), (pgh, sgh) = _rows(dh), _rows(saved), _rows(h_prev), _rows(dgx), _rows(dgh)
+    pr, pi, row0, step = _flags(flags, batch)
+    _check(load().arl_gru_cell_bwd_reset(pdh, sdh, ptr(dh_rec), ptr(dh_dir), ps, ss, php, shp, batch, hidden, pgx, sgx,
+                                         pgh, sgh, ptr(dh_prev), pr, pi, row0, step, stream_ptr(stream)),
+           "arl_gru_cell_bwd_reset")
+
+
+def rnn_cell_bwd_reset(dh, dh_rec, h_out, dpre, flags, stream=None):
+    batch, hidden = h_out.shape
+    (pdh, sdh), (ph, sh), (pd, sd) = _rows(dh), _rows(h_out), _rows(dpre)
+    pr, pi, row0, step = _flags(flags, batch)
+    _check(load().arl_rnn_cell_bwd_reset(pdh, sdh, ptr(dh_rec), ph, sh, batch, hidden, pd, sd, pr, pi, row0, step,
+                                         stream_ptr(stream)), "arl_rnn_cell_bwd_reset")
 
 
 # ---------------------------------------------------------------------------

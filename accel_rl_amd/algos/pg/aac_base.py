@@ -32,7 +32,7 @@ def valids_mean(expression, valids=None):
 class AdvActorCriticBase(RLAlgorithm):
 
     def __init__(self, discount, gae_lambda, v_loss_coeff=1, ent_loss_coeff=0.01,
-                 standardize_adv=False, lr_schedule=None, promo="nep50", use_graph=True):
+                 standardize_adv=False, lr_schedule=None, promo="nep50", use_graph=True, bptt_resets=False):
         if lr_schedule is not None and lr_schedule not in LR_SCHEDULES:
             raise ValueError("Unrecognized lr_schedule: {}, should be None (for constant) or "
                              "in: {}".format(lr_schedule, LR_SCHEDULES))
@@ -41,14 +41,24 @@ class AdvActorCriticBase(RLAlgorithm):
         # promo: numeric contract of the return / advantage scans (include/accel_rl_hip.h): "nep50" / "legacy" = the
         # reference's arithmetic bit for bit under numpy >= 2 / 1.x; "assoc" = wavefront suffix scan, within 1e-5
         self._promo = dict(nep50=_lib.PROMO_NEP50, legacy=_lib.PROMO_LEGACY, assoc=_lib.PROMO_ASSOC)[promo]
+        # bptt_resets (not a reference argument): train a recurrent policy under mid_batch_reset=True with reset-aware
+        # BPTT -- every row is used, no `valids`; the reset flags go to the policy as mb["resets"].
+        # No effect under mid_batch_reset=False or with a feed-forward policy.
 
     def initialize(self, policy, env_spec, sample_size, horizon, mid_batch_reset):
-        if mid_batch_reset and policy.recurrent:
-            raise NotImplementedError
+        self._use_resets = bool(mid_batch_reset and policy.recurrent)
+        if self._use_resets and not self.bptt_resets:
+            raise NotImplementedError("a recurrent policy under mid_batch_reset=True trains only with reset-aware BPTT: "
+                                      "construct the algorithm with bptt_resets=True (INTEGRATION.md, section E); the "
+                                      "reference refuses this combination (aac_base.py:46)")
+        if self._use_resets and not getattr(policy, "supports_bptt_resets", False):
+            raise NotImplementedError("bptt_resets=True with mid_batch_reset=True: %s cannot take the reset flags "
+                                      "(no `supports_bptt_resets = True`; its loss_and_grads must honour mb['resets'])"
+                                      % type(policy).__name__)
         dev = policy.device
         self.policy = policy
         self._lr_mult = torch.ones(1, dtype=torch.float32, device=dev)
-        self._use_valids = not (mid_batch_reset and not policy.recurrent)   # aac_base.py:53-58
+        self._use_valids = not mid_batch_reset                          # aac_base.py:53-58 (there: feed-forward only)
         self._dist_info_keys = policy.distribution.dist_info_keys
         input_names = ["observations", "actions", "advantages", "returns", "old_value"]
         input_names += ["old_%s" % k for k in self._dist_info_keys]
@@ -69,6 +79,8 @@ class AdvActorCriticBase(RLAlgorithm):
         if self._use_valids:
             input_names.append("valids")
             opt_examples["valids"] = np.int8(1)
+        if self._use_resets:
+            input_names.append("resets")
         if not hasattr(policy, "loss_and_grads"):
             raise TypeError("the policy must provide loss_and_grads (HIP forward / backward into its flat "
                             "gradient bucket); got {}".format(type(policy).__name__))
@@ -233,6 +245,10 @@ class AdvActorCriticBase(RLAlgorithm):
         values += tuple(agent_infos[k] for k in self._state_info_keys)
         if self._use_valids:
             values += (opt_data["valids"],)
+        if self._use_resets:
+            # after which rows the sampler zeroed the state: the expression process_samples reads for `valids`
+            # (`dones` alone is wrong with episodic lives: a lost life is done = 1 without a reset)
+            values += (samples_data["env_infos"].get("need_reset", samples_data["dones"]),)
         return values
 
     # ---- loss graph (aac_base.py:60-70) ---------------------------------------

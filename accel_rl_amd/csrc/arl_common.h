@@ -34,6 +34,20 @@ inline unsigned stream_grid(int64_t work_items, int per_block) {
     return (unsigned)b;
 }
 
+// Reset flags of the rows of one time step (reset-aware BPTT: csrc/handover.hip and the *_cell_bwd_reset kernels).
+// Row b of the launch is compact row row0 + b * row_step of a [trajectory][time] batch (row0 = the time step,
+// row_step = the horizon); its flag is reset[idx ? idx[compact row] : compact row], so a trajectory minibatch's row
+// map (arl_traj_minibatch's idx) addresses the full batch's flags in place.
+struct CellFlags {
+    const uint8_t* reset;
+    const int32_t* idx;
+    int64_t row0, row_step;
+    __device__ __forceinline__ bool at(int64_t b) const {
+        const int64_t r = row0 + b * row_step;
+        return reset[idx ? (int64_t)idx[r] : r] != 0;
+    }
+};
+
 }  // namespace arl
 
 #define ARL_REQUIRE(cond, code, msg)            \
@@ -55,3 +69,8 @@ inline unsigned stream_grid(int64_t work_items, int per_block) {
 #define ARL_CELL_STRIDE(p, stride, width, batch)                                                               \
     ARL_REQUIRE(!(p) || (batch) == 1 || ((stride) >= (int64_t)(width) && (stride) <= ARL_CELL_MAX_STRIDE),    \
                 ARL_E_RANGE, #stride ": row width <= stride <= 2^28")
+// the flag rows of a step (arl::CellFlags): 0 <= row0, 1 <= row_step, last compact row <= 2^31 - 1 (an int32 row map)
+#define ARL_CELL_FLAGS(reset, row0, row_step, batch)                                                           \
+    ARL_REQUIRE(!(reset) || ((row0) >= 0 && (row0) <= INT32_MAX && (row_step) >= 1 && (row_step) <= INT32_MAX &&   \
+                             (row0) + ((int64_t)(batch) - 1) * (row_step) <= INT32_MAX),                            \
+                ARL_E_RANGE, "flag rows: 0 <= row0, 1 <= row_step, row0 + (batch - 1) row_step <= 2^31 - 1")

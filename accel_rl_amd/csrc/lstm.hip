@@ -7,6 +7,9 @@
 //   fwd:  f,i,o = sigmoid(.), g = tanh(.); c = f c_prev + i g; h = o tanh(c)
 //   bwd:  given dh (all sources summed) and dc_next: do = dh tanh(c); dc = dc_next + dh o (1 - tanh(c)^2);
 //         df = dc c_prev; di = dc g; dg = dc i; dc_prev = dc f; pre-activation grads via s(1-s), 1-g^2
+//   bwd, reset-aware (arl_lstm_cell_bwd_reset): the same body; where this row's reset flag is set (the state was zeroed
+//         after this step) dh_rec and dc_next, which arrive from step t+1, are left out: exactly the arithmetic of
+//         the call with both NULL for that row.  c_prev is then the caller's masked copy (arl_seq_handover).
 
 #include "arl_common.h"
 
@@ -63,7 +66,8 @@ struct LstmBwdArgs {
     int64_t dh_stride, gates_stride, cprev_stride, c_stride, dgates_stride;
 };
 
-__global__ __launch_bounds__(256) void lstm_bwd_kernel(const LstmBwdArgs a) {
+template <bool kReset>
+__device__ __forceinline__ void lstm_bwd_body(const LstmBwdArgs& a, const arl::CellFlags& fl) {
     const int H = a.hidden;
     const int64_t total = a.batch * H;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -71,12 +75,13 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const LstmBwdArgs a) {
         const int j = (int)(i - b * H);
         const float* gs = a.gates + b * a.gates_stride;
         const float f = gs[j], ig = gs[H + j], g = gs[2 * H + j], o = gs[3 * H + j];
+        const bool keep = !kReset || !fl.at(b);                  // false: nothing arrives from step t+1
         float dh = 0.f;
         if (a.dh) dh += a.dh[b * a.dh_stride + j];
-        if (a.dh_rec) dh += a.dh_rec[i];
+        if (a.dh_rec && keep) dh += a.dh_rec[i];
         const float tc = tanhf(a.c_out[b * a.c_stride + j]);
         float dc = dh * o * (1.f - tc * tc);
-        if (a.dc_next) dc += a.dc_next[i];
+        if (a.dc_next && keep) dc += a.dc_next[i];
         float* dg = a.dgates + b * a.dgates_stride;
         dg[j] = dc * a.c_prev[b * a.cprev_stride + j] * f * (1.f - f);
         dg[H + j] = dc * g * ig * (1.f - ig);
@@ -84,6 +89,12 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const LstmBwdArgs a) {
         dg[3 * H + j] = dh * tc * o * (1.f - o);
         a.dc_prev[i] = dc * f;
     }
+}
+
+__global__ __launch_bounds__(256) void lstm_bwd_kernel(const LstmBwdArgs a) { lstm_bwd_body<false>(a, arl::CellFlags{}); }
+
+__global__ __launch_bounds__(256) void lstm_bwd_reset_kernel(const LstmBwdArgs a, const arl::CellFlags fl) {
+    lstm_bwd_body<true>(a, fl);
 }
 
 }  // namespace
@@ -121,4 +132,30 @@ extern "C" int arl_lstm_cell_bwd(const float* dh_or_null, int64_t dh_stride, con
                      dh_stride, gates_stride, cprev_stride, c_stride, dgates_stride};
     hipLaunchKernelGGL(lstm_bwd_kernel, dim3(arl::stream_grid(batch * hidden, 256)), dim3(256), 0, (hipStream_t)stream, a);
     return arl::check_launch("lstm_bwd_kernel");
+}
+
+extern "C" int arl_lstm_cell_bwd_reset(const float* dh_or_null, int64_t dh_stride, const float* dh_rec_or_null,
+                                       const float* dc_next_or_null, const float* gates, int64_t gates_stride,
+                                       const float* c_prev, int64_t cprev_stride, const float* c_out, int64_t c_stride,
+                                       int64_t batch, int32_t hidden, float* dgates, int64_t dgates_stride,
+                                       float* dc_prev, const uint8_t* reset_or_null, const int32_t* idx_or_null,
+                                       int64_t flag_row0, int64_t flag_row_step, void* stream) {
+    ARL_REQUIRE(gates && c_prev && c_out && dgates && dc_prev, ARL_E_ARG, "null pointer");
+    ARL_CELL_SIZES(batch, hidden);
+    ARL_CELL_STRIDE(dh_or_null, dh_stride, hidden, batch);
+    ARL_CELL_STRIDE(gates, gates_stride, 4 * (int64_t)hidden, batch);
+    ARL_CELL_STRIDE(c_prev, cprev_stride, hidden, batch);
+    ARL_CELL_STRIDE(c_out, c_stride, hidden, batch);
+    ARL_CELL_STRIDE(dgates, dgates_stride, 4 * (int64_t)hidden, batch);
+    ARL_CELL_FLAGS(reset_or_null, flag_row0, flag_row_step, batch);
+    LstmBwdArgs a = {dh_or_null, dh_rec_or_null, dc_next_or_null, gates, c_prev, c_out, dgates, dc_prev, batch, hidden,
+                     dh_stride, gates_stride, cprev_stride, c_stride, dgates_stride};
+    const dim3 grid(arl::stream_grid(batch * hidden, 256));
+    if (!reset_or_null) {                                        // no flags: the kernel of arl_lstm_cell_bwd itself
+        hipLaunchKernelGGL(lstm_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+        return arl::check_launch("lstm_bwd_kernel");
+    }
+    const arl::CellFlags fl = {reset_or_null, idx_or_null, flag_row0, flag_row_step};
+    hipLaunchKernelGGL(lstm_bwd_reset_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, fl);
+    return arl::check_launch("lstm_bwd_reset_kernel");
 }

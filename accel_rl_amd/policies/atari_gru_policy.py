@@ -57,6 +57,9 @@ class AtariGruPolicy(RecurrentCnnPolicy):
     def _cell_fwd(self, gx, gh, prev, out, saved):
         _lib.gru_cell_fwd(gx, gh, prev[0], out[0], saved)
 
-    def _cell_bwd(self, dh, dh_rec, carry, last, saved, prev, out, dgx, dgh):
+    def _cell_bwd(self, dh, dh_rec, carry, last, saved, prev, out, dgx, dgh, flags=None):
         # carry = direct part dh (1 - u) of the next step (in), of this step (out)
-        _lib.gru_cell_bwd(dh, dh_rec, None if last else carry, saved, prev[0], dgx, dgh, carry)
+        if flags is None:
+            _lib.gru_cell_bwd(dh, dh_rec, None if last else carry, saved, prev[0], dgx, dgh, carry)
+        else:
+            _lib.gru_cell_bwd_reset(dh, dh_rec, None if last else carry, saved, prev[0], dgx, dgh, carry, flags)

@@ -28,8 +28,11 @@ class RecurrentCnnPolicy(AtariCnnPolicy):
     """Cell hooks: `_gate_mult` (width of gx / gh in units of H), `_saved_mult` (per-step values kept
     for the backward pass), `_state_keys`, the four `_hidden_*` parameter-layout hooks (which must
     set self._k_x = index of the internal [W_x^T, W_h^T, b] triple relative to the first hidden
-    tensor), `_cell_fwd` and `_cell_bwd`."""
+    tensor), `_cell_fwd` and `_cell_bwd` (whose `flags`, when given, are the reset flags of the step's rows:
+    `_lib._flags`)."""
 
+    supports_bptt_resets = True  # loss_and_grads takes mb["resets"] (reset-aware BPTT, DESIGN.md 12)
+    _masked_prev_key = None     # index of the state key the cell reads elementwise from a masked per-row copy (LSTM: c)
     serves_rows = False         # own prob_value: the sampler keeps a contiguous copy of the current observations
     _gate_mult = 4
     _saved_mult = 4
@@ -168,7 +171,11 @@ class RecurrentCnnPolicy(AtariCnnPolicy):
         """Whole-batch update (rows env-major = [trajectory][time]); mb additionally carries
         `horizon` and the stored previous states (only the rows of t = 0 are used).  With `traj` (i32[n_seg] device
         tensor of segment numbers) the update runs on those segments only, in that order: a trajectory minibatch
-        (`traj_minibatch`); `inv_count` then defaults to that minibatch's own 1 / sum(valids)."""
+        (`traj_minibatch`); `inv_count` then defaults to that minibatch's own 1 / sum(valids).  With `resets`
+        (u8[rows of the full batch], non-zero where the state was set to zero after that row's step: a batch collected
+        under mid_batch_reset) the previous state of step t > 0 is state[t-1] (1 - resets[t-1]) and no gradient crosses
+        a reset: one arl_seq_handover launch per forward step instead of the two copies, the *_cell_bwd_reset cells
+        backward.  Without `resets` nothing changes."""
         if mb.get("idx") is not None:
             raise NotImplementedError("recurrent training takes whole trajectories: no row minibatches")
         with torch.no_grad():
@@ -200,10 +207,22 @@ class RecurrentCnnPolicy(AtariCnnPolicy):
             hp = self._buffer(("hp", nb), (nb, hh))
             gh = self._buffer(("gh", nb), (nb, gm * hh))
             g_hh = self._geom(nb, hh, gm * hh)
+            resets, mk = mb.get("resets"), self._masked_prev_key
+            if resets is not None:
+                # the previous state of step t > 0 is the masked copy the hand-over launch leaves: hprev_all's slice
+                # for h, a per-row buffer for the state the cell reads elementwise besides (the LSTM's c)
+                masked = buf("prev%d_masked" % mk, hh) if mk is not None else None
+                flags_at = lambda t: (resets, idx, t, t_len)                              # noqa: E731
+                prev_at = lambda t: init if t == 0 else [                                 # noqa: E731
+                    sl(hprev_all, t) if i == 0 else sl(masked, t) for i in range(n_state)]
             for t in range(t_len):                                                        # forward scan
                 prev = prev_at(t)
-                hp.copy_(prev[0])
-                sl(hprev_all, t).copy_(hp)
+                if resets is None or t == 0:
+                    hp.copy_(prev[0])
+                    sl(hprev_all, t).copy_(hp)
+                else:
+                    _lib.seq_handover(sl(st_all[0], t - 1), None if mk is None else sl(st_all[mk], t - 1),
+                                      flags_at(t - 1), hp, prev[0], None if mk is None else prev[mk])
                 _lib.conv2d_fwd(hp, w[k + 1], None, gh, g_hh, False, self._conv_ws)
                 self._cell_fwd(sl(gx, t), gh, prev, [sl(s, t) for s in st_all], None if saved is None else sl(saved, t))
             # ---- heads + losses on every step
@@ -222,7 +241,7 @@ class RecurrentCnnPolicy(AtariCnnPolicy):
                 last = t == t_len - 1
                 self._cell_bwd(sl(dh_all, t), None if last else dh_rec, carry, last,
                                None if saved is None else sl(saved, t), prev_at(t), [sl(s, t) for s in st_all],
-                               sl(dgx, t), sl(dgh, t))
+                               sl(dgx, t), sl(dgh, t), *(() if resets is None else (flags_at(t),)))
                 if t > 0:
                     dg_t.copy_(sl(dgh, t))
                     _lib.conv2d_bwd_data(dg_t, w[k + 1], None, dh_rec, g_hh)
@@ -247,6 +266,7 @@ class AtariLstmPolicy(RecurrentCnnPolicy):
 
     _gate_mult, _saved_mult, _separate_dgh = 4, 4, False
     _state_keys = ("hprev_0", "cprev_0")
+    _masked_prev_key = 1
 
     # ---- parameters: W_x (fan, 4H), W_h (H, 4H), b (4H) in the reference's order (layers.py:325-327)
     def _hidden_reference_init(self, fan):
@@ -268,6 +288,9 @@ class AtariLstmPolicy(RecurrentCnnPolicy):
     def _cell_fwd(self, gx, gh, prev, out, saved):
         _lib.lstm_cell_fwd(gx, gh, prev[1], out[0], out[1], saved)
 
-    def _cell_bwd(self, dh, dh_rec, carry, last, saved, prev, out, dgx, dgh):
+    def _cell_bwd(self, dh, dh_rec, carry, last, saved, prev, out, dgx, dgh, flags=None):
         # carry = dc of the next step (in), dc of this step (out)
-        _lib.lstm_cell_bwd(dh, dh_rec, None if last else carry, saved, prev[1], out[1], dgx, carry)
+        if flags is None:
+            _lib.lstm_cell_bwd(dh, dh_rec, None if last else carry, saved, prev[1], out[1], dgx, carry)
+        else:
+            _lib.lstm_cell_bwd_reset(dh, dh_rec, None if last else carry, saved, prev[1], out[1], dgx, carry, flags)

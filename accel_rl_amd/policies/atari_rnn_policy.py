@@ -35,5 +35,8 @@ class AtariRnnPolicy(RecurrentCnnPolicy):
     def _cell_fwd(self, gx, gh, prev, out, saved):
         _lib.rnn_cell_fwd(gx, gh, out[0])
 
-    def _cell_bwd(self, dh, dh_rec, carry, last, saved, prev, out, dgx, dgh):
-        _lib.rnn_cell_bwd(dh, dh_rec, out[0], dgx)
+    def _cell_bwd(self, dh, dh_rec, carry, last, saved, prev, out, dgx, dgh, flags=None):
+        if flags is None:
+            _lib.rnn_cell_bwd(dh, dh_rec, out[0], dgx)
+        else:
+            _lib.rnn_cell_bwd_reset(dh, dh_rec, out[0], dgx, flags)

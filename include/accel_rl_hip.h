@@ -847,6 +847,54 @@ int arl_rnn_cell_bwd(const float* dh_or_null, int64_t dh_stride, const float* dh
                      const float* h_out, int64_t h_stride, int64_t batch, int32_t hidden, float* dpre,
                      int64_t dpre_stride, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Reset-aware BPTT: training a recurrent policy on a batch inside which environments were reset
+ * ------------------------------------------------------------------------- */
+
+/* Flag addressing shared by the four entry points below.  reset is u8[rows of the full batch], non-zero where the
+ * recurrent state was set to zero AFTER that row's step.  Row b of a launch is compact row
+ * flag_row0 + b * flag_row_step of a [trajectory][time] (mini)batch (flag_row0 = the time step, flag_row_step = the
+ * horizon); its flag is reset[idx ? idx[compact row] : compact row], idx being arl_traj_minibatch's row map (or NULL:
+ * the whole batch).  0 <= flag_row0, 1 <= flag_row_step and flag_row0 + (batch - 1) flag_row_step <= 2^31 - 1, else
+ * ARL_E_RANGE; the caller answers for reset / idx covering those rows.
+ *
+ * arl_seq_handover: one launch hands the state of step t-1 (flag rows: those of step t-1) to step t of the learner's
+ * forward scan.  Where the flag is set the previous state is +0, else the stored value bit for bit; no arithmetic.
+ *   h_prev [B][H] strided -> hp [B][H] contiguous (the operand of h_prev W_h) and hprev_out [B][H] strided (the
+ *   slice of step t of the array that feeds dW_h; also the GRU's elementwise h_prev);
+ *   c_prev [B][H] strided -> cprev_out [B][H] strided (the LSTM's c_prev of step t, read by the cell and its
+ *   backward); both NULL for cells with one state.
+ * One float4 per lane: hidden % 4 == 0 and hidden <= 1024 (ARL_E_RANGE), every pointer 16-byte aligned and every
+ * stride a multiple of 4 (ARL_E_ALIGN); batch and stride limits as for the cell entry points above.  A refused call
+ * launches nothing.  Latency-bound (B x H elements); no throughput figure is claimed. */
+int arl_seq_handover(const float* h_prev, int64_t h_stride, const float* c_prev_or_null, int64_t c_stride,
+                     const uint8_t* reset, const int32_t* idx_or_null, int64_t flag_row0, int64_t flag_row_step,
+                     int64_t batch, int32_t hidden, float* hp, float* hprev_out, int64_t hprev_stride,
+                     float* cprev_out_or_null, int64_t cprev_out_stride, void* stream);
+
+/* The three backward cells with the reset flags of THIS step's rows: where a row's flag is set, the gradients that
+ * arrive from step t+1 (dh_rec; the LSTM's dc_next; the GRU's dh_dir) are left out for that row -- the arithmetic of
+ * the plain entry point with those pointers NULL -- and everything else is the plain entry point's arithmetic in the
+ * same order (one templated body).  c_prev / h_prev are the masked values arl_seq_handover wrote.  With
+ * reset_or_null == NULL the plain entry point's own kernel is launched: the same bits.  Arguments, limits and
+ * aliasing rules as for arl_{lstm,gru,rnn}_cell_bwd. */
+int arl_lstm_cell_bwd_reset(const float* dh_or_null, int64_t dh_stride, const float* dh_rec_or_null,
+                            const float* dc_next_or_null, const float* gates, int64_t gates_stride,
+                            const float* c_prev, int64_t cprev_stride, const float* c_out, int64_t c_stride,
+                            int64_t batch, int32_t hidden, float* dgates, int64_t dgates_stride, float* dc_prev,
+                            const uint8_t* reset_or_null, const int32_t* idx_or_null, int64_t flag_row0,
+                            int64_t flag_row_step, void* stream);
+int arl_gru_cell_bwd_reset(const float* dh_or_null, int64_t dh_stride, const float* dh_rec_or_null,
+                           const float* dh_dir_or_null, const float* saved, int64_t saved_stride,
+                           const float* h_prev, int64_t hprev_stride, int64_t batch, int32_t hidden,
+                           float* dgx, int64_t dgx_stride, float* dgh, int64_t dgh_stride, float* dh_prev,
+                           const uint8_t* reset_or_null, const int32_t* idx_or_null, int64_t flag_row0,
+                           int64_t flag_row_step, void* stream);
+int arl_rnn_cell_bwd_reset(const float* dh_or_null, int64_t dh_stride, const float* dh_rec_or_null,
+                           const float* h_out, int64_t h_stride, int64_t batch, int32_t hidden, float* dpre,
+                           int64_t dpre_stride, const uint8_t* reset_or_null, const int32_t* idx_or_null,
+                           int64_t flag_row0, int64_t flag_row_step, void* stream);
+
 /* Optimiser state for ONE flat fp32 parameter bucket (all trainable params in
  * get_params order, accel_rl/optimizers/util.py:35-39). */
 typedef struct arl_opt_state {
