@@ -193,6 +193,8 @@ _SIGNATURES = {
     "arl_catdqn_loss": (_i32, [_vp] * 8 + [_i64, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "arl_catdqn_loss_parts": (_i32, [_vp] * 8 + [_i64, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _i32,
                                _vp]),
+    "arl_qrdqn_act": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "arl_qrdqn_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "arl_dqn_act": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "arl_dqn_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "arl_lstm_cell_fwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -1006,6 +1008,24 @@ def catdqn_loss_parts(pred, tgt_next, pol_next, z, actions, returns, terminals, 
                                         float(v_max), float(gamma_n), ptr(dlogits), ptr(loss_rows), ptr(kl),
                                         None if wt_items is None else C.cast(wt_items, _vp), n_wt,
                                         stream_ptr(stream)), "arl_catdqn_loss_parts")
+
+
+def qrdqn_act(theta, override, n_actions, n_quantiles, onehot, greedy=None, dueling=False, stream=None):
+    batch = onehot.shape[0]
+    stride = theta.numel() // (batch * (n_actions + int(dueling)))
+    _check(load().arl_qrdqn_act(ptr(theta), ptr(override), batch, n_actions, n_quantiles, stride, int(dueling),
+                                ptr(onehot), ptr(greedy), stream_ptr(stream)), "arl_qrdqn_act")
+
+
+def qrdqn_loss(pred, tgt_next, pol_next, actions, returns, terminals, is_weights, n_actions, n_quantiles, gamma_n, kappa,
+               dtheta, loss_rows, priorities, dueling=False, stream=None):
+    """kappa 0: plain quantile regression."""
+    batch = actions.numel()
+    stride = pred.numel() // (batch * (n_actions + int(dueling)))
+    _check(load().arl_qrdqn_loss(ptr(pred), ptr(tgt_next), ptr(pol_next), ptr(actions), ptr(returns), ptr(terminals),
+                                 ptr(is_weights), batch, n_actions, n_quantiles, stride, int(dueling), float(gamma_n),
+                                 float(kappa), ptr(dtheta), ptr(loss_rows), ptr(priorities), stream_ptr(stream)),
+           "arl_qrdqn_loss")
 
 
 def dqn_act(q, override, n_actions, onehot, greedy=None, dueling=False, stream=None):

@@ -17,6 +17,15 @@
 //   arl_dqn_loss      one-step / n-step Q-learning target (max or double-DQN selection), squared or
 //                     Huber loss, clipped |TD error| priorities, d loss / d Q (algos/dqn/dqn.py:137-172)
 //
+//   arl_qrdqn_act     quantile-regression DQN twin of arl_catdqn_act: Q_a = (sum_i theta(a, i)) / N, greedy action = first
+//                     maximum, override and one-hot row as there (Dabney et al. 2018; not in the reference)
+//   arl_qrdqn_loss    greedy next action, target quantiles T_j = return + keep * (gamma_n * theta_tgt(a*, j)), the pairwise
+//                     quantile-Huber loss over the N x N differences u_ij = T_j - theta_pred(action, i), priorities and
+//                     d loss / d theta in one pass.  Summation order (per predicted quantile i = lane i): wave w adds its
+//                     terms j = w, w + 4, w + 8, ... to 0 in ascending j; the four partial sums are combined as
+//                     ((p0 + p1) + p2) + p3 -- at most N / 4 + 3 additions in a row; the loss then sums the lanes in
+//                     wave_sum's butterfly order.  No atomics: two runs give the same bits.
+//
 // Layout: logits f32[batch][n_actions (+ 1 value row when dueling)][atom_stride], atom_stride = n_atoms rounded up to a
 // multiple of 4 (the dense layer producing them is an MFMA kernel with 16-byte rows); the padding
 // columns are ignored on input and receive zero gradient.  Lane i owns atom i; one wave per sample (action
@@ -394,6 +403,148 @@ __global__ __launch_bounds__(256) void dqn_loss_kernel(const DqnLossArgs a) {
     a.td_abs[b] = c > 0.f ? fminf(ad, c) : ad;                             // :165
 }
 
+// ---- quantile-regression DQN: theta f32[batch][n_actions (+ 1)][q_stride], lane i = quantile i (layout and dueling
+// merge as the categorical head's) ----
+// Q_a of every action under `theta`, first maximum; one wave.  Q_a = wave_sum(theta(a, .)) / N (lanes >= N add 0)
+__device__ __forceinline__ int qr_greedy_action(const float* theta_p, int lane, int n_actions, int n, int stride,
+                                                bool dueling) {
+    const Plain theta = {theta_p};
+    const Duel d = duel_terms(theta, lane, n_actions, n, stride, dueling);
+    int best = 0;
+    float best_q = -3.0e38f;
+    for (int a = 0; a < n_actions; ++a) {
+        const float q = wave_sum(atom_logit(theta, a, lane, n, stride, d)) / (float)n;
+        if (a == 0 || q > best_q) { best_q = q; best = a; }
+    }
+    return best;
+}
+
+__global__ __launch_bounds__(256) void qrdqn_act_kernel(const float* __restrict__ theta,
+                                                        const int32_t* __restrict__ override_or_null, int64_t batch,
+                                                        int n_actions, int n, int stride, int dueling,
+                                                        float* __restrict__ onehot, uint8_t* __restrict__ greedy) {
+    const int lane = threadIdx.x & 63;
+    const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= batch) return;
+    const int g = qr_greedy_action(theta + b * (n_actions + dueling) * stride, lane, n_actions, n, stride, dueling != 0);
+    int act = g;
+    if (override_or_null && override_or_null[b] >= 0) act = override_or_null[b];
+    if (lane < n_actions) onehot[b * n_actions + lane] = lane == act ? 1.f : 0.f;
+    if (lane == 0 && greedy) greedy[b] = (uint8_t)g;
+}
+
+struct QrLossArgs {
+    const float* pred;              // policy net on obs              [B][A (+ 1)][S]
+    const float* tgt_next;          // target net on next_obs         [B][A (+ 1)][S]
+    const float* pol_next;          // policy net on next_obs (double DQN) or null
+    const uint8_t* actions;         // [B]
+    const float* returns;           // [B] n-step discounted return
+    const uint8_t* terminals;       // [B]
+    const float* is_weights;        // [B] or null
+    float* dtheta;                  // [B][A (+ 1)][S]
+    float* loss_rows;               // [B] per-sample (weighted) loss / B
+    float* priorities;              // [B] clip(unweighted loss, 1e-6, 1e6)
+    int64_t batch;
+    int n_actions, n, stride;
+    int dueling;
+    float gamma_n, kappa;           // kappa == 0: plain quantile regression
+};
+
+// One workgroup per sample.  The actions of the greedy search are dealt to the four waves (a wave reduction each); wave 0
+// stages the target quantiles T_j and the taken action's predicted quantiles in LDS; the N x N phase has lane i = predicted
+// quantile i in every wave and the j loop dealt to the waves (j = wave, wave + 4, ...: all lanes read the same T_j, a
+// broadcast); the four partial sums per lane are combined in the fixed order ((p0 + p1) + p2) + p3 by every wave alike,
+// and the waves share the rows of dtheta between them.
+__global__ __launch_bounds__(256) void qrdqn_loss_kernel(const QrLossArgs a) {
+    __shared__ float s_q[64], s_t[64], s_pred[64], s_g[4][64], s_r[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t b = blockIdx.x;
+    if (b >= a.batch) return;                                  // (whole workgroup: no barrier is left waiting)
+    const int A = a.n_actions, n = a.n, S = a.stride;
+    const bool duel = a.dueling != 0;
+    const int64_t R = (int64_t)(A + a.dueling) * S;            // floats per sample
+    const Plain tgt = {a.tgt_next + b * R};
+    {
+        const Plain sel = {(a.pol_next ? a.pol_next : a.tgt_next) + b * R};
+        const Duel d = duel_terms(sel, lane, A, n, S, duel);
+        float xs[16];                   // this wave's actions (k = wave, wave + 4, ...): every row requested before the first sum
+#pragma unroll
+        for (int j = 0; j < 16; ++j) xs[j] = wave + 4 * j < A ? atom_logit(sel, wave + 4 * j, lane, n, S, d) : 0.f;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int k = wave + 4 * j;
+            if (k < A) {
+                const float q = wave_sum(xs[j]) / (float)n;
+                if (lane == 0) s_q[k] = q;
+            }
+        }
+    }
+    int act = a.actions[b];
+    act = act < A ? act : A - 1;                               // an action the net does not have: never out of bounds
+    if (wave == 0) {
+        const Plain prd = {a.pred + b * R};
+        s_pred[lane] = atom_logit(prd, act, lane, n, S, duel_terms(prd, lane, A, n, S, duel));
+    }
+    __syncthreads();
+    if (wave == 0) {
+        int a_next = 0;
+        float best_q = s_q[0];
+        for (int k = 1; k < A; ++k) {
+            const float q = s_q[k];
+            if (q > best_q) { best_q = q; a_next = k; }
+        }
+        const float keep = a.terminals[b] ? 0.f : 1.f;
+        s_t[lane] = a.returns[b] + keep * (a.gamma_n * atom_logit(tgt, a_next, lane, n, S, duel_terms(tgt, lane, A, n, S, duel)));
+    }
+    __syncthreads();
+    // N x N phase: this wave's share of sum_j for predicted quantile `lane`
+    const float kappa = a.kappa;
+    float g = 0.f, r = 0.f;
+    if (lane < n) {
+        const float th = s_pred[lane];
+        const float tau = ((float)lane + 0.5f) / (float)n;
+        for (int j = wave; j < n; j += 4) {
+            const float u = s_t[j] - th;
+            const float wt = fabsf(tau - (u < 0.f ? 1.f : 0.f));
+            float gt, rt;
+            if (kappa > 0.f) {
+                const float au = fabsf(u);
+                const float l = au <= kappa ? 0.5f * (u * u) : kappa * (au - 0.5f * kappa);
+                rt = wt * l / kappa;
+                gt = wt * fminf(fmaxf(u, -kappa), kappa) / kappa;
+            } else {
+                rt = wt * fabsf(u);
+                gt = tau - (u < 0.f ? 1.f : 0.f);
+            }
+            g += gt;
+            r += rt;
+        }
+    }
+    s_g[wave][lane] = g;
+    s_r[wave][lane] = r;
+    __syncthreads();
+    // every wave combines the four partial sums in the same fixed order (a wave without terms left an exact 0)
+    const float gs = ((s_g[0][lane] + s_g[1][lane]) + s_g[2][lane]) + s_g[3][lane];
+    const float rs = ((s_r[0][lane] + s_r[1][lane]) + s_r[2][lane]) + s_r[3][lane];
+    const float wgt = (a.is_weights ? a.is_weights[b] : 1.f) / (float)a.batch;
+    const float d_lane = lane < n ? -(wgt / (float)n * gs) : 0.f;          // d loss / d theta(act, lane)
+    float* dl = a.dtheta + b * R;
+    const float share = d_lane / (float)A;
+    for (int k = wave; k < A + a.dueling; k += 4) {            // the rows dealt to the waves; padding columns: exact zeros
+        float v;
+        if (!duel) v = k == act ? d_lane : 0.f;                // every other action gets 0
+        else v = k == A ? d_lane : k == act ? d_lane - share : -share;     // through the merge: adv rows, then the value row
+        for (int i = lane; i < S; i += 64) dl[(int64_t)k * S + i] = i < n ? v : 0.f;
+    }
+    if (wave == 0) {
+        const float loss_b = wave_sum(lane < n ? rs : 0.f) / (float)n;
+        if (lane == 0) {
+            a.loss_rows[b] = wgt * loss_b;
+            a.priorities[b] = fminf(fmaxf(loss_b, 1e-6f), 1e6f);
+        }
+    }
+}
+
 }  // namespace
 
 static int check_q(int64_t batch, int n_actions, int stride, int dueling) {
@@ -470,6 +621,47 @@ extern "C" int arl_catdqn_loss(const float* pred_logits, const float* tgt_next_l
     a.v_min = v_min; a.v_max = v_max; a.gamma_n = gamma_n;
     hipLaunchKernelGGL(catdqn_loss_kernel<-1>, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, a, arlw::DgradWtArgs{});
     return arl::check_launch("catdqn_loss_kernel");
+}
+
+static int check_qr(int64_t batch, int n_actions, int n_quantiles, int stride) {
+    if (batch <= 0 || batch > 0x7fffffffLL || n_actions <= 0 || n_actions > 64 || n_quantiles < 2 || n_quantiles > 64 ||
+        stride < n_quantiles || (stride & 3) || stride > (1 << 20)) {
+        arl::set_error("qrdqn: need 1 <= batch < 2^31, 1 <= n_actions <= 64, 2 <= n_quantiles <= 64, "
+                       "n_quantiles <= q_stride <= 2^20 and q_stride %% 4 == 0");
+        return ARL_E_RANGE;
+    }
+    return 0;
+}
+
+extern "C" int arl_qrdqn_act(const float* theta, const int32_t* override_or_null, int64_t batch, int32_t n_actions,
+                             int32_t n_quantiles, int32_t q_stride, int32_t dueling, float* onehot,
+                             uint8_t* greedy_or_null, void* stream) {
+    ARL_REQUIRE(theta && onehot, ARL_E_ARG, "null pointer");
+    int rc = check_qr(batch, n_actions, n_quantiles, q_stride);
+    if (rc) return rc;
+    hipLaunchKernelGGL(qrdqn_act_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                       theta, override_or_null, batch, n_actions, n_quantiles, q_stride, dueling != 0, onehot,
+                       greedy_or_null);
+    return arl::check_launch("qrdqn_act_kernel");
+}
+
+extern "C" int arl_qrdqn_loss(const float* pred, const float* tgt_next, const float* pol_next_or_null,
+                              const uint8_t* actions, const float* returns, const uint8_t* terminals,
+                              const float* is_weights_or_null, int64_t batch, int32_t n_actions, int32_t n_quantiles,
+                              int32_t q_stride, int32_t dueling, float gamma_n, float kappa, float* dtheta,
+                              float* loss_rows, float* priorities, void* stream) {
+    ARL_REQUIRE(pred && tgt_next && actions && returns && terminals && dtheta && loss_rows && priorities, ARL_E_ARG,
+                "null pointer");
+    int rc = check_qr(batch, n_actions, n_quantiles, q_stride);
+    if (rc) return rc;
+    ARL_REQUIRE(kappa >= 0.f && kappa <= 3.0e38f, ARL_E_ARG, "kappa must be finite and >= 0");
+    QrLossArgs a = {};
+    a.pred = pred; a.tgt_next = tgt_next; a.pol_next = pol_next_or_null; a.actions = actions; a.returns = returns;
+    a.terminals = terminals; a.is_weights = is_weights_or_null; a.dtheta = dtheta; a.loss_rows = loss_rows;
+    a.priorities = priorities; a.batch = batch; a.n_actions = n_actions; a.n = n_quantiles; a.stride = q_stride;
+    a.dueling = dueling != 0; a.gamma_n = gamma_n; a.kappa = kappa;
+    hipLaunchKernelGGL(qrdqn_loss_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, a);
+    return arl::check_launch("qrdqn_loss_kernel");
 }
 
 extern "C" int arl_catdqn_loss_parts(const arl_logit_src* pred, const arl_logit_src* tgt_next,

@@ -753,6 +753,48 @@ int arl_catdqn_loss_parts(const arl_logit_src* pred, const arl_logit_src* tgt_ne
 /* (wt_items_or_null / n_wt: as in arl_pg_head_loss_parts -- the launch also writes these layers' k-contiguous weight copies
  *  for the backward pass that follows, in extra workgroups.) */
 
+/* ------------------------------------------------------------------------- *
+ * Quantile-regression DQN output stage
+ * ------------------------------------------------------------------------- */
+
+/* QR-DQN (Dabney et al. 2018; the reference has none): the network predicts N = n_quantiles quantile locations per
+ * action -- no fixed support, no projection.
+ *   theta f32[batch][n_actions][q_stride], lane i of a wave = quantile i; the padding columns are ignored
+ *   dueling != 0: theta f32[batch][n_actions + 1][q_stride], advantage rows then ONE value row, merged as the
+ *   categorical head's: theta(a, i) = val_i + (adv_ai - mean_a adv_ai)
+ * Limits (else ARL_E_RANGE, nothing launched, no output written): 1 <= batch < 2^31, 1 <= n_actions <= 64,
+ *   2 <= n_quantiles <= 64, n_quantiles <= q_stride <= 2^20, q_stride % 4 == 0.  A NULL mandatory pointer: ARL_E_ARG.
+ *
+ * Action serving: Q_a = (sum_i theta(a, i)) / n_quantiles in fp32 (the 64 lanes summed as a butterfly: lane ^ 32, ^ 16,
+ * ... ^ 1), greedy action = FIRST maximum (two identical rows tie to the lower index); override, the one-hot row and
+ * `greedy` exactly as in the categorical action entry point above.
+ *   onehot f32[batch][n_actions]; greedy u8[batch] or NULL                                                        */
+int arl_qrdqn_act(const float* theta, const int32_t* override_or_null, int64_t batch, int32_t n_actions,
+                  int32_t n_quantiles, int32_t q_stride, int32_t dueling, float* onehot, uint8_t* greedy_or_null,
+                  void* stream);
+
+/* Pairwise quantile-Huber loss with its gradient.  Per sample b, N = n_quantiles, w_b = (is_weight_b or 1) / batch,
+ * tau_i = (i + 0.5) / N, keep = 1 - terminal_b:
+ *   a*     = first maximum over a of Q_a (as above) under pol_next if given (double DQN), else under tgt_next
+ *   T_j    = returns_b + keep * (gamma_n * theta_tgt(a*, j))                      (fp32, in this order)
+ *   u_ij   = T_j - theta_pred(actions_b, i);  [u<0] = 1 for u < 0, else 0 (u == 0 counts as not negative)
+ *   kappa > 0:   L(u) = 0.5 u^2 if |u| <= kappa else kappa (|u| - 0.5 kappa)
+ *                rho_ij = |tau_i - [u_ij<0]| L(u_ij) / kappa
+ *                dtheta_i = -(w_b / N) sum_j |tau_i - [u_ij<0]| clip(u_ij, -kappa, kappa) / kappa
+ *   kappa == 0:  rho_ij = |tau_i - [u_ij<0]| |u_ij|          (plain quantile regression)
+ *                dtheta_i = -(w_b / N) sum_j (tau_i - [u_ij<0])
+ *   loss_b = (1 / N) sum_i sum_j rho_ij;  loss_rows[b] = w_b loss_b (the rows sum to the loss);
+ *   priorities[b] = clip(loss_b, 1e-6, 1e6), unweighted.
+ * dtheta has pred's shape: the rows of the other actions and the padding columns are written as exact zeros; dueling:
+ * the gradient w.r.t. the advantage rows and the value row (through the merge).  The target net gets no gradient.
+ * Summation order: for each i, four partial sums over j = w, w + 4, ... (w = 0 .. 3, ascending j, from 0), combined as
+ * ((p0 + p1) + p2) + p3; the loss then sums over i as the butterfly above.  Deterministic: no atomics.
+ * actions_b >= n_actions is read as n_actions - 1.  kappa < 0 or not finite: ARL_E_ARG.                            */
+int arl_qrdqn_loss(const float* pred, const float* tgt_next, const float* pol_next_or_null, const uint8_t* actions,
+                   const float* returns, const uint8_t* terminals, const float* is_weights_or_null, int64_t batch,
+                   int32_t n_actions, int32_t n_quantiles, int32_t q_stride, int32_t dueling, float gamma_n, float kappa,
+                   float* dtheta, float* loss_rows, float* priorities, void* stream);
+
 /* Plain DQN action serving: greedy action = first maximum of the Q row (T.argmax), override as
  * above, one-hot row out.  Replaces AtariDqnPolicy.get_actions / actions_sym,
  * accel_rl/policies/dqn/atari_dqn_policy.py:61-63,76-79,118-130.
