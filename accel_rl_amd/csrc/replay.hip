@@ -47,6 +47,11 @@ __global__ __launch_bounds__(256) void replay_append_kernel(const AppendArgs a) 
     if (idx == 0) {                                   // mirror the ring's tail (frame.py:134-137)
         copy_bytes16(frames, frames + (int64_t)S * P, (F - 1) * P, tid, 256);
         if (tid < F - 1) nb[tid] = nb[S + tid];
+        // the mirror reads slots S .. S+F-2, the loop below writes slots F-1 .. F-2+T: they overlap when
+        // T > S-F+1 (always when size == horizon), and one 16-byte chunk's reader and writer are different
+        // threads, possibly of different waves.  Mirror first, write second, as the reference does (idx is
+        // uniform across the workgroup)
+        __syncthreads();
     }
     for (int t = 0; t < T; ++t)                       // newest frame of every step (:142-143)
         copy_bytes16(frames + (int64_t)(idx + F - 1 + t) * P,
@@ -381,6 +386,12 @@ int check_replay(const arl_replay* rb) {
     if (rb->n_env <= 0 || rb->size <= 0 || rb->n_stack < 2 || rb->frame_bytes <= 0 || (rb->frame_bytes & 15) ||
         rb->reward_horizon < 1 || rb->reward_horizon > ARL_REPLAY_MAX_HORIZON || rb->reward_horizon > rb->size) {
         arl::set_error("replay: need n_stack >= 2, frame_bytes %% 16 == 0, 1 <= reward_horizon <= %d", ARL_REPLAY_MAX_HORIZON);
+        return ARL_E_RANGE;
+    }
+    // a smaller store's mirror would overlap itself (copy_bytes16 is a parallel copy, numpy copies as if through a
+    // temporary), and none of its states could ever be sampled
+    if (rb->size < rb->n_stack - 1) {
+        arl::set_error("replay: need size >= n_stack - 1 (a smaller store can never be sampled)");
         return ARL_E_RANGE;
     }
     if (!arl::aligned16(rb->frames)) { arl::set_error("replay: frames must be 16-byte aligned"); return ARL_E_ALIGN; }

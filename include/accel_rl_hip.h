@@ -613,7 +613,10 @@ int arl_conv2d_u8_bwd_weight_parts(const float* dy, const uint8_t* obs, int64_t 
 /* Frame-dedup replay storage for all environments, struct-of-arrays in HBM.
  * Replaces FrameReplayBuffer + one EnvBuffer per environment,
  * accel_rl/algos/dqn/replay_buffers/frame.py:23-119.  Per environment `size`
- * states; every frame is stored once in a ring of size + n_stack - 1 slots. */
+ * states; every frame is stored once in a ring of size + n_stack - 1 slots.
+ * Both entry points refuse (ARL_E_RANGE, nothing launched) n_stack < 2, frame_bytes not a multiple of 16,
+ * reward_horizon outside 1 .. min(ARL_REPLAY_MAX_HORIZON, size), and size < n_stack - 1 (the mirror of the
+ * ring's tail would overlap itself, and no state of such a store could be sampled). */
 typedef struct arl_replay {
     int64_t  n_env;
     int32_t  size;            /* states per environment (env_replay_size, frame.py:44) */
