@@ -195,6 +195,11 @@ _SIGNATURES = {
                                _vp]),
     "arl_qrdqn_act": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "arl_qrdqn_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "arl_iqn_embed": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "arl_iqn_merge_fwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
+    "arl_iqn_merge_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "arl_iqn_act": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "arl_iqn_loss": (_i32, [_vp] * 8 + [_i64, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "arl_dqn_act": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "arl_dqn_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "arl_lstm_cell_fwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -1026,6 +1031,59 @@ def qrdqn_loss(pred, tgt_next, pol_next, actions, returns, terminals, is_weights
                                  ptr(is_weights), batch, n_actions, n_quantiles, stride, int(dueling), float(gamma_n),
                                  float(kappa), ptr(dtheta), ptr(loss_rows), ptr(priorities), stream_ptr(stream)),
            "arl_qrdqn_loss")
+
+
+# ---- implicit quantile networks (csrc/iqn.hip): theta f32[batch][fractions][a_stride] ----
+IQN_COS = 64                    # ARL_IQN_COS
+IQN_MAX_FRACTIONS = 64          # ARL_IQN_MAX_FRACTIONS
+
+
+def iqn_embed(tau_in, state, rows, r, tau, cosf, row0=0, call_offset=0, stream=None):
+    """tau f32[rows r] and cosf f32[rows r][64]: given (tau_in) or drawn (state = i64[2] (seed, counter), only read;
+    the stream is indexed by the global pair index (row0 + row) r + fraction and by counter + call_offset)."""
+    _want(tau, torch.float32, "tau")
+    _want(cosf, torch.float32, "cosf")
+    assert tau.numel() == rows * r and cosf.numel() == rows * r * IQN_COS, "tau / cosf size"
+    if tau_in is not None:
+        _want(tau_in, torch.float32, "tau_in")
+        assert tau_in.numel() == rows * r, "tau_in size"
+    if state is not None:
+        _want(state, torch.int64, "state")
+    _check(load().arl_iqn_embed(ptr(tau_in), ptr(state), row0, call_offset, rows, r, ptr(tau), ptr(cosf),
+                                stream_ptr(stream)), "arl_iqn_embed")
+
+
+def iqn_merge_fwd(psi, phi, batch, r, f, x, stream=None):
+    assert psi.numel() == batch * f and phi.numel() == x.numel() == batch * r * f, "psi / phi / x size"
+    _check(load().arl_iqn_merge_fwd(ptr(psi), ptr(phi), batch, r, f, ptr(x), stream_ptr(stream)), "arl_iqn_merge_fwd")
+
+
+def iqn_merge_bwd(g, psi, phi, batch, r, f, dphi, dpsi, stream=None):
+    assert psi.numel() == dpsi.numel() == batch * f, "psi / dpsi size"
+    assert g.numel() == phi.numel() == dphi.numel() == batch * r * f, "g / phi / dphi size"
+    _check(load().arl_iqn_merge_bwd(ptr(g), ptr(psi), ptr(phi), batch, r, f, ptr(dphi), ptr(dpsi), stream_ptr(stream)),
+           "arl_iqn_merge_bwd")
+
+
+def iqn_act(theta, override, n_actions, k, onehot, greedy=None, state=None, advance=0, stream=None):
+    batch = onehot.shape[0]
+    stride = theta.numel() // (batch * k)
+    _check(load().arl_iqn_act(ptr(theta), ptr(override), batch, n_actions, k, stride, ptr(onehot), ptr(greedy),
+                              ptr(state), advance, stream_ptr(stream)), "arl_iqn_act")
+
+
+def iqn_loss(pred, tau_pred, tgt_next, pol_next, actions, returns, terminals, is_weights, n_actions, n, n_target,
+             gamma_n, kappa, dtheta, loss_rows, priorities, state=None, advance=0, stream=None):
+    """kappa 0: plain quantile regression.  state: the (seed, counter) buffer to advance by `advance` (drawn fractions)."""
+    batch = actions.numel()
+    stride = pred.numel() // (batch * n)
+    assert tau_pred.numel() == batch * n and tgt_next.numel() == batch * n_target * stride, "tau_pred / tgt_next size"
+    assert pol_next is None or pol_next.numel() == tgt_next.numel(), "pol_next size"
+    assert dtheta.numel() == pred.numel(), "dtheta size"
+    _check(load().arl_iqn_loss(ptr(pred), ptr(tau_pred), ptr(tgt_next), ptr(pol_next), ptr(actions), ptr(returns),
+                               ptr(terminals), ptr(is_weights), batch, n_actions, n, n_target, stride, float(gamma_n),
+                               float(kappa), ptr(dtheta), ptr(loss_rows), ptr(priorities), ptr(state), advance,
+                               stream_ptr(stream)), "arl_iqn_loss")
 
 
 def dqn_act(q, override, n_actions, onehot, greedy=None, dueling=False, stream=None):

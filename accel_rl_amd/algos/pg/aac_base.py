@@ -14,7 +14,7 @@ from accel_rl_amd import _lib
 from accel_rl_amd.algos.base import RLAlgorithm
 from accel_rl_amd.buffers import buffer_with_segs_view
 from accel_rl_amd.util import logger
-from accel_rl_amd.util.misc import graph_capture_mode
+from accel_rl_amd.util.misc import capture_graph
 from accel_rl_amd.util.quick_args import save_args
 import numpy as np
 
@@ -146,7 +146,7 @@ class AdvActorCriticBase(RLAlgorithm):
             opt_host = {k: getattr(self.optimizer, k) for k in
                         ("_n_updates", "_hole", "_call_hole", "_hole_count", "_pending_avg") if hasattr(self.optimizer, k)}
             try:
-                with torch.cuda.graph(graph, capture_error_mode=graph_capture_mode()):
+                with capture_graph(graph):
                     self._graph_out = self._device_optimize(itr, samples_data)
                     self._append_infos(self._graph_out[1])
             except Exception as e:          # single GPU: a bug, raise.  N > 1: every rank must take the same road

@@ -22,6 +22,7 @@
 // fp32 elsewhere, compiled with -ffp-contract=off.
 
 #include "arl_common.h"
+#include "philox_dev.h"
 
 namespace arlc {
 int fold_wide_from();           // mfma_conv.hip: the split count from which a fold sums 64-way (fold_slot)
@@ -29,19 +30,7 @@ int fold_wide_from();           // mfma_conv.hip: the split count from which a f
 
 namespace {
 
-constexpr uint32_t PH_M0 = 0xD2511F53u, PH_M1 = 0xCD9E8D57u, PH_W0 = 0x9E3779B9u, PH_W1 = 0xBB67AE85u;
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        if (i > 0) { k0 += PH_W0; k1 += PH_W1; }
-        const uint64_t p0 = (uint64_t)PH_M0 * c[0], p1 = (uint64_t)PH_M1 * c[2];
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-    }
-}
+using arlp::philox4x32_10;           // philox_dev.h (shared with csrc/iqn.hip)
 
 // the four normals of block q (elements 4q .. 4q + 3) of one (layer, which, row group, call) stream
 __device__ __forceinline__ void normals4(uint64_t seed, uint64_t counter, int stream_id, uint32_t group, uint32_t q,

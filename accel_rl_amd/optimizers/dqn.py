@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from accel_rl_amd.optimizers.base import BaseOptimizer
-from accel_rl_amd.util.misc import graph_capture_mode
+from accel_rl_amd.util.misc import capture_graph
 
 
 class DqnOptimizer(BaseOptimizer):
@@ -47,7 +47,7 @@ class DqnOptimizer(BaseOptimizer):
                 self._ring_replays = 0
             torch.cuda.synchronize(self._target.device)
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, capture_error_mode=graph_capture_mode()):
+            with capture_graph(graph):
                 self._graph_out = self._step(static)
             self._graph = graph
         self._graph.replay()

@@ -207,8 +207,8 @@ class AtariNoisyNetDqnPolicy(AtariDqnPolicy):
     # ---- acting: greedy on the noisy Q values, no host randomness ---------------
     def host_draws(self, horizon, n_envs, n_groups=2):
         """No epsilon (atari_noisy_net_dqn_policy.py:144-148): an all-greedy override table, and no np.random draw."""
-        if n_envs not in self._overrides or self._overrides[n_envs][1].shape[0] != horizon:
-            self._overrides[n_envs] = (None, torch.full((horizon, n_envs), -1, dtype=torch.int32, device=self.device))
+        self._select_overrides(horizon, n_envs, lambda: (
+            None, torch.full((horizon, n_envs), -1, dtype=torch.int32, device=self.device)))
         return np.full(horizon * n_envs, 0.5)
 
     def get_actions(self, observations, deterministic=False):

@@ -91,7 +91,8 @@ class QPolicyBase(AtariCnnPolicy):
         self.flat_target = self.flat_params.clone()             # target network (:57-61)
         sizes = [int(np.prod(s)) for s in self._shapes]
         self._w_target = [self.flat_target[o:o + n] for o, n in zip(self._offsets, sizes)]
-        self._overrides = dict()          # n_envs -> (pinned host, device) i32[horizon][n_envs]
+        self._overrides = dict()          # n_envs -> (pinned host, device) i32[horizon][n_envs], the last one drawn
+        self._override_tables = dict()    # (n_envs, horizon) -> the same pair, kept for good (_select_overrides)
         self._step = 0
         if self._dueling:                 # 1 on the two blocks of the output matrix that exist, 0 elsewhere
             hs = self.hidden_sizes[0]
@@ -245,13 +246,23 @@ class QPolicyBase(AtariCnnPolicy):
                 ov[s, j * per + idx] = np.random.randint(low=0, high=self.n_act, size=len(idx), dtype=np.uint8)
         # one table per env count (training / evaluation), allocated once: a captured rollout graph
         # keeps reading the same device buffer
-        if n_envs not in self._overrides or self._overrides[n_envs][1].shape[0] != horizon:
-            self._overrides[n_envs] = (torch.zeros(ov.shape, dtype=torch.int32).pin_memory(),
-                                       torch.zeros(ov.shape, dtype=torch.int32, device=self.device))
-        host, dev = self._overrides[n_envs]
+        host, dev = self._select_overrides(horizon, n_envs, lambda: (
+            torch.zeros(ov.shape, dtype=torch.int32).pin_memory(),
+            torch.zeros(ov.shape, dtype=torch.int32, device=self.device)))
         host.copy_(torch.from_numpy(ov))
         dev.copy_(host, non_blocking=True)
         return np.full(horizon * n_envs, 0.5)
+
+    def _select_overrides(self, horizon, n_envs, make):
+        """Make (once) and select the (pinned host, device) tables of one (env count, horizon).  A table is never
+        replaced: a captured rollout graph holds its device address, and training and evaluation may serve the same
+        number of envs over different horizons -- a table reallocated at every switch between them would leave the
+        graph reading whichever block the allocator happened to hand out for the one before."""
+        key = (n_envs, horizon)
+        if key not in self._override_tables:
+            self._override_tables[key] = make()
+        self._overrides[n_envs] = self._override_tables[key]
+        return self._overrides[n_envs]
 
     def set_step(self, s):
         self._step = s

@@ -33,7 +33,7 @@ from accel_rl_amd.envs import synthetic_atari as synth
 from accel_rl_amd.sampler.base import BaseMbSampler
 from accel_rl_amd.sampler.util import TrajInfo
 from accel_rl_amd.util import logger
-from accel_rl_amd.util.misc import graph_capture_mode, nbytes_unit, struct
+from accel_rl_amd.util.misc import capture_graph, nbytes_unit, struct
 
 NOOP_RING = 4096
 
@@ -446,7 +446,7 @@ class GpuVecSampler(BaseMbSampler):
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize(self.device)
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode=graph_capture_mode()):
+        with capture_graph(graph):
             self._enqueue_batch(cur)
         # warm-up and capture-time work must not count: restore the state
         for k, v in snap.items():

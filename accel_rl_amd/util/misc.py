@@ -1,5 +1,7 @@
 """Small host-side helpers mirroring accel_rl/util/misc.py (attr-dict `struct`,
 byte-size formatting, time-jitter seed)."""
+import contextlib
+import gc
 import time
 
 
@@ -56,3 +58,25 @@ def graph_capture_mode():
     by ANY other thread's HIP call; seen as 'operation failed due to a previous error during capture')."""
     import torch.distributed as dist
     return "thread_local" if dist.is_available() and dist.is_initialized() else "global"
+
+
+@contextlib.contextmanager
+def capture_graph(graph):
+    """`with torch.cuda.graph(graph, capture_error_mode=graph_capture_mode())`, with the cyclic garbage collector kept
+    out of the capture.  torch no longer collects before a capture, so a dead reference cycle that still holds an
+    earlier torch.cuda.CUDAGraph (a runner <-> sampler <-> algorithm left behind by its caller) waits for whichever
+    allocation next trips the collector -- and the capture body makes thousands.  A CUDAGraph destroyed there takes
+    the process down: on ROCm its destructor synchronises the device, which a global-mode capture forbids, and the
+    error is thrown from a destructor (seen as `Fatal Python error: Aborted` with `Garbage-collecting` on top of a
+    stack inside the capture).  So: collect first, while such a destructor is legal, and hold the collector off until
+    the capture has ended.  Reference counting still frees the body's temporaries at once."""
+    import torch
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, capture_error_mode=graph_capture_mode()):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()

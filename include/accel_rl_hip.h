@@ -798,6 +798,81 @@ int arl_qrdqn_loss(const float* pred, const float* tgt_next, const float* pol_ne
                    int32_t n_actions, int32_t n_quantiles, int32_t q_stride, int32_t dueling, float gamma_n, float kappa,
                    float* dtheta, float* loss_rows, float* priorities, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Implicit quantile networks (IQN)
+ * ------------------------------------------------------------------------- */
+
+/* IQN (Dabney et al. 2018, "Implicit Quantile Networks for Distributional RL"; the reference has none): the quantile
+ * fractions tau ~ U(0, 1) are drawn per sample, embedded with cosine features and multiplied into the conv features;
+ * the network's output holds one row per (sample, fraction) and one column per action:
+ *   theta f32[batch][R][a_stride], a_stride % 4 == 0, a_stride >= n_actions; the padding columns are ignored.
+ * The five entry points below refuse with ARL_E_ARG (-1), before any HIP call and with no output written: a NULL
+ * mandatory pointer, a size below 1, more than ARL_IQN_MAX_FRACTIONS (64) fractions per sample, more than 64 actions,
+ * a_stride % 4 != 0, a_stride < n_actions or > 2^20, batch or rows x R (row0 included) above 2^31 - 1, f % 4 != 0,
+ * f > 2^24, batch x R x f > 2^40, kappa negative or not finite, and arl_iqn_embed given neither or both of tau_in / state.  A vector operand
+ * (psi, phi, x, g, dphi, dpsi, cosf) not 16-byte aligned: ARL_E_ALIGN.  Plain fp32, no atomics, deterministic.   */
+#define ARL_IQN_COS 64                      /* cosine features per fraction (the paper's n = 64)               */
+#define ARL_IQN_MAX_FRACTIONS 64
+#define ARL_IQN_PHILOX_STREAM 0xC9514E31u   /* second key word; csrc/noisy.hip's streams are all below 2^31    */
+
+/* Fractions and their cosine features for rows x R (sample, fraction) pairs, pair (row, r) at p = row R + r:
+ *   tau f32[rows R], cosf f32[rows R][64], cosf[p][i] = cos(pi i tau[p]), i = 0 .. 63 (Eq. 4 of the paper, i = 0 included)
+ * given mode (tau_in != NULL, state == NULL): tau[p] = tau_in[p].
+ * drawn mode (state = int64[2] (seed, counter) != NULL, tau_in == NULL; the kernel only READS state):
+ *   e = (row0 + row) R + r; call = state[1] + call_offset (two's complement int64)
+ *   words = Philox4x32-10(key = ((uint32) seed, ARL_IQN_PHILOX_STREAM),
+ *                         counter = ((uint32)(e / 4), 0, (uint32) call, (uint32)(call >> 32)))
+ *   k = words[e % 4] >> 9 (23 bits);  tau = (2 k + 1) * 2^-24: exact in fp32, never 0 or 1.
+ *   row0 / call_offset let a chunked pass and the passes of one update read disjoint parts of the streams.
+ * Cosine: the argument is reduced in integers.  |tau| = s 2^e (s its 24-bit significand): the angle i tau (in units of
+ * pi) is i s 2^e exactly; it is taken modulo 2 and folded by cos(2 - t) = cos t, cos(1 - t) = -cos t and
+ * cos(1/2 - t) = sin t to t in [0, 1/4], all on integers, then cospif(t) or sinpif(t) of the device library is taken.
+ * t has at most 24 significant bits (converts exactly) whenever |tau| >= 2^-5 or tau is a drawn fraction; below that
+ * it is rounded once to fp32 (relative 2^-24).  i = 0 gives exactly 1, an odd multiple of 1/2 exactly 0.  A tau_in of
+ * magnitude 2^24 or more is an even integer (cos = 1); a tau_in that is not finite is not checked and also gives 1. */
+int arl_iqn_embed(const float* tau_in_or_null, const int64_t* state_or_null, int64_t row0, int64_t call_offset,
+                  int64_t rows, int32_t r, float* tau, float* cosf, void* stream);
+
+/* The merge x[b R + r][f] = psi[b][f] * phi[b R + r][f] (psi f32[batch][f] the rectified conv features, phi
+ * f32[batch R][f] the rectified embedding) and its backward pass for g = d loss / d x, f32[batch R][f]:
+ *   dphi[b R + r][f] = g[b R + r][f] * psi[b][f] where phi[b R + r][f] > 0, else 0
+ *   dpsi[b][f] = sum_r g[b R + r][f] * phi[b R + r][f] where psi[b][f] > 0, else 0; r ascending, the sum starts at 0.
+ * Both are the pre-activation gradients of the layers below.  One lane per float4 along f, the r loop inside it.   */
+int arl_iqn_merge_fwd(const float* psi, const float* phi, int64_t batch, int32_t r, int32_t f, float* x, void* stream);
+int arl_iqn_merge_bwd(const float* g, const float* psi, const float* phi, int64_t batch, int32_t r, int32_t f,
+                      float* dphi, float* dpsi, void* stream);
+
+/* Action serving: Q_a = (sum_k theta(k, a)) / K in fp32, k ascending, the sum starts at 0; greedy action = FIRST maximum
+ * (a = 0, then every a whose Q_a > the best so far); override, the one-hot row and `greedy` exactly as arl_qrdqn_act.
+ * state_or_null != NULL: after its own work one thread does state[1] += advance (the last launch of a pass that drew
+ * fractions; no launch of that pass reads state afterwards).
+ *   theta f32[batch][K][a_stride]; onehot f32[batch][n_actions]; greedy u8[batch] or NULL                            */
+int arl_iqn_act(const float* theta, const int32_t* override_or_null, int64_t batch, int32_t n_actions, int32_t k,
+                int32_t a_stride, float* onehot, uint8_t* greedy_or_null, int64_t* state_or_null, int64_t advance,
+                void* stream);
+
+/* Pairwise quantile-Huber loss at drawn fractions, with its gradient.  pred f32[batch][N][a_stride] at fractions
+ * tau_pred f32[batch][N]; tgt_next, pol_next_or_null f32[batch][N'][a_stride].  Per sample b,
+ * w_b = (is_weight_b or 1) / batch, keep = 1 - terminal_b, L the Huber function of arl_qrdqn_loss:
+ *   a*     = first maximum over a of Q_a (as arl_iqn_act, K = N') under pol_next if given (double DQN), else tgt_next
+ *   T_j    = returns_b + keep * (gamma_n * theta_tgt(j, a*))                      (fp32, in this order)
+ *   u_ij   = T_j - theta_pred(i, actions_b);  [u<0] = 1 for u < 0, else 0 (u == 0 counts as not negative)
+ *   kappa > 0:   rho_ij = |tau_i - [u_ij<0]| L(u_ij) / kappa
+ *                dtheta_i = -(w_b / N') sum_j |tau_i - [u_ij<0]| clip(u_ij, -kappa, kappa) / kappa
+ *   kappa == 0:  rho_ij = |tau_i - [u_ij<0]| |u_ij|
+ *                dtheta_i = -(w_b / N') sum_j (tau_i - [u_ij<0])
+ *   loss_b = (1 / N') sum_i sum_j rho_ij;  loss_rows[b] = w_b loss_b;  priorities[b] = clip(loss_b, 1e-6, 1e6).
+ * dtheta f32[batch][N][a_stride]: column actions_b of row i holds dtheta_i, everything else exact zeros.
+ * Summation order: for each i, four partial sums over j = w, w + 4, ... (w = 0 .. 3, ascending j, each from 0),
+ * combined as ((p0 + p1) + p2) + p3: no chain is longer than N' / 4 + 3 additions.  The loss then sums over i as a
+ * butterfly over the 64 lanes (lane ^ 32, ^ 16, ... ^ 1; lanes >= N add 0).  One 256-thread workgroup per sample.
+ * actions_b >= n_actions is read as n_actions - 1.  state_or_null / advance as in arl_iqn_act.                      */
+int arl_iqn_loss(const float* pred, const float* tau_pred, const float* tgt_next, const float* pol_next_or_null,
+                 const uint8_t* actions, const float* returns, const uint8_t* terminals,
+                 const float* is_weights_or_null, int64_t batch, int32_t n_actions, int32_t n, int32_t n_target,
+                 int32_t a_stride, float gamma_n, float kappa, float* dtheta, float* loss_rows, float* priorities,
+                 int64_t* state_or_null, int64_t advance, void* stream);
+
 /* Plain DQN action serving: greedy action = first maximum of the Q row (T.argmax), override as
  * above, one-hot row out.  Replaces AtariDqnPolicy.get_actions / actions_sym,
  * accel_rl/policies/dqn/atari_dqn_policy.py:61-63,76-79,118-130.
