@@ -72,6 +72,13 @@ class ArlFoldItem(C.Structure):
 FOLD_MAX_ITEMS = 24
 
 
+class ArlWgradPlan(C.Structure):
+    _fields_ = [("opaque", _i64 * 32)]
+
+
+WGRAD_GROUP_MAX = 4
+
+
 class ArlLogitSrc(C.Structure):
     _fields_ = [("part", _vp), ("bias_or_null", _vp), ("split_stride", _i64), ("splits", _i32), ("reserved", _i32)]
 
@@ -178,6 +185,15 @@ _SIGNATURES = {
     "arl_conv2d_bwd_pair": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _vp, _i64,
                                    C.POINTER(ArlFoldItem), _vp, C.POINTER(ArlFoldItem), C.POINTER(ArlCorunJob),
                                    C.POINTER(_i32), _vp]),
+    "arl_conv2d_bwd_weight_plan": (_i32, [_vp, _vp, _vp, C.POINTER(ArlConvGeom), _vp, _i64, C.POINTER(ArlFoldItem),
+                                          _vp, C.POINTER(ArlFoldItem), C.POINTER(ArlWgradPlan)]),
+    "arl_conv2d_u8_bwd_weight_plan": (_i32, [_vp, _vp, _i64, _vp, _f32, _vp, C.POINTER(ArlConvGeom), _vp, _i64,
+                                             C.POINTER(ArlFoldItem), _vp, C.POINTER(ArlFoldItem),
+                                             C.POINTER(ArlWgradPlan)]),
+    "arl_conv2d_bwd_pair_plan": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _vp, _i64,
+                                        C.POINTER(ArlFoldItem), _vp, C.POINTER(ArlFoldItem), C.POINTER(ArlCorunJob),
+                                        C.POINTER(_i32), C.POINTER(ArlWgradPlan), _vp]),
+    "arl_conv2d_bwd_weight_group": (_i32, [C.POINTER(ArlWgradPlan), _i32, _vp]),
     "arl_relu_bwd_bias_parts": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, C.POINTER(ArlFoldItem), _vp]),
     "arl_replay_append": (_i32, [C.POINTER(ArlReplay), _vp, _vp, _vp, _vp, _i32, _i32, _f64, _i32, _vp]),
     "arl_replay_extract": (_i32, [C.POINTER(ArlReplay), _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -756,11 +772,16 @@ def conv2d_bwd_weight(dy, x, dw, geom, workspace, stream=None):
 
 class FoldList(object):
     """Pending split folds of one backward pass (arl_fold_item): the *_parts calls append, run()
-    folds everything in one launch.  Every appended call needs its own workspace tensor."""
+    folds everything in one launch.  Every appended call needs its own workspace tensor.
+    With defer=True a weight-gradient call only plans its launch (arl_wgrad_plan; its fold items are appended as
+    usual): run_wgrads() then issues the planned ones, the group-eligible in one launch (arl_conv2d_bwd_weight_group),
+    before run()."""
 
     def __init__(self):
         self._items = (ArlFoldItem * FOLD_MAX_ITEMS)()
         self._n = 0
+        self._plans = (ArlWgradPlan * WGRAD_GROUP_MAX)()
+        self._n_plans = 0
         self.last_dw_in_place = False
         self.corun_taken = False
 
@@ -784,7 +805,19 @@ class FoldList(object):
             return False
         return True
 
-    def conv2d_bwd_weight(self, dy, x, dw, geom, workspace, dbias=None, stream=None):
+    def _next_plan(self, stream):
+        if self._n_plans == WGRAD_GROUP_MAX:        # a full list goes out as a group of its own
+            self.run_wgrads(stream)
+        self._n_plans += 1
+        return C.byref(self._plans[self._n_plans - 1])
+
+    def run_wgrads(self, stream=None):
+        """The deferred weight gradients' launch(es); their folds stay pending."""
+        n, self._n_plans = self._n_plans, 0
+        if n:
+            _check(load().arl_conv2d_bwd_weight_group(self._plans, n, stream_ptr(stream)), "arl_conv2d_bwd_weight_group")
+
+    def conv2d_bwd_weight(self, dy, x, dw, geom, workspace, dbias=None, stream=None, defer=False):
         """dw partials (and, with dbias, the column sums of dy) for the deferred fold.  Returns False when
         dbias was asked for but not produced (the caller then uses relu_bwd_bias_grad)."""
         ho, wo = conv_out_hw(geom)
@@ -793,12 +826,17 @@ class FoldList(object):
         assert dw.numel() == geom.out_c * geom.kh * geom.kw * geom.in_c, "dw size"
         item = self._next()
         pb, ib = self._bias_slot(dbias)
+        if defer:
+            _check(load().arl_conv2d_bwd_weight_plan(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), C.byref(geom),
+                                                     ptr(workspace), workspace.numel() * workspace.element_size(),
+                                                     item, pb, ib, self._next_plan(stream)), "arl_conv2d_bwd_weight_plan")
+            return self._bias_done(dbias)
         _check(load().arl_conv2d_bwd_weight_parts(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), C.byref(geom),
                                                   ptr(workspace), workspace.numel() * workspace.element_size(),
                                                   item, pb, ib, stream_ptr(stream)), "arl_conv2d_bwd_weight_parts")
         return self._bias_done(dbias)
 
-    def conv2d_u8_bwd_weight(self, dy, obs, idx, scale, dw, geom, workspace, dbias=None, stream=None):
+    def conv2d_u8_bwd_weight(self, dy, obs, idx, scale, dw, geom, workspace, dbias=None, stream=None, defer=False):
         """dw[K,C,kh,kw] partials (and, with dbias, the column sums of dy) of a convolution on u8 observations."""
         _u8_rows(obs, idx, geom)
         ho, wo = conv_out_hw(geom)
@@ -806,16 +844,24 @@ class FoldList(object):
         assert dw.numel() == geom.out_c * geom.kh * geom.kw * geom.in_c, "dw size"
         item = self._next()
         pb, ib = self._bias_slot(dbias)
+        if defer:
+            _check(load().arl_conv2d_u8_bwd_weight_plan(dy.data_ptr(), obs.data_ptr(), obs.shape[0], ptr(idx),
+                                                        float(scale), dw.data_ptr(), C.byref(geom), ptr(workspace),
+                                                        workspace.numel() * workspace.element_size(), item, pb, ib,
+                                                        self._next_plan(stream)), "arl_conv2d_u8_bwd_weight_plan")
+            return self._bias_done(dbias)
         _check(load().arl_conv2d_u8_bwd_weight_parts(dy.data_ptr(), obs.data_ptr(), obs.shape[0], ptr(idx),
                                                      float(scale), dw.data_ptr(), C.byref(geom), ptr(workspace),
                                                      workspace.numel() * workspace.element_size(), item, pb, ib,
                                                      stream_ptr(stream)), "arl_conv2d_u8_bwd_weight_parts")
         return self._bias_done(dbias)
 
-    def conv2d_bwd_pair(self, dy, w, mask, dx, x, dw, geom, workspace, dbias=None, stream=None, corun=None, wt=None):
+    def conv2d_bwd_pair(self, dy, w, mask, dx, x, dw, geom, workspace, dbias=None, stream=None, corun=None, wt=None,
+                        defer=False):
         """dx (times mask > 0 if given) and (deferred) dw [+ dbias] of one layer in a single launch.
         corun: an ArlCorunJob the data-gradient launch may carry; `self.corun_taken` says whether it did.
-        wt: conv2d_dgrad_weights' copy of w for the data gradient."""
+        wt: conv2d_dgrad_weights' copy of w for the data gradient.
+        defer: a layer that does not pair runs its data gradient now and leaves its weight gradient to run_wgrads()."""
         ho, wo = conv_out_hw(geom)
         assert dy.numel() == geom.batch * ho * wo * geom.out_c, "dy size"
         assert x.numel() == dx.numel() == geom.batch * geom.in_h * geom.in_w * geom.in_c, "x / dx size"
@@ -824,11 +870,19 @@ class FoldList(object):
         slot = self._n - 1
         pb, ib = self._bias_slot(dbias)
         taken = _i32(0)
-        _check(load().arl_conv2d_bwd_pair(dy.data_ptr(), w.data_ptr(), ptr(wt), ptr(mask), dx.data_ptr(), x.data_ptr(),
-                                          dw.data_ptr(), C.byref(geom), ptr(workspace),
-                                          workspace.numel() * workspace.element_size(), item, pb, ib,
-                                          None if corun is None else C.byref(corun), C.byref(taken),
-                                          stream_ptr(stream)), "arl_conv2d_bwd_pair")
+        if defer:
+            _check(load().arl_conv2d_bwd_pair_plan(dy.data_ptr(), w.data_ptr(), ptr(wt), ptr(mask), dx.data_ptr(),
+                                                   x.data_ptr(), dw.data_ptr(), C.byref(geom), ptr(workspace),
+                                                   workspace.numel() * workspace.element_size(), item, pb, ib,
+                                                   None if corun is None else C.byref(corun), C.byref(taken),
+                                                   self._next_plan(stream), stream_ptr(stream)),
+                   "arl_conv2d_bwd_pair_plan")
+        else:
+            _check(load().arl_conv2d_bwd_pair(dy.data_ptr(), w.data_ptr(), ptr(wt), ptr(mask), dx.data_ptr(), x.data_ptr(),
+                                              dw.data_ptr(), C.byref(geom), ptr(workspace),
+                                              workspace.numel() * workspace.element_size(), item, pb, ib,
+                                              None if corun is None else C.byref(corun), C.byref(taken),
+                                              stream_ptr(stream)), "arl_conv2d_bwd_pair")
         self.corun_taken = bool(taken.value)
         self.last_dw_in_place = self._items[slot].splits == 0      # no split partials: dw is final as written
         return self._bias_done(dbias)
@@ -865,6 +919,7 @@ class FoldList(object):
             "arl_pg_head_loss_parts")
 
     def run(self, stream=None):
+        self.run_wgrads(stream)                 # (partials that were only planned)
         n, self._n = self._n, 0
         _check(load().arl_fold_many(self._items, n, stream_ptr(stream)), "arl_fold_many")
 

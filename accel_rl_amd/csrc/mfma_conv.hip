@@ -1,5 +1,5 @@
 // Entry points of the MFMA contraction kernels (kernels and launchers: mfma_conv_impl.h; their instantiations are
-// built in mfma_conv_p1 .. p7.hip so that the translation units compile side by side).
+// built in mfma_conv_p1 .. p8.hip so that the translation units compile side by side).
 #include "mfma_conv_impl.h"
 #include "dgrad_wt_dev.h"
 
@@ -413,6 +413,42 @@ int dgrad_impl(const float* dy, const float* w, const float* mask_or_null, float
     return 0;
 }
 
+// the launch a planned weight gradient asks for (the route is the calling scope's: g_split == p.route)
+int launch_wgrad_plan(const WgradPlan& p, hipStream_t s) {
+    constexpr int FBK = 32;
+    const WgradArgs& a = p.a;
+    const int K = a.K_out, splits = p.splits;
+    if (p.kind == WPLAN_U8) {
+        // (cfg: 0 = 16-row tiles, 1 / 2 = split kernel on 256 / 128 columns, 3 = fp32 chain on 32-row tiles)
+        if (p.cfg == 1) return launch_wgrad_split<1, 4, 1, 2, FBK, true, 2>(a, splits, false, s);
+        if (p.cfg == 2) return launch_wgrad_split<1, 4, 1, 1, FBK, true, 2>(a, splits, false, s);
+        const int bm = K <= 16 ? 16 : 32, bn = 128;
+        const size_t lds = (size_t)2 * FBK * (bm + bn) * sizeof(float);
+        const dim3 grid((a.N + bn - 1) / bn, (K + bm - 1) / bm, splits);
+        if (p.cfg == 0) hipLaunchKernelGGL((wgrad_u8_kernel<1, 4, 1, 1, FBK, true>), grid, dim3(256), lds, s, a);
+        else hipLaunchKernelGGL((wgrad_u8_kernel<1, 4, 1, 1, FBK, false>), grid, dim3(256), lds, s, a);
+        return arl::check_launch("wgrad_u8_kernel");
+    }
+    if (p.fast) {
+        if (K <= 16) return launch_wgrad_fast<1, 4, 1, 1, FBK, true>(a, splits, p.has_pad, s);       // 16-row MFMA tiles
+        if (g_split && K <= 32) return launch_wgrad_split<1, 4, 1, 1, FBK, false, 2>(a, splits, p.has_pad, s);
+        if (g_split && K <= 64) return launch_wgrad_split<2, 2, 1, 1, FBK, false, 2>(a, splits, p.has_pad, s);
+        if (g_split) return launch_wgrad_split<2, 2, 2, 2, FBK, false, 1>(a, splits, p.has_pad, s);
+        if (K <= 32) return launch_wgrad_fast<1, 4, 1, 1, FBK>(a, splits, p.has_pad, s);
+        if (K <= 64) return launch_wgrad_fast<2, 2, 1, 1, FBK>(a, splits, p.has_pad, s);
+        return launch_wgrad_fast<2, 2, 2, 2, FBK>(a, splits, p.has_pad, s);
+    }
+    if (K <= 32) return launch_wgrad<1, 4, 1, 1, 16>(a, splits, s);
+    if (K <= 64) return launch_wgrad<2, 2, 1, 1, 16>(a, splits, s);
+    return launch_wgrad<2, 2, 2, 2, 16>(a, splits, s);
+}
+
+// workgroups of a group-eligible plan's own launch (launch_wgrad_split's grid)
+int group_blocks(const WgradPlan& p) {
+    const int bm = p.kind == WPLAN_U8 ? 32 : 64, bn = p.kind == WPLAN_U8 ? (p.cfg == 1 ? 256 : 128) : 64;
+    return ((p.a.N + bn - 1) / bn) * ((p.a.K_out + bm - 1) / bm) * p.splits;
+}
+
 // weight gradient; with more than one row split the partials go to `workspace` and *splits_out > 1
 // bias_part_out (optional): the fast kernels also leave [splits][K_out] column sums of dy behind the
 // weight partials in `workspace`; *bias_part_out = their address, or null when the generic kernels ran.
@@ -472,28 +508,14 @@ int wgrad_impl(const float* dy, const float* x, float* dw, const arl_conv_geom* 
         a.adv_b = WG_ROWS / img;
         a.adv_y = (WG_ROWS % img) / g.Wo;
         a.adv_x = (WG_ROWS % img) % g.Wo;
-        if (plan_only) {
-            plan_only->a = a; plan_only->fast = true; plan_only->has_pad = has_pad;
-            plan_only->cfg = g.K <= 32 ? 0 : g.K <= 64 ? 1 : 2;
-            plan_only->splits = splits; plan_only->total = total;
-            return 0;
-        }
-        if (g.K <= 16) rc = launch_wgrad_fast<1, 4, 1, 1, FBK, true>(a, splits, has_pad, s);       // 16-row MFMA tiles
-        else if (g_split && g.K <= 32) rc = launch_wgrad_split<1, 4, 1, 1, FBK, false, 2>(a, splits, has_pad, s);
-        else if (g_split && g.K <= 64) rc = launch_wgrad_split<2, 2, 1, 1, FBK, false, 2>(a, splits, has_pad, s);
-        else if (g_split) rc = launch_wgrad_split<2, 2, 2, 2, FBK, false, 1>(a, splits, has_pad, s);
-        else if (g.K <= 32) rc = launch_wgrad_fast<1, 4, 1, 1, FBK>(a, splits, has_pad, s);
-        else if (g.K <= 64) rc = launch_wgrad_fast<2, 2, 1, 1, FBK>(a, splits, has_pad, s);
-        else rc = launch_wgrad_fast<2, 2, 2, 2, FBK>(a, splits, has_pad, s);
-    } else {
-        if (plan_only) { plan_only->fast = false; return 0; }
-        if (g.K <= 32) rc = launch_wgrad<1, 4, 1, 1, 16>(a, splits, s);
-        else if (g.K <= 64) rc = launch_wgrad<2, 2, 1, 1, 16>(a, splits, s);
-        else rc = launch_wgrad<2, 2, 2, 2, 16>(a, splits, s);
     }
+    WgradPlan p = {};
+    p.a = a; p.fast = fast; p.has_pad = has_pad; p.cfg = g.K <= 32 ? 0 : g.K <= 64 ? 1 : 2;
+    p.splits = splits; p.total = total; p.kind = WPLAN_F32; p.route = g_split;
     *splits_out = splits;
     *total_out = total;
-    return rc;
+    if (plan_only) { *plan_only = p; return 0; }
+    return launch_wgrad_plan(p, s);
 }
 }  // namespace
 
@@ -524,14 +546,15 @@ void bias_item(arl_fold_item* item, const float* bias_part, float* dbias, int sp
 }
 int wgrad_parts_impl(const float* dy, const float* x, float* dw, const arl_conv_geom* geom,
                      void* workspace, int64_t workspace_bytes, arl_fold_item* item,
-                     float* dbias_or_null, arl_fold_item* bias_item_or_null, void* stream) {
+                     float* dbias_or_null, arl_fold_item* bias_item_or_null, void* stream,
+                     WgradPlan* plan_only = nullptr) {
     ARL_REQUIRE(item && (!dbias_or_null || bias_item_or_null), ARL_E_ARG, "null pointer");
     ARL_REQUIRE(!dbias_or_null || arl::aligned16(dbias_or_null), ARL_E_ALIGN, "16-byte alignment");
     int splits = 1;
     int64_t total = 0;
     float* bias_part = nullptr;
     int rc = wgrad_impl(dy, x, dw, geom, workspace, workspace_bytes, &splits, &total,
-                        dbias_or_null ? &bias_part : nullptr, nullptr, stream);
+                        dbias_or_null ? &bias_part : nullptr, plan_only, stream);
     item->part = (const float*)workspace; item->out = dw; item->total = total;
     item->splits = splits > 1 ? splits : 0;             // 0: dw is already final
     item->valid = 0;
@@ -545,6 +568,18 @@ extern "C" int arl_conv2d_bwd_weight_parts(const float* dy, const float* x, floa
                                            float* dbias_or_null, arl_fold_item* bias_item_or_null, void* stream) {
     ARL_ROUTE_SCOPE(geom, nullptr);
     return wgrad_parts_impl(dy, x, dw, geom, workspace, workspace_bytes, item, dbias_or_null, bias_item_or_null, stream);
+}
+
+static_assert(sizeof(WgradPlan) <= sizeof(arl_wgrad_plan), "arl_wgrad_plan too small");
+
+extern "C" int arl_conv2d_bwd_weight_plan(const float* dy, const float* x, float* dw, const arl_conv_geom* geom,
+                                          void* workspace, int64_t workspace_bytes, arl_fold_item* item,
+                                          float* dbias_or_null, arl_fold_item* bias_item_or_null, arl_wgrad_plan* plan) {
+    ARL_REQUIRE(plan, ARL_E_ARG, "null pointer");
+    *plan = arl_wgrad_plan{};
+    ARL_ROUTE_SCOPE(geom, nullptr);
+    return wgrad_parts_impl(dy, x, dw, geom, workspace, workspace_bytes, item, dbias_or_null, bias_item_or_null, nullptr,
+                            reinterpret_cast<WgradPlan*>(plan));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -630,11 +665,10 @@ extern "C" int arl_conv2d_u8_fwd(const uint8_t* obs, int64_t obs_rows, const int
     return arl::check_launch("igemm_u8_kernel");
 }
 
-extern "C" int arl_conv2d_u8_bwd_weight_parts(const float* dy, const uint8_t* obs, int64_t obs_rows,
-                                              const int32_t* idx_or_null, float scale, float* dw,
-                                              const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes,
-                                              arl_fold_item* item, float* dbias_or_null,
-                                              arl_fold_item* bias_item_or_null, void* stream) {
+namespace {
+int wgrad_u8_impl(const float* dy, const uint8_t* obs, int64_t obs_rows, const int32_t* idx_or_null, float scale, float* dw,
+                  const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes, arl_fold_item* item,
+                  float* dbias_or_null, arl_fold_item* bias_item_or_null, WgradPlan* plan_only, void* stream) {
     ARL_REQUIRE(dy && dw && workspace && item && (!dbias_or_null || bias_item_or_null), ARL_E_ARG, "null pointer");
     U8Geom g;
     int rc = check_u8(obs, obs_rows, geom, &g);
@@ -667,28 +701,47 @@ extern "C" int arl_conv2d_u8_bwd_weight_parts(const float* dy, const uint8_t* ob
     if (dbias_or_null) a.bias_part = (float*)workspace + used;
     const int img = g.Ho * g.Wo;
     a.adv_b = WG_ROWS / img; a.adv_y = (WG_ROWS % img) / g.Wo; a.adv_x = (WG_ROWS % img) % g.Wo;
-    constexpr int BK = 32;
-    const size_t lds = (size_t)2 * BK * (bm + bn) * sizeof(float);
-    const dim3 grid((a.N + bn - 1) / bn, (a.K_out + bm - 1) / bm, splits);
-    if (g.K > 16 && g_split && g.kw % 8 == 0) {     // (the split kernel gathers whole 8-pixel filter rows)
-        if (wide) rc = launch_wgrad_split<1, 4, 1, 2, BK, true, 2>(a, splits, false, (hipStream_t)stream);
-        else rc = launch_wgrad_split<1, 4, 1, 1, BK, true, 2>(a, splits, false, (hipStream_t)stream);
-        if (rc) return rc;
-    } else if (g.K <= 16) hipLaunchKernelGGL((wgrad_u8_kernel<1, 4, 1, 1, BK, true>), grid, dim3(256), lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((wgrad_u8_kernel<1, 4, 1, 1, BK, false>), grid, dim3(256), lds, (hipStream_t)stream, a);
+    WgradPlan p = {};
+    p.a = a; p.splits = splits; p.total = total; p.kind = WPLAN_U8; p.route = g_split;
+    // (the split kernel gathers whole 8-pixel filter rows)
+    p.cfg = g.K > 16 && g_split && g.kw % 8 == 0 ? (wide ? 1 : 2) : g.K <= 16 ? 0 : 3;
+    p.fast = p.cfg == 1 || p.cfg == 2;
     item->part = (const float*)workspace; item->out = dw; item->total = total;
     item->splits = splits > 1 ? splits : 0;
     item->valid = 0;
     if (dbias_or_null) bias_item(bias_item_or_null, a.bias_part, dbias_or_null, splits, g.K);
-    return arl::check_launch("wgrad_u8_kernel");
+    if (plan_only) { *plan_only = p; return 0; }
+    return launch_wgrad_plan(p, (hipStream_t)stream);
+}
+}  // namespace
+
+extern "C" int arl_conv2d_u8_bwd_weight_parts(const float* dy, const uint8_t* obs, int64_t obs_rows,
+                                              const int32_t* idx_or_null, float scale, float* dw,
+                                              const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes,
+                                              arl_fold_item* item, float* dbias_or_null,
+                                              arl_fold_item* bias_item_or_null, void* stream) {
+    return wgrad_u8_impl(dy, obs, obs_rows, idx_or_null, scale, dw, geom, workspace, workspace_bytes, item, dbias_or_null,
+                         bias_item_or_null, nullptr, stream);
+}
+
+extern "C" int arl_conv2d_u8_bwd_weight_plan(const float* dy, const uint8_t* obs, int64_t obs_rows,
+                                             const int32_t* idx_or_null, float scale, float* dw,
+                                             const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes,
+                                             arl_fold_item* item, float* dbias_or_null,
+                                             arl_fold_item* bias_item_or_null, arl_wgrad_plan* plan) {
+    ARL_REQUIRE(plan, ARL_E_ARG, "null pointer");
+    *plan = arl_wgrad_plan{};
+    return wgrad_u8_impl(dy, obs, obs_rows, idx_or_null, scale, dw, geom, workspace, workspace_bytes, item, dbias_or_null,
+                         bias_item_or_null, reinterpret_cast<WgradPlan*>(plan), nullptr);
 }
 
 
-extern "C" int arl_conv2d_bwd_pair(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
-                                   float* dx, const float* x, float* dw, const arl_conv_geom* geom, void* workspace,
-                                   int64_t workspace_bytes, arl_fold_item* item, float* dbias_or_null,
-                                   arl_fold_item* bias_item_or_null, const arl_corun_job* job_or_null,
-                                   int32_t* job_taken_or_null, void* stream) {
+namespace {
+// defer: the weight gradient of a layer that does not pair is planned into *defer instead of launched
+int pair_impl(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null, float* dx, const float* x,
+              float* dw, const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes, arl_fold_item* item,
+              float* dbias_or_null, arl_fold_item* bias_item_or_null, const arl_corun_job* job_or_null,
+              int32_t* job_taken_or_null, WgradPlan* defer, void* stream) {
     ARL_REQUIRE(item && geom && (!dbias_or_null || bias_item_or_null), ARL_E_ARG, "null pointer");
     if (job_taken_or_null) *job_taken_or_null = 0;
     ARL_ROUTE_SCOPE(geom, job_or_null);
@@ -722,7 +775,7 @@ extern "C" int arl_conv2d_bwd_pair(const float* dy, const float* w, const float*
                         wt_or_null);
         if (job_taken_or_null) *job_taken_or_null = t_ctx.corun_taken ? 1 : 0;
         if (rc) return rc;
-        return wgrad_parts_impl(dy, x, dw, geom, workspace, half, item, dbias_or_null, bias_item_or_null, stream);
+        return wgrad_parts_impl(dy, x, dw, geom, workspace, half, item, dbias_or_null, bias_item_or_null, stream, defer);
     }
     hipStream_t s = (hipStream_t)stream;
     // split kernels: 16-deep k-tiles halve the LDS images (98 -> 49 KB), so that TWO workgroups share a CU and one's
@@ -735,6 +788,80 @@ extern "C" int arl_conv2d_bwd_pair(const float* dy, const float* w, const float*
     item->valid = 0;
     if (dbias_or_null) bias_item(bias_item_or_null, bias_part, dbias_or_null, wp.splits, geom->out_c);
     return rc;
+}
+}  // namespace
+
+extern "C" int arl_conv2d_bwd_pair(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
+                                   float* dx, const float* x, float* dw, const arl_conv_geom* geom, void* workspace,
+                                   int64_t workspace_bytes, arl_fold_item* item, float* dbias_or_null,
+                                   arl_fold_item* bias_item_or_null, const arl_corun_job* job_or_null,
+                                   int32_t* job_taken_or_null, void* stream) {
+    return pair_impl(dy, w, wt_or_null, mask_or_null, dx, x, dw, geom, workspace, workspace_bytes, item, dbias_or_null,
+                     bias_item_or_null, job_or_null, job_taken_or_null, nullptr, stream);
+}
+
+extern "C" int arl_conv2d_bwd_pair_plan(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
+                                        float* dx, const float* x, float* dw, const arl_conv_geom* geom, void* workspace,
+                                        int64_t workspace_bytes, arl_fold_item* item, float* dbias_or_null,
+                                        arl_fold_item* bias_item_or_null, const arl_corun_job* job_or_null,
+                                        int32_t* job_taken_or_null, arl_wgrad_plan* plan, void* stream) {
+    ARL_REQUIRE(plan, ARL_E_ARG, "null pointer");
+    *plan = arl_wgrad_plan{};                       // (kind 0: nothing left to launch)
+    return pair_impl(dy, w, wt_or_null, mask_or_null, dx, x, dw, geom, workspace, workspace_bytes, item, dbias_or_null,
+                     bias_item_or_null, job_or_null, job_taken_or_null, reinterpret_cast<WgradPlan*>(plan), stream);
+}
+
+// The planned weight gradients of a backward pass: the group-eligible ones (a bf16-split route, one of
+// wgrad_group_kernel's bodies, no trace buffer) in one launch, every other one on its own first.
+extern "C" int arl_conv2d_bwd_weight_group(const arl_wgrad_plan* plans, int32_t n, void* stream) {
+    ARL_REQUIRE(plans || n == 0, ARL_E_ARG, "null pointer");
+    ARL_REQUIRE(n >= 0 && n <= ARL_WGRAD_GROUP_MAX, ARL_E_RANGE, "0 .. ARL_WGRAD_GROUP_MAX plans");
+    hipStream_t s = (hipStream_t)stream;
+    const WgradPlan* pl[ARL_WGRAD_GROUP_MAX];
+    for (int i = 0; i < n; ++i) pl[i] = reinterpret_cast<const WgradPlan*>(&plans[i]);
+    auto body_of = [](const WgradPlan& p) {         // wgrad_group_kernel's body, or -1
+        if (!p.route || g_trace) return -1;
+        if (p.kind == WPLAN_U8) return p.cfg == 1 ? 2 : p.cfg == 2 ? 3 : -1;
+        return p.kind == WPLAN_F32 && p.fast && p.cfg == 1 ? (p.has_pad ? 1 : 0) : -1;
+    };
+    int route = 0, n_el = 0, el[ARL_WGRAD_GROUP_MAX];
+    for (int i = 0; i < n; ++i) {                   // the group's route is its first eligible plan's
+        if (pl[i]->kind != WPLAN_F32 && pl[i]->kind != WPLAN_U8) continue;
+        if (body_of(*pl[i]) >= 0 && !route) route = pl[i]->route;
+        if (body_of(*pl[i]) >= 0 && pl[i]->route == route) el[n_el++] = i;
+    }
+    for (int i = 0; i < n; ++i) {
+        if (pl[i]->kind != WPLAN_F32 && pl[i]->kind != WPLAN_U8) continue;
+        bool grouped = false;
+        for (int k = 0; k < n_el; ++k) grouped = grouped || el[k] == i;
+        if (grouped && n_el > 1) continue;
+        const CallScope scope(pl[i]->route);
+        const int rc = launch_wgrad_plan(*pl[i], s);
+        if (rc) return rc;
+    }
+    if (n_el < 2) return 0;
+    // largest item first
+    for (int i = 1; i < n_el; ++i)
+        for (int k = i; k > 0 && group_blocks(*pl[el[k]]) > group_blocks(*pl[el[k - 1]]); --k) std::swap(el[k], el[k - 1]);
+    WgradGroupArgs g = {};
+    size_t lds = 0;
+    int groups = 0;
+    for (int k = 0; k < n_el; ++k) {
+        const WgradPlan& p = *pl[el[k]];
+        const int body = body_of(p);
+        const int bm = body < 2 ? 64 : 32, bn = body < 2 ? 64 : body == 2 ? 256 : 128;
+        const int npl = planes_of(route);
+        const size_t l = (size_t)2 * (npl * bm + (body < 2 ? npl : 1) * bn) * 32 * 2;      // launch_wgrad_split's
+        if (l > lds) lds = l;
+        g.a[k] = p.a; g.body[k] = body;
+        g.gx[k] = (p.a.N + bn - 1) / bn; g.gy[k] = (p.a.K_out + bm - 1) / bm;
+        g.blocks[k] = group_blocks(p);
+        g.group_start[k] = groups;
+        groups += (g.blocks[k] + 7) / 8;
+    }
+    g.group_start[n_el] = groups; g.n = n_el;
+    const CallScope scope(route);
+    return launch_wgrad_group(g, groups, lds, s);
 }
 
 namespace {

@@ -6,7 +6,7 @@
 //   mfma_wgrad.h     scalar-addressed weight gradient (wgrad_fast_body)
 //   mfma_pair.h      data + weight gradient of one layer in one launch
 //   mfma_dispatch.h  launchers, per-call context, instantiation lists
-// Entry points: mfma_conv.hip; instantiations: mfma_conv_p1 .. p7.hip.
+// Entry points: mfma_conv.hip; instantiations: mfma_conv_p1 .. p8.hip.
 #pragma once
 #include "mfma_common.h"
 #include "mfma_generic.h"

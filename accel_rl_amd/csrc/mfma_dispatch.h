@@ -1,4 +1,4 @@
-// Launchers, per-call context, split planning and the instantiation lists dealt out to mfma_conv_p1 .. p7.hip.
+// Launchers, per-call context, split planning and the instantiation lists dealt out to mfma_conv_p1 .. p8.hip.
 // Part of mfma_conv_impl.h.
 #pragma once
 #include "mfma_generic.h"
@@ -287,7 +287,11 @@ inline void plan_split(int tiles, int red, int* splits, int* per, int want = TAR
 // (arl_conv2d_bwd_pair).  cfg: data gradient 0 = <4,1,1,1>, 1 = <2,2,1,1>, 2 = <2,2,2,2>;
 // weight gradient 0 = <1,4,1,1>, 1 = <2,2,1,1>, 2 = <2,2,2,2>.
 struct DgradPlan { GemmArgs a; bool fast, has_pad; int cfg; };
-struct WgradPlan { WgradArgs a; bool fast, has_pad; int cfg, splits; int64_t total; };
+// kind / route: what arl_wgrad_plan keeps of a deferred weight gradient (arl_conv2d_bwd_weight_group): WPLAN_F32 = f32
+// input (wgrad_impl; cfg as above), WPLAN_U8 = planar u8 input (cfg 0 = 16-row tiles, 1 / 2 = split kernel on 256 / 128
+// columns, 3 = fp32 chain on 32-row tiles), 0 = nothing to launch; route = the planning call's split mode.
+constexpr int WPLAN_F32 = 1, WPLAN_U8 = 2;
+struct WgradPlan { WgradArgs a; bool fast, has_pad; int cfg, splits; int64_t total; int kind, route; };
 
 template <int DWGM, int DWGN, int DTM, int DTN, int WWGM, int WWGN, int WTM, int WTN, int BK = 32>
 int launch_pair(const DgradPlan& d, const WgradPlan& w, bool has_pad, hipStream_t s) {
@@ -372,6 +376,22 @@ int launch_conv1_img(const unsigned char* obs, int64_t obs_rows, const int32_t* 
     T int launch_wgrad_fast<1, 4, 1, 1, 32, true>(const WgradArgs&, int, bool, hipStream_t);
 #ifndef ARL_CONV_PART
 #define ARL_CONV_PART 0
+#endif
+// (part 8: the grouped weight gradient, three routes of one kernel that holds four bodies)
+int launch_wgrad_group(const WgradGroupArgs& g, int groups, size_t lds, hipStream_t s);
+#if ARL_CONV_PART == 8
+int launch_wgrad_group(const WgradGroupArgs& g, int groups, size_t lds, hipStream_t s) {
+    int rc = 0;
+#define ARL_WGROUP(SPL)                                                                                    \
+    do {                                                                                                   \
+        auto k = wgrad_group_kernel<SPL>;                                                                  \
+        rc = allow_big_lds(k, lds + 4096);                                                                 \
+        if (!rc) hipLaunchKernelGGL(k, dim3((unsigned)groups * 8), dim3(256), lds, s, g);                  \
+    } while (0)
+    ARL_BY_MODE(ARL_WGROUP(1), ARL_WGROUP(6), ARL_WGROUP(9));
+#undef ARL_WGROUP
+    return rc ? rc : arl::check_launch("wgrad_group_kernel");
+}
 #endif
 #define ARL_T_DEF template
 #define ARL_T_EXT extern template

@@ -12,6 +12,14 @@ namespace arlc {
 // Requirements: Mred % 256 == 0 is NOT needed, but Mred % BK == 0 and m_per_split % BK == 0.
 constexpr int WG_ROWS = 256;
 
+// The row table of wgrad_fast_body, in a function of its own so that a kernel that holds several instantiations of the
+// body (wgrad_group_kernel) pays for ONE table: a table per body put that kernel at 64 KB of LDS, two workgroups per
+// CU where the single-body kernels (53 KB) fit three.
+__device__ __forceinline__ uint2 (*wgrad_row_table())[WG_ROWS] {
+    __shared__ uint2 table[2][WG_ROWS];
+    return table;
+}
+
 // M16: <= 16 output channels (spec 0's conv 1) -> v_mfma_f32_16x16x4_f32, 16 channel rows x 16-column groups
 // (a 32-row tile would spend half of every MFMA on channels that do not exist).
 // U8: the gathered rows come from planar u8 images (GatherDesc::src8; column r = (ch * kh8 + ty) * kw8 + tx,
@@ -40,7 +48,7 @@ __device__ __forceinline__ void wgrad_fast_body(const WgradArgs& a, const int bx
     char* const sS = reinterpret_cast<char*>(smem);
     constexpr int TILES_PER_GROUP = WG_ROWS / BK;
     static_assert(WGM * WGN == 4 && 256 % NC4 == 0 && BK % KROWS == 0 && BK % 8 == 0 && WG_ROWS % BK == 0, "tile shape");
-    __shared__ uint2 s_row[2][WG_ROWS];     // per gathered row: byte offset of its tap origin, inverted tap mask
+    uint2 (*const s_row)[WG_ROWS] = wgrad_row_table();     // per gathered row: byte offset of its tap origin, inverted tap mask
     float* sA = smem;
     float* sB = smem + 2 * A_SZ;
     unsigned long long tr0 = 0, tr1 = 0, tr2 = 0, rt0 = 0;
@@ -541,6 +549,42 @@ __global__ __launch_bounds__(256, MINW) void wgrad_split_kernel(const WgradArgs 
         by = u % gy; bz = u / gy;
     }
     wgrad_fast_body<WGM, WGN, TM, TN, BK, HAS_PAD, false, U8, SPLIT>(a, bx, by, bz, smem);
+}
+
+// Several independent weight gradients in one launch (arl_conv2d_bwd_weight_group): the grid is dealt out in GROUPS of
+// eight consecutive blocks -- one per XCD, as the dispatcher deals them -- and a group belongs to one item (the items
+// one behind the other, largest first; interleaving them in proportion to their sizes measured slower), so that
+// block 8 g + x of an item is on the XCD where block 8 g + x of the item's own launch would have been: xcd_chunk keeps
+// handing every XCD the contiguous tile range it has today.  An item's last group may be ragged (its surplus blocks
+// leave at once).  Every other workgroup rebuilds its item's (bx, by, bz) as wgrad_split_kernel does and runs that
+// item's unchanged body: the same tiles, products, partials and bias sums at the same addresses.  Nothing is shared
+// between workgroups.  body: 0 / 1 = <2,2,1,1> without / with padding, 2 = u8 <1,4,1,2>, 3 = u8 <1,4,1,1>.
+struct WgradGroupArgs {
+    WgradArgs a[ARL_WGRAD_GROUP_MAX];
+    int gx[ARL_WGRAD_GROUP_MAX], gy[ARL_WGRAD_GROUP_MAX], blocks[ARL_WGRAD_GROUP_MAX], body[ARL_WGRAD_GROUP_MAX];
+    int group_start[ARL_WGRAD_GROUP_MAX + 1];       // in groups of eight blocks, items in launch order
+    int n;
+};
+
+template <int SPLIT>
+__global__ __launch_bounds__(256, 2) void wgrad_group_kernel(const WgradGroupArgs g) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int grp = (int)blockIdx.x >> 3;
+    int it = 0;
+    while (it + 1 < g.n && grp >= g.group_start[it + 1]) ++it;                  // uniform
+    const int id = ((grp - g.group_start[it]) << 3) | ((int)blockIdx.x & 7);    // the block's index in its item's own grid
+    const int blocks = g.blocks[it];
+    if (id >= blocks) return;
+    const int gx = g.gx[it], gy = g.gy[it];
+    const int t = g.a[it].xcd ? xcd_chunk(id, blocks) : id;
+    const int bx = t % gx, u = t / gx;
+    const int by = u % gy, bz = u / gy;
+    switch (g.body[it]) {
+    case 0: wgrad_fast_body<2, 2, 1, 1, 32, false, false, false, SPLIT>(g.a[it], bx, by, bz, smem); break;
+    case 1: wgrad_fast_body<2, 2, 1, 1, 32, true, false, false, SPLIT>(g.a[it], bx, by, bz, smem); break;
+    case 2: wgrad_fast_body<1, 4, 1, 2, 32, false, false, true, SPLIT>(g.a[it], bx, by, bz, smem); break;
+    default: wgrad_fast_body<1, 4, 1, 1, 32, false, false, true, SPLIT>(g.a[it], bx, by, bz, smem); break;
+    }
 }
 
 }  // namespace arlc

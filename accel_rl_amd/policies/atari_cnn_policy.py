@@ -558,20 +558,24 @@ class AtariCnnPolicy(object):
             items = self._dgrad_weight_items(b)
             if items:
                 _lib.conv2d_dgrad_weights(items)
+        # the data gradients first: the layers' weight gradients, independent of one another, are only planned and then
+        # share one launch (arl_conv2d_bwd_weight_group); ARL_WGRAD_GROUP=0: each right behind its data gradient (A/B switch)
+        group = os.environ.get("ARL_WGRAD_GROUP", "1") != "0"
         for i in range(self._n_conv - 1, -1, -1):
             nf, ci, sz, st, pad, ho, wo = self._conv_geom[i]
             d_in = self._buffer(("dx_conv", i, b), tuple(acts[i - 1].shape)) if i > 0 else None
             self._layer_grads(d_act, masked, acts[i], b * ho * wo, nf, 2 * i, conv_g[i], acts[i - 1] if i > 0 else x, d_in,
                               corun=corun if i > 0 else None,
-                              wt=self._wt.get(i) if _lib.default_route != _lib.ROUTE_FP32 else None)
+                              wt=self._wt.get(i) if _lib.default_route != _lib.ROUTE_FP32 else None, defer=group)
             if corun is not None and i > 0 and self._folds.corun_taken:
                 corun = None
             d_act, masked = d_in, True
+        self._folds.run_wgrads()
         if corun is not None:
             _lib.corun_job_run(corun)           # no launch could carry it: on its own, ahead of the step's update
         self._folds.run()
 
-    def _layer_grads(self, d, masked, y, rows, channels, k, geom, inp, d_in, corun=None, wt=None):
+    def _layer_grads(self, d, masked, y, rows, channels, k, geom, inp, d_in, corun=None, wt=None, defer=False):
         """One layer's backward: bias and weight gradient (deferred folds) and, with d_in, the data gradient
         already multiplied by the rectifier mask of `inp` (the layer below's output), so that the layer below
         gets its pre-activation gradient without another pass.  Not `masked`: d still needs this layer's own
@@ -582,12 +586,12 @@ class AtariCnnPolicy(object):
         dbias = g[k + 1] if masked else None
         if isinstance(inp, ObsRows):
             done = folds.conv2d_u8_bwd_weight(d, inp.obs, inp.idx, self._scale, self._g[k], geom,
-                                              self._fold_ws(("dw", k)), dbias=dbias)
+                                              self._fold_ws(("dw", k)), dbias=dbias, defer=defer)
         elif d_in is not None:      # data + weight gradient share one launch where that pays (dense layers)
             done = folds.conv2d_bwd_pair(d, self._w[k], inp, d_in, inp, self._g[k], geom, self._fold_ws(("dw", k)),
-                                         dbias=dbias, corun=corun, wt=wt)
+                                         dbias=dbias, corun=corun, wt=wt, defer=defer)
         else:
-            done = folds.conv2d_bwd_weight(d, inp, self._g[k], geom, self._fold_ws(("dw", k)), dbias=dbias)
+            done = folds.conv2d_bwd_weight(d, inp, self._g[k], geom, self._fold_ws(("dw", k)), dbias=dbias, defer=defer)
         if not done:                # generic kernels leave the bias sums to the streaming kernel (its mask is idempotent)
             folds.relu_bwd_bias_grad(d, y, rows, channels, g[k + 1], self._fold_ws(("db", k)))
 

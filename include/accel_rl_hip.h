@@ -604,6 +604,41 @@ int arl_conv2d_u8_bwd_weight_parts(const float* dy, const uint8_t* obs, int64_t 
                                    arl_fold_item* item, float* dbias_or_null,
                                    arl_fold_item* bias_item_or_null, void* stream);
 
+/* Several layers' weight gradients as ONE launch.  The weight gradients of a backward pass do not depend on one another
+ * (each reads its own layer's dy and input), so the caller walks the data gradients first and has every weight gradient
+ * described instead of launched: a caller-owned arl_wgrad_plan per layer, filled by the *_plan calls below, which
+ * validate, plan the row split and fill the fold item(s) exactly as their launching counterparts do (same workspace,
+ * same split count, same partial layout, same bias partials) and launch nothing.  arl_conv2d_bwd_weight_group then
+ * runs up to ARL_WGRAD_GROUP_MAX plans: those on a bf16-split route whose kernel is one of the 64-filter f32 tile or the
+ * two u8 tiles share one grid -- every workgroup finds its layer from its block index and does what its layer's own
+ * launch would have had it do, writing where it would have written (bit-identical partials; no synchronisation between
+ * workgroups) -- one ramp and one tail instead of three, and the L1-bound u8 workgroups resident beside matrix-bound
+ * ones.  Every other plan (fp32 route, generic kernels, <= 16 filters, other tiles, a trace buffer set) is launched on
+ * its own first, as arl_conv2d_bwd_weight_parts / arl_conv2d_u8_bwd_weight_parts would have; so is a single eligible
+ * plan.  The plans' buffers must stay untouched between the *_plan call and the group's launch.
+ * Replaces the same T.grad nodes as arl_conv2d_bwd_weight (optimizers/single/ppo_optimizer.py:38-40).               */
+#define ARL_WGRAD_GROUP_MAX 4
+typedef struct arl_wgrad_plan { int64_t opaque[32]; } arl_wgrad_plan;
+/* arl_conv2d_bwd_weight_parts without its launch. */
+int arl_conv2d_bwd_weight_plan(const float* dy, const float* x, float* dw, const arl_conv_geom* geom,
+                               void* workspace, int64_t workspace_bytes, arl_fold_item* item,
+                               float* dbias_or_null, arl_fold_item* bias_item_or_null, arl_wgrad_plan* plan);
+/* arl_conv2d_u8_bwd_weight_parts without its launch. */
+int arl_conv2d_u8_bwd_weight_plan(const float* dy, const uint8_t* obs, int64_t obs_rows,
+                                  const int32_t* idx_or_null, float scale, float* dw,
+                                  const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes,
+                                  arl_fold_item* item, float* dbias_or_null,
+                                  arl_fold_item* bias_item_or_null, arl_wgrad_plan* plan);
+/* arl_conv2d_bwd_pair with the weight gradient of a layer that does not pair left to the group: the data gradient is
+ * launched now (and carries the job, as there); a layer that pairs runs its shared launch now and leaves *plan empty
+ * (the group skips it). */
+int arl_conv2d_bwd_pair_plan(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
+                             float* dx, const float* x, float* dw, const arl_conv_geom* geom, void* workspace,
+                             int64_t workspace_bytes, arl_fold_item* item, float* dbias_or_null,
+                             arl_fold_item* bias_item_or_null, const struct arl_corun_job* job_or_null,
+                             int32_t* job_taken_or_null, arl_wgrad_plan* plan, void* stream);
+int arl_conv2d_bwd_weight_group(const arl_wgrad_plan* plans, int32_t n, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Replay memory of the DQN family
  * ------------------------------------------------------------------------- */
