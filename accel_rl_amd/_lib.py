@@ -216,8 +216,11 @@ _SIGNATURES = {
     "arl_iqn_merge_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "arl_iqn_act": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "arl_iqn_loss": (_i32, [_vp] * 8 + [_i64, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "arl_miqn_loss": (_i32, [_vp] * 8 + [_i64, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp,
+                             _i64, _vp]),
     "arl_dqn_act": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "arl_dqn_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "arl_mdqn_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "arl_lstm_cell_fwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "arl_lstm_cell_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp]),
     "arl_gru_cell_fwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp]),
@@ -1141,6 +1144,21 @@ def iqn_loss(pred, tau_pred, tgt_next, pol_next, actions, returns, terminals, is
                                stream_ptr(stream)), "arl_iqn_loss")
 
 
+def miqn_loss(pred, tau_pred, tgt_next, tgt_cur, actions, returns, terminals, is_weights, n_actions, n, n_target,
+              gamma_n, kappa, tau_e, alpha, l0, dtheta, loss_rows, priorities, state=None, advance=0, stream=None):
+    """Munchausen IQN: tgt_next / tgt_cur are the target net on next_obs / obs; tau_e, alpha, l0 the entropy temperature,
+    the bonus scale and the clip floor.  kappa, state and advance as iqn_loss."""
+    batch = actions.numel()
+    stride = pred.numel() // (batch * n)
+    assert tau_pred.numel() == batch * n and tgt_next.numel() == batch * n_target * stride, "tau_pred / tgt_next size"
+    assert tgt_cur is None or tgt_cur.numel() == tgt_next.numel(), "tgt_cur size"
+    assert dtheta.numel() == pred.numel(), "dtheta size"
+    _check(load().arl_miqn_loss(ptr(pred), ptr(tau_pred), ptr(tgt_next), ptr(tgt_cur), ptr(actions), ptr(returns),
+                                ptr(terminals), ptr(is_weights), batch, n_actions, n, n_target, stride, float(gamma_n),
+                                float(kappa), float(tau_e), float(alpha), float(l0), ptr(dtheta), ptr(loss_rows),
+                                ptr(priorities), ptr(state), advance, stream_ptr(stream)), "arl_miqn_loss")
+
+
 def dqn_act(q, override, n_actions, onehot, greedy=None, dueling=False, stream=None):
     batch = onehot.shape[0]
     _check(load().arl_dqn_act(ptr(q), ptr(override), batch, n_actions, q.numel() // batch, int(dueling),
@@ -1155,6 +1173,16 @@ def dqn_loss(q, tgt_next_q, pol_next_q, actions, returns, terminals, is_weights,
                                ptr(terminals), ptr(is_weights), batch, n_actions, q.numel() // batch, int(dueling),
                                float(gamma_n), 0.0 if delta_clip is None else float(delta_clip), ptr(dq),
                                ptr(loss_rows), ptr(td_abs), stream_ptr(stream)), "arl_dqn_loss")
+
+
+def mdqn_loss(q, tgt_next_q, tgt_cur_q, actions, returns, terminals, is_weights, n_actions, gamma_n, delta_clip, tau_e,
+              alpha, l0, dq, loss_rows, td_abs, dueling=False, stream=None):
+    """Munchausen DQN: tgt_next_q / tgt_cur_q are the target net on next_obs / obs.  delta_clip None: squared loss."""
+    batch = actions.numel()
+    _check(load().arl_mdqn_loss(ptr(q), ptr(tgt_next_q), ptr(tgt_cur_q), ptr(actions), ptr(returns), ptr(terminals),
+                                ptr(is_weights), batch, n_actions, q.numel() // batch, int(dueling), float(gamma_n),
+                                0.0 if delta_clip is None else float(delta_clip), float(tau_e), float(alpha), float(l0),
+                                ptr(dq), ptr(loss_rows), ptr(td_abs), stream_ptr(stream)), "arl_mdqn_loss")
 
 
 # ---------------------------------------------------------------------------

@@ -16,6 +16,10 @@
 //                     (policies/dqn/atari_dqn_policy.py:61-63,118-130)
 //   arl_dqn_loss      one-step / n-step Q-learning target (max or double-DQN selection), squared or
 //                     Huber loss, clipped |TD error| priorities, d loss / d Q (algos/dqn/dqn.py:137-172)
+//   arl_mdqn_loss     Munchausen DQN (Vieillard et al. 2020; not in the reference): arl_dqn_loss with the soft-max
+//                     bootstrap sum_a pi_a (q_a - tau_e log pi_a) of the target net on next_obs and the bonus
+//                     alpha clip(tau_e log pi(action | obs), l0, 0) of the target net on obs added to the reward; max,
+//                     then the exp sum with a ascending from 0, in the lane (formulas: include/accel_rl_hip.h)
 //
 //   arl_qrdqn_act     quantile-regression DQN twin of arl_catdqn_act: Q_a = (sum_i theta(a, i)) / N, greedy action = first
 //                     maximum, override and one-hot row as there (Dabney et al. 2018; not in the reference)
@@ -403,6 +407,86 @@ __global__ __launch_bounds__(256) void dqn_loss_kernel(const DqnLossArgs a) {
     a.td_abs[b] = c > 0.f ? fminf(ad, c) : ad;                             // :165
 }
 
+// ---- Munchausen DQN: dqn_loss_kernel with a soft-max bootstrap and the clipped log-policy bonus; one lane per sample ----
+struct MdqnLossArgs {
+    const float* q;                 // policy net on obs              [B][S]
+    const float* tgt_next_q;        // target net on next_obs         [B][S]
+    const float* tgt_cur_q;         // target net on obs              [B][S]
+    const uint8_t* actions;         // [B]
+    const float* returns;           // [B] one-step reward
+    const uint8_t* terminals;       // [B]
+    const float* is_weights;        // [B] or null
+    float* dq;                      // [B][S]
+    float* loss_rows;               // [B] per-sample (weighted) loss / B
+    float* td_abs;                  // [B] priorities: |TD error| clipped to delta_clip
+    int64_t batch;
+    int n_actions, stride;
+    int dueling;
+    float gamma_n, delta_clip;
+    float tau_e, alpha, l0;         // entropy temperature (> 0), bonus scale (>= 0), clip floor (<= 0)
+};
+
+// v = max_a q_a, s = sum_a expf((q_a - v) / tau_e) (a ascending, from 0) and tl = tau_e logf(s) of one row:
+// tau_e log pi_a = (q_a - v) - tl
+struct SoftRow { float v, s, tl; };
+__device__ __forceinline__ SoftRow soft_row(const float* row, int n, bool dueling, float mean, float tau_e) {
+    SoftRow r;
+    r.v = q_at(row, 0, n, dueling, mean);
+    for (int a = 1; a < n; ++a) r.v = fmaxf(r.v, q_at(row, a, n, dueling, mean));
+    r.s = 0.f;
+    for (int a = 0; a < n; ++a) r.s += expf((q_at(row, a, n, dueling, mean) - r.v) / tau_e);
+    r.tl = tau_e * logf(r.s);
+    return r;
+}
+
+__global__ __launch_bounds__(256) void mdqn_loss_kernel(const MdqnLossArgs a) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.batch) return;
+    const int A = a.n_actions, S = a.stride;
+    const bool duel = a.dueling != 0;
+    const float te = a.tau_e;
+    const float* tgt = a.tgt_next_q + b * S;
+    const float mean_n = duel ? row_mean(tgt, A) : 0.f;
+    const SoftRow sn = soft_row(tgt, A, duel, mean_n, te);
+    float soft = 0.f;                                                      // sum_a pi_a (q_a - tau_e log pi_a)
+    for (int k = 0; k < A; ++k) {
+        const float qk = q_at(tgt, k, A, duel, mean_n);
+        const float ck = qk - sn.v;
+        const float pi = expf(ck / te) / sn.s;
+        soft += pi * (qk - (ck - sn.tl));
+    }
+    const int act = a.actions[b];
+    const float* cur = a.tgt_cur_q + b * S;
+    const float mean_c = duel ? row_mean(cur, A) : 0.f;
+    const SoftRow sc = soft_row(cur, A, duel, mean_c, te);
+    const float lp_act = (q_at(cur, act, A, duel, mean_c) - sc.v) - sc.tl;
+    const float bonus = a.alpha * fminf(fmaxf(lp_act, a.l0), 0.f);         // on terminal rows too
+    const float keep = a.terminals[b] ? 0.f : 1.f;
+    const float y = (a.returns[b] + bonus) + keep * (a.gamma_n * soft);
+    // from here on: dqn_loss_kernel
+    const float* qrow = a.q + b * S;
+    const float d = y - q_at(qrow, act, A, duel, duel ? row_mean(qrow, A) : 0.f);
+    const float ad = fabsf(d), c = a.delta_clip;
+    float loss = 0.5f * (d * d), slope = d;
+    if (c > 0.f && ad > c) {
+        loss = c * (ad - c / 2.f);
+        slope = d > 0.f ? c : -c;
+    }
+    const float w = (a.is_weights ? a.is_weights[b] : 1.f) / (float)a.batch;
+    float* dq = a.dq + b * S;
+    const float gq = -(w * slope);
+    for (int k = 0; k < S; ++k) dq[k] = 0.f;
+    if (!duel) {
+        dq[act] = gq;
+    } else {
+        const float share = gq / (float)A;
+        for (int k = 0; k < A; ++k) dq[k] = k == act ? gq - share : -share;
+        dq[A] = gq;
+    }
+    a.loss_rows[b] = w * loss;
+    a.td_abs[b] = c > 0.f ? fminf(ad, c) : ad;
+}
+
 // ---- quantile-regression DQN: theta f32[batch][n_actions (+ 1)][q_stride], lane i = quantile i (layout and dueling
 // merge as the categorical head's) ----
 // Q_a of every action under `theta`, first maximum; one wave.  Q_a = wave_sum(theta(a, .)) / N (lanes >= N add 0)
@@ -581,6 +665,27 @@ extern "C" int arl_dqn_loss(const float* q, const float* tgt_next_q, const float
     a.delta_clip = delta_clip;
     hipLaunchKernelGGL(dqn_loss_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     return arl::check_launch("dqn_loss_kernel");
+}
+
+extern "C" int arl_mdqn_loss(const float* q, const float* tgt_next_q, const float* tgt_cur_q, const uint8_t* actions,
+                             const float* returns, const uint8_t* terminals, const float* is_weights_or_null,
+                             int64_t batch, int32_t n_actions, int32_t q_stride, int32_t dueling, float gamma_n,
+                             float delta_clip, float tau_e, float alpha, float l0, float* dq, float* loss_rows,
+                             float* td_abs, void* stream) {
+    ARL_REQUIRE(q && tgt_next_q && tgt_cur_q && actions && returns && terminals && dq && loss_rows && td_abs, ARL_E_ARG,
+                "null pointer");
+    int rc = check_q(batch, n_actions, q_stride, dueling);
+    if (rc) return rc;
+    ARL_REQUIRE(tau_e > 0.f && tau_e <= 3.0e38f, ARL_E_ARG, "tau_e must be finite and > 0");
+    ARL_REQUIRE(alpha >= 0.f && alpha <= 3.0e38f, ARL_E_ARG, "alpha must be finite and >= 0");
+    ARL_REQUIRE(l0 <= 0.f && l0 >= -3.0e38f, ARL_E_ARG, "l0 must be finite and <= 0");
+    MdqnLossArgs a = {};
+    a.q = q; a.tgt_next_q = tgt_next_q; a.tgt_cur_q = tgt_cur_q; a.actions = actions; a.returns = returns;
+    a.terminals = terminals; a.is_weights = is_weights_or_null; a.dq = dq; a.loss_rows = loss_rows; a.td_abs = td_abs;
+    a.batch = batch; a.n_actions = n_actions; a.stride = q_stride; a.dueling = dueling != 0; a.gamma_n = gamma_n;
+    a.delta_clip = delta_clip; a.tau_e = tau_e; a.alpha = alpha; a.l0 = l0;
+    hipLaunchKernelGGL(mdqn_loss_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return arl::check_launch("mdqn_loss_kernel");
 }
 
 static int check_cat(int64_t batch, int n_actions, int n_atoms, int stride) {

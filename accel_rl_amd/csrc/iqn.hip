@@ -8,6 +8,9 @@
 //   arl_iqn_act        Q_a = mean over the fractions, first maximum, override, one-hot row; may advance the call counter
 //   arl_iqn_loss       greedy next action, targets T_j, the N x N' quantile-Huber loss and its gradient; one workgroup
 //                      per sample; may advance the call counter
+//   arl_miqn_loss      Munchausen IQN (Vieillard et al. 2020): arl_iqn_loss with the soft-max targets
+//                      T_j = (return + bonus) + keep * (gamma_n * sum_a pi_a (theta_tgt(j, a) - tau_e log pi_a)), pi the
+//                      soft-max of the target net's Q over the actions (max and exp sum: butterflies over the lanes)
 //
 // Plain fp32 C++ (compiled with -ffp-contract=off), wave64, no atomics: every launch is deterministic.
 
@@ -229,6 +232,131 @@ __global__ __launch_bounds__(256) void loss_kernel(const IqnLossArgs a) {
     if (a.state && b == 0 && threadIdx.x == 0) a.state[1] += a.advance;    // the update's three passes have drawn
 }
 
+__device__ __forceinline__ float wave_max(float v) {          // butterfly, as wave_sum
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+    return v;
+}
+
+struct MiqnLossArgs {
+    const float* pred;              // online net on obs                  [B][N][S]
+    const float* tau_pred;          // its fractions                      [B][N]
+    const float* tgt_next;          // target net on next_obs             [B][N'][S]
+    const float* tgt_cur;           // target net on obs                  [B][N'][S]
+    const uint8_t* actions;         // [B]
+    const float* returns;           // [B] one-step reward
+    const uint8_t* terminals;       // [B]
+    const float* is_weights;        // [B] or null
+    float* dtheta;                  // [B][N][S]
+    float* loss_rows;               // [B] per-sample (weighted) loss / B
+    float* priorities;              // [B] clip(unweighted loss, 1e-6, 1e6)
+    int64_t* state;                 // (seed, counter) or null
+    int64_t advance;
+    int64_t batch;
+    int n_actions, n, n_target, stride;
+    float gamma_n, kappa;
+    float tau_e, alpha, l0;         // entropy temperature (> 0), bonus scale (>= 0), clip floor (<= 0)
+};
+
+constexpr int MIQN_TILE_ROW = 64 + 1;       // 64 actions, and odd: the lanes walking their rows meet no bank conflict
+
+// Munchausen IQN: loss_kernel with the targets T_j = (return + bonus) + keep * (gamma_n * soft_j).  One workgroup per sample.
+// Q phase: waves 0 and 2, lane = action, take Q^next and Q^cur (the N' rows read coalesced), wave 1 stages the taken action's
+// predicted quantiles and their fractions, and all 256 threads stage the [N'][A] tile of tgt_next in LDS.  Soft-max phase:
+// waves 0 and 2 take max and exp sum of their row as butterflies; wave 0 keeps pi_a and tau_e log pi_a, wave 2 the bonus.
+// Then wave 0, lane = j, walks its row of the tile (a ascending, from 0) and stages T_j.  The rest is loss_kernel's.
+__global__ __launch_bounds__(256) void mloss_kernel(const MiqnLossArgs a) {
+    __shared__ float s_tile[ARL_IQN_MAX_FRACTIONS * MIQN_TILE_ROW];
+    __shared__ float s_q[64], s_qc[64], s_pi[64], s_lp[64], s_bonus;
+    __shared__ float s_t[64], s_pred[64], s_tau[64], s_d[64], s_g[4][64], s_r[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t b = blockIdx.x;                               // (grid = batch exactly)
+    const int A = a.n_actions, n = a.n, m = a.n_target, S = a.stride;
+    int act = a.actions[b];
+    act = act < A ? act : A - 1;                                // an action the net does not have: never out of bounds
+    const float* nxt = a.tgt_next + b * m * S;
+    if (wave == 0) {
+        s_q[lane] = q_of_lane(nxt, lane, A, m, S);
+    } else if (wave == 1) {
+        s_pred[lane] = lane < n ? a.pred[(b * n + lane) * S + act] : 0.f;
+        s_tau[lane] = lane < n ? a.tau_pred[b * n + lane] : 0.f;
+    } else if (wave == 2) {
+        s_qc[lane] = q_of_lane(a.tgt_cur + b * m * S, lane, A, m, S);
+    }
+    for (int o = threadIdx.x; o < m * A; o += 256) {            // row o / A (a fraction), column o % A (an action)
+        const int j = o / A;
+        s_tile[j * MIQN_TILE_ROW + (o - j * A)] = nxt[(int64_t)j * S + (o - j * A)];
+    }
+    __syncthreads();
+    if (wave == 0 || wave == 2) {
+        const float q = wave == 0 ? s_q[lane] : s_qc[lane];
+        const float v = wave_max(lane < A ? q : -INFINITY);
+        const float c = q - v;
+        const float e = lane < A ? expf(c / a.tau_e) : 0.f;
+        const float s = wave_sum(e);
+        const float lp = c - a.tau_e * logf(s);                 // tau_e log pi_a
+        if (wave == 0) {
+            s_pi[lane] = e / s;
+            s_lp[lane] = lp;
+        } else if (lane == act) {
+            s_bonus = a.alpha * fminf(fmaxf(lp, a.l0), 0.f);    // on terminal rows too
+        }
+    }
+    __syncthreads();
+    if (wave == 0) {
+        float soft = 0.f;                                       // sum_a pi_a (theta(j, a) - tau_e log pi_a)
+        if (lane < m)
+            for (int k = 0; k < A; ++k) soft += s_pi[k] * (s_tile[lane * MIQN_TILE_ROW + k] - s_lp[k]);
+        const float keep = a.terminals[b] ? 0.f : 1.f;
+        s_t[lane] = lane < m ? (a.returns[b] + s_bonus) + keep * (a.gamma_n * soft) : 0.f;
+    }
+    __syncthreads();
+    // from here on: loss_kernel
+    const float kappa = a.kappa;
+    float g = 0.f, r = 0.f;
+    if (lane < n) {
+        const float th = s_pred[lane], tau = s_tau[lane];
+        for (int j = wave; j < m; j += 4) {
+            const float u = s_t[j] - th;
+            const float ind = u < 0.f ? 1.f : 0.f;
+            const float wt = fabsf(tau - ind);
+            float gt, rt;
+            if (kappa > 0.f) {
+                const float au = fabsf(u);
+                const float l = au <= kappa ? 0.5f * (u * u) : kappa * (au - 0.5f * kappa);
+                rt = wt * l / kappa;
+                gt = wt * fminf(fmaxf(u, -kappa), kappa) / kappa;
+            } else {
+                rt = wt * fabsf(u);
+                gt = tau - ind;
+            }
+            g += gt;
+            r += rt;
+        }
+    }
+    s_g[wave][lane] = g;
+    s_r[wave][lane] = r;
+    __syncthreads();
+    const float wgt = (a.is_weights ? a.is_weights[b] : 1.f) / (float)a.batch;
+    if (wave == 0) {
+        const float gs = ((s_g[0][lane] + s_g[1][lane]) + s_g[2][lane]) + s_g[3][lane];
+        const float rs = ((s_r[0][lane] + s_r[1][lane]) + s_r[2][lane]) + s_r[3][lane];
+        s_d[lane] = lane < n ? -(wgt / (float)m * gs) : 0.f;
+        const float loss_b = wave_sum(lane < n ? rs : 0.f) / (float)m;
+        if (lane == 0) {
+            a.loss_rows[b] = wgt * loss_b;
+            a.priorities[b] = fminf(fmaxf(loss_b, 1e-6f), 1e6f);
+        }
+    }
+    __syncthreads();
+    float* dl = a.dtheta + b * n * S;
+    for (int o = threadIdx.x; o < n * S; o += 256) {
+        const int i = o / S;
+        dl[o] = o - i * S == act ? s_d[i] : 0.f;
+    }
+    if (a.state && b == 0 && threadIdx.x == 0) a.state[1] += a.advance;
+}
+
 inline unsigned grid_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 bool theta_sizes_ok(int64_t batch, int n_actions, int fractions, int stride) {
@@ -313,4 +441,28 @@ extern "C" int arl_iqn_loss(const float* pred, const float* tau_pred, const floa
     a.n_actions = n_actions; a.n = n; a.n_target = n_target; a.stride = a_stride; a.gamma_n = gamma_n; a.kappa = kappa;
     hipLaunchKernelGGL(loss_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, a);
     return arl::check_launch("iqn loss_kernel");
+}
+
+extern "C" int arl_miqn_loss(const float* pred, const float* tau_pred, const float* tgt_next, const float* tgt_cur,
+                             const uint8_t* actions, const float* returns, const uint8_t* terminals,
+                             const float* is_weights_or_null, int64_t batch, int32_t n_actions, int32_t n,
+                             int32_t n_target, int32_t a_stride, float gamma_n, float kappa, float tau_e, float alpha,
+                             float l0, float* dtheta, float* loss_rows, float* priorities, int64_t* state_or_null,
+                             int64_t advance, void* stream) {
+    ARL_REQUIRE(pred && tau_pred && tgt_next && tgt_cur && actions && returns && terminals && dtheta && loss_rows &&
+                priorities, ARL_E_ARG, "null pointer");
+    ARL_REQUIRE(theta_sizes_ok(batch, n_actions, n, a_stride) && theta_sizes_ok(batch, n_actions, n_target, a_stride),
+                ARL_E_ARG, THETA_SIZES);
+    ARL_REQUIRE(kappa >= 0.f && kappa <= 3.0e38f, ARL_E_ARG, "kappa must be finite and >= 0");
+    ARL_REQUIRE(tau_e > 0.f && tau_e <= 3.0e38f, ARL_E_ARG, "tau_e must be finite and > 0");
+    ARL_REQUIRE(alpha >= 0.f && alpha <= 3.0e38f, ARL_E_ARG, "alpha must be finite and >= 0");
+    ARL_REQUIRE(l0 <= 0.f && l0 >= -3.0e38f, ARL_E_ARG, "l0 must be finite and <= 0");
+    MiqnLossArgs a = {};
+    a.pred = pred; a.tau_pred = tau_pred; a.tgt_next = tgt_next; a.tgt_cur = tgt_cur; a.actions = actions;
+    a.returns = returns; a.terminals = terminals; a.is_weights = is_weights_or_null; a.dtheta = dtheta;
+    a.loss_rows = loss_rows; a.priorities = priorities; a.state = state_or_null; a.advance = advance; a.batch = batch;
+    a.n_actions = n_actions; a.n = n; a.n_target = n_target; a.stride = a_stride; a.gamma_n = gamma_n; a.kappa = kappa;
+    a.tau_e = tau_e; a.alpha = alpha; a.l0 = l0;
+    hipLaunchKernelGGL(mloss_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, a);
+    return arl::check_launch("iqn mloss_kernel");
 }

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from accel_rl_amd import _lib
-from accel_rl_amd.policies.atari_cnn_policy import _norm_c
+from accel_rl_amd.policies.atari_cnn_policy import ObsRows, _norm_c
 from accel_rl_amd.policies.dqn.q_policy_base import QPolicyBase
 
 
@@ -111,6 +111,36 @@ class AtariDqnPolicy(QPolicyBase):
             loss_rows, td_abs = pack[0], pack[1]
             _lib.dqn_loss(q, tgt_q, pol_next, actions, returns, terminals, is_weights, self.n_act, gamma_n,
                           delta_clip, dq, loss_rows, td_abs, dueling=self._dueling)
+            self._head_backward(dq, x, acts, hids)
+            if self._shared_last_bias:          # the folds have run: d loss / d (shared scalar) = the sum over the actions
+                gb = self.grads[self._k_head + 1]
+                gb[:self.n_act] = gb[:self.n_act].sum()
+            return loss_rows, td_abs
+
+    def munchausen_loss_and_grads(self, obs, next_obs, actions, returns, terminals, is_weights, gamma_n, delta_clip,
+                                  tau_e, alpha, l0):
+        """One minibatch of MunchausenDQN.build_loss: forward of the policy net on obs, of the target net on next_obs
+        AND on obs (u8 observations: one target pass over the 2B rows of _pair_rows, sliced; else two passes), the
+        Munchausen (Huber) TD loss of csrc/dqn.hip:arl_mdqn_loss and the full backward pass into flat_grads.  Returns
+        (loss_rows f32[B] whose sum is the loss, td_abs f32[B]), the two rows of one (2, B) buffer as q_loss_and_grads'.
+        No host synchronisation and no allocation outside _buffer: it runs inside the captured update graph."""
+        with torch.no_grad():
+            b = obs.shape[0]
+            if self._u8:
+                both = self._pair_rows(obs, next_obs)
+                tgt2 = self._logits(ObsRows(both, None), w=self._w_target, tag="t2")[0]
+                tgt_cur, tgt_next = tgt2[:b], tgt2[b:]
+                x = ObsRows(both[:b], None)
+            else:
+                tgt_next = self._logits(self._scaled(next_obs, tag="n"), w=self._w_target, tag="t")[0]
+                x = self._scaled(obs)
+                tgt_cur = self._logits(x, w=self._w_target, tag="tc")[0]
+            q, acts, hids = self._logits(x)
+            dq = self._buffer(("dlogits", b), tuple(q.shape))
+            pack = self._buffer(("loss_td", b), (2, b))         # one buffer: DqnOptimizer's statistics ring takes both rows at once
+            loss_rows, td_abs = pack[0], pack[1]
+            _lib.mdqn_loss(q, tgt_next, tgt_cur, actions, returns, terminals, is_weights, self.n_act, gamma_n,
+                           delta_clip, tau_e, alpha, l0, dq, loss_rows, td_abs, dueling=self._dueling)
             self._head_backward(dq, x, acts, hids)
             if self._shared_last_bias:          # the folds have run: d loss / d (shared scalar) = the sum over the actions
                 gb = self.grads[self._k_head + 1]

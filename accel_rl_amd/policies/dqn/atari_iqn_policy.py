@@ -250,6 +250,41 @@ class AtariIqnPolicy(QPolicyBase):
             self._pair_backward(x, acts, psi, cosf, phi, merged, hids, dtheta, b, n)
             return loss_rows, priorities
 
+    def munchausen_loss_and_grads(self, obs, next_obs, actions, returns, terminals, is_weights, gamma_n, kappa, tau_e,
+                                  alpha, l0, taus=None):
+        """One minibatch of MunchausenIQN.build_loss: the online net on obs at N fractions (call offset 0), the target net
+        on next_obs (offset 1) and on obs (offset 2) at N' fractions each -- the target conv stack runs once over the 2B
+        rows of _pair_rows where the observations are u8 --, the Munchausen quantile-Huber loss of
+        csrc/iqn.hip:arl_miqn_loss and the full backward pass into flat_grads.  taus = (tau_pred f32[B N], tau_next
+        f32[B N'], tau_cur f32[B N']): given fractions, and the call counter stays as it is.  Returns (loss_rows, priorities)
+        as iqn_loss_and_grads.  No host synchronisation and no allocation outside _buffer."""
+        with torch.no_grad():
+            b, f = obs.shape[0], self._f
+            n, m = self.n_quantiles, self.n_target_quantiles
+            t_pred, t_next, t_cur = taus if taus is not None else (None, None, None)
+            if self._u8:
+                both = self._pair_rows(obs, next_obs)
+                psi_t2 = self._convs(ObsRows(both, None), w=self._w_target, tag="t2")[-1].view(2 * b, f)
+                psi_tc, psi_tn = psi_t2[:b], psi_t2[b:]
+                x = ObsRows(both[:b], None)
+            else:
+                psi_tn = self._convs(self._scaled(next_obs, tag="n"), w=self._w_target, tag="t")[-1].view(b, f)
+                x = self._scaled(obs)
+                psi_tc = self._convs(x, w=self._w_target, tag="tc")[-1].view(b, f)
+            acts = self._convs(x)
+            psi = acts[-1].view(b, f)
+            tau, cosf, phi, merged, hids, theta = self._quantile_pass(psi, n, tau_in=t_pred, call_offset=0)
+            tgt_next = self._quantile_pass(psi_tn, m, w=self._w_target, tag="t", tau_in=t_next, call_offset=1)[-1]
+            tgt_cur = self._quantile_pass(psi_tc, m, w=self._w_target, tag="tc", tau_in=t_cur, call_offset=2)[-1]
+            dtheta = self._buffer(("dtheta", b), (b * n, self._a_stride))
+            pack = self._buffer(("loss_pri", b), (2, b))        # one buffer: DqnOptimizer's statistics ring takes both rows at once
+            loss_rows, priorities = pack[0], pack[1]
+            _lib.miqn_loss(theta, tau, tgt_next, tgt_cur, actions, returns, terminals, is_weights, self.n_act, n, m,
+                           gamma_n, kappa, tau_e, alpha, l0, dtheta, loss_rows, priorities,
+                           state=None if taus is not None else self._iqn_state, advance=3)
+            self._pair_backward(x, acts, psi, cosf, phi, merged, hids, dtheta, b, n)
+            return loss_rows, priorities
+
     def _pair_backward(self, x, acts, psi, cosf, phi, merged, hids, dtheta, b, r):
         """Backward of one online pass at b r rows: output layer, hidden layers, the merge, the embedding layer's weight
         gradient, then the conv stack at b rows."""

@@ -223,6 +223,9 @@ class AtariNoisyNetDqnPolicy(AtariDqnPolicy):
     def set_epsilon(self, value):
         pass
 
+    def munchausen_loss_and_grads(self, *args, **kwargs):
+        raise NotImplementedError("a noisy Munchausen agent is not built (INTEGRATION.md, section E)")
+
     # ---- training: the noisy layers' backward, then the conv stack's ----------------
     def _head_backward(self, dout, x, acts, hids):
         b = x.shape[0]

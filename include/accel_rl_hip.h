@@ -908,6 +908,31 @@ int arl_iqn_loss(const float* pred, const float* tau_pred, const float* tgt_next
                  int32_t a_stride, float gamma_n, float kappa, float* dtheta, float* loss_rows, float* priorities,
                  int64_t* state_or_null, int64_t advance, void* stream);
 
+/* Munchausen IQN (Vieillard, Pietquin, Geist 2020, "Munchausen Reinforcement Learning"): arl_iqn_loss with a soft-max
+ * bootstrap and the scaled, clipped log-policy bonus added to the reward.  tgt_next, tgt_cur f32[batch][N'][a_stride]:
+ * the TARGET net on next_obs and on obs.  tau_e > 0 the entropy temperature, alpha >= 0 the bonus scale, l0 <= 0 the
+ * clip floor (the paper: 0.03, 0.9, -1).  For a row Q[0 .. A) of action values, in fp32 with expf / logf of the device
+ * library:
+ *   v = max_a Q_a;  c_a = Q_a - v;  e_a = expf(c_a / tau_e);  s = sum_a e_a
+ *   lp_a = c_a - tau_e * logf(s)      (= tau_e log pi_a: finite even where pi_a underflows to 0);   pi_a = e_a / s
+ * Per sample b:
+ *   Q^next_a = (sum_j tgt_next(j, a)) / N', j ascending, the sum starts at 0 (as arl_iqn_act); Q^cur likewise of tgt_cur
+ *   m_b    = alpha * clip(lp^cur_{actions_b}, l0, 0)                               (on terminal rows too)
+ *   soft_j = sum_a pi^next_a * (tgt_next(j, a) - lp^next_a)                        a ascending, the sum starts at 0
+ *   T_j    = (returns_b + m_b) + keep * (gamma_n * soft_j)                         (in this order)
+ * and from T_j on everything is arl_iqn_loss: u_ij, rho_ij, dtheta, loss_rows, priorities, their summation orders, the
+ * actions_b >= n_actions rule, state_or_null / advance.  No action is selected by an argmax; there is no double-DQN form.
+ * Summation order of the soft-max: lane = action; v and s are butterflies over the 64 lanes (lane ^ 32, ^ 16, ... ^ 1;
+ * lanes >= A add 0 to s and take no part in the maximum).  One 256-thread workgroup per sample; the [N'][A] tile of
+ * tgt_next is staged in LDS.  With alpha == 0 and a maximum of Q^next unique by a gap of at least 88 tau_e (so that every
+ * other e_a is 0): s == 1, soft_j == tgt_next(j, a*), and the outputs equal arl_iqn_loss's (pol_next NULL) bit for bit.
+ * Refusals as arl_iqn_loss's, and ARL_E_ARG for tau_e not finite or <= 0, alpha not finite or < 0, l0 not finite or > 0. */
+int arl_miqn_loss(const float* pred, const float* tau_pred, const float* tgt_next, const float* tgt_cur,
+                  const uint8_t* actions, const float* returns, const uint8_t* terminals,
+                  const float* is_weights_or_null, int64_t batch, int32_t n_actions, int32_t n, int32_t n_target,
+                  int32_t a_stride, float gamma_n, float kappa, float tau_e, float alpha, float l0, float* dtheta,
+                  float* loss_rows, float* priorities, int64_t* state_or_null, int64_t advance, void* stream);
+
 /* Plain DQN action serving: greedy action = first maximum of the Q row (T.argmax), override as
  * above, one-hot row out.  Replaces AtariDqnPolicy.get_actions / actions_sym,
  * accel_rl/policies/dqn/atari_dqn_policy.py:61-63,76-79,118-130.
@@ -929,6 +954,25 @@ int arl_dqn_loss(const float* q, const float* tgt_next_q, const float* pol_next_
                  const float* is_weights_or_null, int64_t batch, int32_t n_actions, int32_t q_stride,
                  int32_t dueling, float gamma_n, float delta_clip, float* dq, float* loss_rows, float* td_abs,
                  void* stream);
+
+/* Munchausen DQN (Vieillard, Pietquin, Geist 2020): arl_dqn_loss with a soft-max bootstrap and the scaled, clipped
+ * log-policy bonus added to the reward.  tgt_next_q, tgt_cur_q f32[batch][q_stride]: the TARGET net on next_obs and on
+ * obs (dueling rows merged as in arl_dqn_act).  With v, c_a, e_a, s, lp_a, pi_a of a row as defined at arl_miqn_loss
+ * (tau_e > 0, alpha >= 0, l0 <= 0; expf / logf of the device library, fp32):
+ *   m_b    = alpha * clip(lp^cur_{actions_b}, l0, 0)                               (on terminal rows too)
+ *   soft_b = sum_a pi^next_a * (q^next_a - lp^next_a)                              a ascending, the sum starts at 0
+ *   y_b    = (returns_b + m_b) + keep * (gamma_n * soft_b)                         (in this order)
+ *   d_b    = y_b - q(obs)[actions_b]
+ * and from d_b on everything is arl_dqn_loss: squared or Huber loss, importance weights, dq (through the dueling merge),
+ * loss_rows, td_abs.  No action is selected by an argmax; there is no double-DQN form.  One lane per sample: the
+ * maximum, then s with a ascending from 0, then soft_b, all inside the lane.  With alpha == 0 and a maximum of q^next
+ * unique by a gap of at least 88 tau_e: s == 1, soft_b == max_a q^next_a, and the outputs equal arl_dqn_loss's
+ * (pol_next_q NULL) bit for bit.  Sizes as arl_dqn_loss (ARL_E_RANGE); a NULL mandatory pointer, tau_e not finite or
+ * <= 0, alpha not finite or < 0, l0 not finite or > 0: ARL_E_ARG.  A refused call launches nothing.                  */
+int arl_mdqn_loss(const float* q, const float* tgt_next_q, const float* tgt_cur_q, const uint8_t* actions,
+                  const float* returns, const uint8_t* terminals, const float* is_weights_or_null, int64_t batch,
+                  int32_t n_actions, int32_t q_stride, int32_t dueling, float gamma_n, float delta_clip, float tau_e,
+                  float alpha, float l0, float* dq, float* loss_rows, float* td_abs, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * LSTM cell of the recurrent policies
