@@ -2,7 +2,6 @@
 epsilon = 0.01 / batch_size, epsilon-greedy 1 -> 0.01 (eval 0.001), support linspace(V_min, V_max,
 n_atoms).  The loss graph of the reference is csrc/dqn.hip:arl_catdqn_loss."""
 import numpy as np
-import torch
 
 from accel_rl_amd.algos.dqn.dqn import DQN
 from accel_rl_amd.optimizers import update_methods
@@ -25,25 +24,14 @@ class CategoricalDQN(DQN):
         return opt_args, eps_greedy_args, priority_args
 
     def build_loss(self, env_spec, policy):
-        assert bool(self.dueling_dqn) == bool(getattr(policy, "_dueling", False)), \
-            "dueling_dqn and the policy's `dueling` must agree (the reference's scripts pass both)"
+        self._check_dueling(policy)
         z = np.linspace(self.V_min, self.V_max, policy.n_atoms, dtype=np.float32)      # cat_dqn.py:49-52
         policy.incorporate_z(z)
         gamma_n = float(np.float32(self.discount ** self.reward_horizon))
-        inputs = ["obs", "next_obs", "act", "disc_n_return", "terminal"]
-        if self.prioritized_replay:
-            inputs.append("importance_sample_weights")
 
         def loss(minibatch):
-            obs, next_obs, act, ret, term = minibatch[:5]
-            isw = None
-            if self.prioritized_replay:
-                isw = minibatch[5]
-                if not isinstance(isw, torch.Tensor):
-                    isw = torch.as_tensor(np.asarray(isw, np.float32)).to(policy.device)
-            term_u8 = term.view(torch.uint8) if term.dtype == torch.bool else term
-            loss_rows, kl = policy.cat_loss_and_grads(obs, next_obs, act, ret, term_u8, isw, self.V_min, self.V_max,
-                                                      gamma_n, double_dqn=self.double_dqn)
+            loss_rows, kl = policy.cat_loss_and_grads(*self._unpack(minibatch, policy), self.V_min, self.V_max, gamma_n,
+                                                      double_dqn=self.double_dqn)
             return kl, loss_rows                    # (the loss is their sum: DqnOptimizer)
 
-        return inputs, loss
+        return self._loss_inputs(), loss

@@ -71,28 +71,41 @@ class DQN(RLAlgorithm):
             self.replay_buffer = UniformReplayBuffer(**replay_args)
         self.replay_buffer.reuse_outputs = True       # minibatches are consumed before the next one is drawn
 
-    def build_loss(self, env_spec, policy):
-        """dqn.py:137-172"""
+    # ---- what every build_loss of the family shares ----
+    def _check_dueling(self, policy):
         assert bool(self.dueling_dqn) == bool(getattr(policy, "_dueling", False)), \
             "dueling_dqn and the policy's `dueling` must agree (the reference's scripts pass both)"
-        gamma_n = float(np.float32(self.discount ** self.reward_horizon))
+
+    def _loss_inputs(self):
+        """Names of a minibatch's entries, in the order _unpack reads them."""
         inputs = ["obs", "next_obs", "act", "disc_n_return", "terminal"]
         if self.prioritized_replay:
             inputs.append("importance_sample_weights")
+        return inputs
+
+    def _unpack(self, minibatch, policy):
+        """(obs, next_obs, act, ret, term_u8, isw) as the policies' *_loss_and_grads take them: bool terminals viewed as
+        u8, importance weights (None when replay is uniform) as a float32 tensor on the policy's device."""
+        obs, next_obs, act, ret, term = minibatch[:5]
+        isw = None
+        if self.prioritized_replay:
+            isw = minibatch[5]
+            if not isinstance(isw, torch.Tensor):
+                isw = torch.as_tensor(np.asarray(isw, np.float32)).to(policy.device)
+        term_u8 = term.view(torch.uint8) if term.dtype == torch.bool else term
+        return obs, next_obs, act, ret, term_u8, isw
+
+    def build_loss(self, env_spec, policy):
+        """dqn.py:137-172"""
+        self._check_dueling(policy)
+        gamma_n = float(np.float32(self.discount ** self.reward_horizon))
 
         def loss(minibatch):
-            obs, next_obs, act, ret, term = minibatch[:5]
-            isw = None
-            if self.prioritized_replay:
-                isw = minibatch[5]
-                if not isinstance(isw, torch.Tensor):
-                    isw = torch.as_tensor(np.asarray(isw, np.float32)).to(policy.device)
-            term_u8 = term.view(torch.uint8) if term.dtype == torch.bool else term
-            loss_rows, td_abs = policy.q_loss_and_grads(obs, next_obs, act, ret, term_u8, isw, gamma_n,
-                                                        self.delta_clip, double_dqn=self.double_dqn)
+            loss_rows, td_abs = policy.q_loss_and_grads(*self._unpack(minibatch, policy), gamma_n, self.delta_clip,
+                                                        double_dqn=self.double_dqn)
             return td_abs, loss_rows                # (the loss is their sum: DqnOptimizer)
 
-        return inputs, loss
+        return self._loss_inputs(), loss
 
     def optimize_policy(self, itr, samples_data):
         """dqn.py:174-193"""

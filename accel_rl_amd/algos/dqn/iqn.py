@@ -3,7 +3,6 @@ prioritized replay and schedules with the pairwise quantile-Huber loss taken at 
 sample (csrc/iqn.hip:arl_iqn_loss).  Defaults and the kappa check are QuantileDQN's; priorities are the clipped
 per-sample loss.  The numbers of fractions (N, N', K) belong to the policy: AtariIqnPolicy."""
 import numpy as np
-import torch
 
 from accel_rl_amd.algos.dqn.qr_dqn import QuantileDQN
 from accel_rl_amd.policies.dqn.atari_iqn_policy import AtariIqnPolicy
@@ -20,20 +19,10 @@ class ImplicitQuantileDQN(QuantileDQN):
         if not isinstance(policy, AtariIqnPolicy):
             raise TypeError("ImplicitQuantileDQN trains an AtariIqnPolicy (got %s)" % type(policy).__name__)
         gamma_n = float(np.float32(self.discount ** self.reward_horizon))
-        inputs = ["obs", "next_obs", "act", "disc_n_return", "terminal"]
-        if self.prioritized_replay:
-            inputs.append("importance_sample_weights")
 
         def loss(minibatch):
-            obs, next_obs, act, ret, term = minibatch[:5]
-            isw = None
-            if self.prioritized_replay:
-                isw = minibatch[5]
-                if not isinstance(isw, torch.Tensor):
-                    isw = torch.as_tensor(np.asarray(isw, np.float32)).to(policy.device)
-            term_u8 = term.view(torch.uint8) if term.dtype == torch.bool else term
-            loss_rows, priorities = policy.iqn_loss_and_grads(obs, next_obs, act, ret, term_u8, isw, gamma_n, self.kappa,
+            loss_rows, priorities = policy.iqn_loss_and_grads(*self._unpack(minibatch, policy), gamma_n, self.kappa,
                                                               double_dqn=self.double_dqn)
             return priorities, loss_rows            # (the loss is their sum: DqnOptimizer)
 
-        return inputs, loss
+        return self._loss_inputs(), loss

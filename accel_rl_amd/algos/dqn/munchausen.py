@@ -7,7 +7,6 @@ epsilon = 0.01 / batch_size, epsilon-greedy 1 -> 0.01 (eval 0.001); entropy_tau 
 munchausen_clip = -1.  Nothing is selected by an argmax, so there is no double-DQN form; the bonus of the intermediate
 steps of an n-step return is not in the replay's disc_n_return, so reward_horizon must be 1."""
 import numpy as np
-import torch
 
 from accel_rl_amd.algos.dqn.dqn import DQN
 from accel_rl_amd.algos.dqn.iqn import ImplicitQuantileDQN
@@ -32,17 +31,6 @@ def _check_munchausen_args(entropy_tau, munchausen_alpha, munchausen_clip, kwarg
                                   "in the replay's disc_n_return (INTEGRATION.md, section E)")
 
 
-def _minibatch_args(algo, policy, minibatch):
-    obs, next_obs, act, ret, term = minibatch[:5]
-    isw = None
-    if algo.prioritized_replay:
-        isw = minibatch[5]
-        if not isinstance(isw, torch.Tensor):
-            isw = torch.as_tensor(np.asarray(isw, np.float32)).to(policy.device)
-    term_u8 = term.view(torch.uint8) if term.dtype == torch.bool else term
-    return obs, next_obs, act, ret, term_u8, isw
-
-
 class MunchausenDQN(DQN):
 
     def __init__(self, entropy_tau=0.03, munchausen_alpha=0.9, munchausen_clip=-1.0, **kwargs):
@@ -56,16 +44,16 @@ class MunchausenDQN(DQN):
         if type(policy) is not AtariDqnPolicy:
             raise TypeError("MunchausenDQN trains an AtariDqnPolicy itself, not a subclass (got %s)" %
                             type(policy).__name__)
-        inputs, _ = super().build_loss(env_spec, policy)        # (the dueling agreement is checked there)
+        self._check_dueling(policy)
         gamma_n = float(np.float32(self.discount))
 
         def loss(minibatch):
             loss_rows, td_abs = policy.munchausen_loss_and_grads(
-                *_minibatch_args(self, policy, minibatch), gamma_n, self.delta_clip, self.entropy_tau,
+                *self._unpack(minibatch, policy), gamma_n, self.delta_clip, self.entropy_tau,
                 self.munchausen_alpha, self.munchausen_clip)
             return td_abs, loss_rows                # (the loss is their sum: DqnOptimizer)
 
-        return inputs, loss
+        return self._loss_inputs(), loss
 
 
 class MunchausenIQN(ImplicitQuantileDQN):
@@ -78,13 +66,12 @@ class MunchausenIQN(ImplicitQuantileDQN):
     def build_loss(self, env_spec, policy):
         if not isinstance(policy, AtariIqnPolicy):
             raise TypeError("MunchausenIQN trains an AtariIqnPolicy (got %s)" % type(policy).__name__)
-        inputs, _ = super().build_loss(env_spec, policy)
         gamma_n = float(np.float32(self.discount))
 
         def loss(minibatch):
             loss_rows, priorities = policy.munchausen_loss_and_grads(
-                *_minibatch_args(self, policy, minibatch), gamma_n, self.kappa, self.entropy_tau,
+                *self._unpack(minibatch, policy), gamma_n, self.kappa, self.entropy_tau,
                 self.munchausen_alpha, self.munchausen_clip)
             return priorities, loss_rows            # (the loss is their sum: DqnOptimizer)
 
-        return inputs, loss
+        return self._loss_inputs(), loss

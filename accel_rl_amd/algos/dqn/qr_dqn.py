@@ -3,7 +3,6 @@ prioritized replay and schedules with the pairwise quantile-Huber loss of csrc/d
 are the paper's: adam, learning rate 5e-5, epsilon = 0.01 / batch_size, epsilon-greedy 1 -> 0.01 (eval 0.001),
 kappa = 1 (kappa = 0: plain quantile regression).  Priorities are the clipped per-sample loss."""
 import numpy as np
-import torch
 
 from accel_rl_amd.algos.dqn.dqn import DQN
 from accel_rl_amd.optimizers import update_methods
@@ -28,23 +27,12 @@ class QuantileDQN(DQN):
         return opt_args, eps_greedy_args, priority_args
 
     def build_loss(self, env_spec, policy):
-        assert bool(self.dueling_dqn) == bool(getattr(policy, "_dueling", False)), \
-            "dueling_dqn and the policy's `dueling` must agree"
+        self._check_dueling(policy)
         gamma_n = float(np.float32(self.discount ** self.reward_horizon))
-        inputs = ["obs", "next_obs", "act", "disc_n_return", "terminal"]
-        if self.prioritized_replay:
-            inputs.append("importance_sample_weights")
 
         def loss(minibatch):
-            obs, next_obs, act, ret, term = minibatch[:5]
-            isw = None
-            if self.prioritized_replay:
-                isw = minibatch[5]
-                if not isinstance(isw, torch.Tensor):
-                    isw = torch.as_tensor(np.asarray(isw, np.float32)).to(policy.device)
-            term_u8 = term.view(torch.uint8) if term.dtype == torch.bool else term
-            loss_rows, priorities = policy.qr_loss_and_grads(obs, next_obs, act, ret, term_u8, isw, gamma_n, self.kappa,
+            loss_rows, priorities = policy.qr_loss_and_grads(*self._unpack(minibatch, policy), gamma_n, self.kappa,
                                                              double_dqn=self.double_dqn)
             return priorities, loss_rows            # (the loss is their sum: DqnOptimizer)
 
-        return inputs, loss
+        return self._loss_inputs(), loss

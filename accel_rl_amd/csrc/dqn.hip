@@ -34,9 +34,11 @@
 // multiple of 4 (the dense layer producing them is an MFMA kernel with 16-byte rows); the padding
 // columns are ignored on input and receive zero gradient.  Lane i owns atom i; one wave per sample (action
 // kernel) / one workgroup per sample (loss kernel); n_atoms <= 64.  fp32, compiled with -ffp-contract=off.
+// The butterflies, first_max, the quantile-Huber term, the four-way combine and the serve tail are csrc/q_loss_dev.h's.
 
 #include "arl_common.h"
 #include "dgrad_wt_dev.h"
+#include "q_loss_dev.h"
 #include <type_traits>
 
 namespace arlc {
@@ -45,16 +47,7 @@ int fold_wide_from();           // mfma_conv.hip: the split count from which a f
 
 namespace {
 
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x = fmaxf(x, __shfl_xor(x, off, 64));
-    return x;
-}
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
-}
+using namespace arlq;
 
 // softmax over the atoms of one action; lane i holds logit x (lanes >= n_atoms: anything) and returns p_i (0 there)
 __device__ __forceinline__ float atom_softmax(float x, int lane, int n_atoms) {
@@ -180,10 +173,7 @@ __global__ __launch_bounds__(256) void catdqn_act_kernel(const float* __restrict
     const float z_lane = lane < n_atoms ? z[lane] : 0.f;
     const int g = greedy_action(logits + b * (n_actions + dueling) * stride, lane, n_actions, n_atoms, stride, z_lane,
                                 dueling != 0);
-    int act = g;
-    if (override_or_null && override_or_null[b] >= 0) act = override_or_null[b];
-    if (lane < n_actions) onehot[b * n_actions + lane] = lane == act ? 1.f : 0.f;
-    if (lane == 0 && greedy) greedy[b] = (uint8_t)g;
+    serve_wave(g, b, lane, n_actions, override_or_null, onehot, greedy);
 }
 
 struct LogitSrc { const float* p; const float* bias; long long ss; int splits; };     // splits == 0: finished logits
@@ -267,12 +257,7 @@ __global__ __launch_bounds__(256) void catdqn_loss_kernel(const CatLossArgs a, c
     if (wave == 0) pred_x = atom_logit(prd, act, lane, n, S, duel_terms(prd, lane, A, n, S, duel));
     __syncthreads();
     if (wave != 0) return;
-    int a_next = 0;
-    float best_q = s_q[0];
-    for (int k = 1; k < A; ++k) {
-        const float q = s_q[k];
-        if (q > best_q) { best_q = q; a_next = k; }
-    }
+    const int a_next = first_max(s_q, A);
     const float next_p = atom_softmax(atom_logit(tgt, a_next, lane, n, S, duel_terms(tgt, lane, A, n, S, duel)), lane, n);
     // shifted support, clipped to [v_min, v_max] (:56-62)
     const float keep = a.terminals[b] ? 0.f : 1.f;
@@ -372,18 +357,11 @@ struct DqnLossArgs {
     float gamma_n, delta_clip;      // delta_clip <= 0: squared loss, unclipped priorities
 };
 
-__global__ __launch_bounds__(256) void dqn_loss_kernel(const DqnLossArgs a) {
-    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= a.batch) return;
+// Second half of dqn_loss_kernel and mdqn_loss_kernel: from sample b's target y and taken action to the (Huber) loss, its
+// gradient through the dueling merge, and the priority
+__device__ __forceinline__ void dqn_loss_tail(const DqnLossArgs& a, int64_t b, float y, int act) {
     const int A = a.n_actions, S = a.stride;
-    const float* tgt = a.tgt_next_q + b * S;
-    // dqn.py:146-150: double DQN picks the action with the policy net and values it with the target net
     const bool duel = a.dueling != 0;
-    const int a_next = first_argmax(a.pol_next_q ? a.pol_next_q + b * S : tgt, A, duel);
-    const float next_q = q_at(tgt, a_next, A, duel, duel ? row_mean(tgt, A) : 0.f);
-    const float keep = a.terminals[b] ? 0.f : 1.f;
-    const float y = a.returns[b] + keep * (a.gamma_n * next_q);            // :152-153
-    const int act = a.actions[b];
     const float* qrow = a.q + b * S;
     const float d = y - q_at(qrow, act, A, duel, duel ? row_mean(qrow, A) : 0.f);
     const float ad = fabsf(d), c = a.delta_clip;
@@ -407,22 +385,23 @@ __global__ __launch_bounds__(256) void dqn_loss_kernel(const DqnLossArgs a) {
     a.td_abs[b] = c > 0.f ? fminf(ad, c) : ad;                             // :165
 }
 
+__global__ __launch_bounds__(256) void dqn_loss_kernel(const DqnLossArgs a) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.batch) return;
+    const int A = a.n_actions, S = a.stride;
+    const float* tgt = a.tgt_next_q + b * S;
+    // dqn.py:146-150: double DQN picks the action with the policy net and values it with the target net
+    const bool duel = a.dueling != 0;
+    const int a_next = first_argmax(a.pol_next_q ? a.pol_next_q + b * S : tgt, A, duel);
+    const float next_q = q_at(tgt, a_next, A, duel, duel ? row_mean(tgt, A) : 0.f);
+    const float keep = a.terminals[b] ? 0.f : 1.f;
+    const float y = a.returns[b] + keep * (a.gamma_n * next_q);            // :152-153
+    dqn_loss_tail(a, b, y, a.actions[b]);
+}
+
 // ---- Munchausen DQN: dqn_loss_kernel with a soft-max bootstrap and the clipped log-policy bonus; one lane per sample ----
-struct MdqnLossArgs {
-    const float* q;                 // policy net on obs              [B][S]
-    const float* tgt_next_q;        // target net on next_obs         [B][S]
-    const float* tgt_cur_q;         // target net on obs              [B][S]
-    const uint8_t* actions;         // [B]
-    const float* returns;           // [B] one-step reward
-    const uint8_t* terminals;       // [B]
-    const float* is_weights;        // [B] or null
-    float* dq;                      // [B][S]
-    float* loss_rows;               // [B] per-sample (weighted) loss / B
-    float* td_abs;                  // [B] priorities: |TD error| clipped to delta_clip
-    int64_t batch;
-    int n_actions, stride;
-    int dueling;
-    float gamma_n, delta_clip;
+// (a Munchausen target selects no action: pol_next_q's slot carries the target net on obs, [B][S]; returns: the reward)
+struct MdqnLossArgs : DqnLossArgs {
     float tau_e, alpha, l0;         // entropy temperature (> 0), bonus scale (>= 0), clip floor (<= 0)
 };
 
@@ -456,35 +435,14 @@ __global__ __launch_bounds__(256) void mdqn_loss_kernel(const MdqnLossArgs a) {
         soft += pi * (qk - (ck - sn.tl));
     }
     const int act = a.actions[b];
-    const float* cur = a.tgt_cur_q + b * S;
+    const float* cur = a.pol_next_q + b * S;
     const float mean_c = duel ? row_mean(cur, A) : 0.f;
     const SoftRow sc = soft_row(cur, A, duel, mean_c, te);
     const float lp_act = (q_at(cur, act, A, duel, mean_c) - sc.v) - sc.tl;
     const float bonus = a.alpha * fminf(fmaxf(lp_act, a.l0), 0.f);         // on terminal rows too
     const float keep = a.terminals[b] ? 0.f : 1.f;
     const float y = (a.returns[b] + bonus) + keep * (a.gamma_n * soft);
-    // from here on: dqn_loss_kernel
-    const float* qrow = a.q + b * S;
-    const float d = y - q_at(qrow, act, A, duel, duel ? row_mean(qrow, A) : 0.f);
-    const float ad = fabsf(d), c = a.delta_clip;
-    float loss = 0.5f * (d * d), slope = d;
-    if (c > 0.f && ad > c) {
-        loss = c * (ad - c / 2.f);
-        slope = d > 0.f ? c : -c;
-    }
-    const float w = (a.is_weights ? a.is_weights[b] : 1.f) / (float)a.batch;
-    float* dq = a.dq + b * S;
-    const float gq = -(w * slope);
-    for (int k = 0; k < S; ++k) dq[k] = 0.f;
-    if (!duel) {
-        dq[act] = gq;
-    } else {
-        const float share = gq / (float)A;
-        for (int k = 0; k < A; ++k) dq[k] = k == act ? gq - share : -share;
-        dq[A] = gq;
-    }
-    a.loss_rows[b] = w * loss;
-    a.td_abs[b] = c > 0.f ? fminf(ad, c) : ad;
+    dqn_loss_tail(a, b, y, act);
 }
 
 // ---- quantile-regression DQN: theta f32[batch][n_actions (+ 1)][q_stride], lane i = quantile i (layout and dueling
@@ -511,10 +469,7 @@ __global__ __launch_bounds__(256) void qrdqn_act_kernel(const float* __restrict_
     const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= batch) return;
     const int g = qr_greedy_action(theta + b * (n_actions + dueling) * stride, lane, n_actions, n, stride, dueling != 0);
-    int act = g;
-    if (override_or_null && override_or_null[b] >= 0) act = override_or_null[b];
-    if (lane < n_actions) onehot[b * n_actions + lane] = lane == act ? 1.f : 0.f;
-    if (lane == 0 && greedy) greedy[b] = (uint8_t)g;
+    serve_wave(g, b, lane, n_actions, override_or_null, onehot, greedy);
 }
 
 struct QrLossArgs {
@@ -571,12 +526,7 @@ __global__ __launch_bounds__(256) void qrdqn_loss_kernel(const QrLossArgs a) {
     }
     __syncthreads();
     if (wave == 0) {
-        int a_next = 0;
-        float best_q = s_q[0];
-        for (int k = 1; k < A; ++k) {
-            const float q = s_q[k];
-            if (q > best_q) { best_q = q; a_next = k; }
-        }
+        const int a_next = first_max(s_q, A);
         const float keep = a.terminals[b] ? 0.f : 1.f;
         s_t[lane] = a.returns[b] + keep * (a.gamma_n * atom_logit(tgt, a_next, lane, n, S, duel_terms(tgt, lane, A, n, S, duel)));
     }
@@ -588,18 +538,8 @@ __global__ __launch_bounds__(256) void qrdqn_loss_kernel(const QrLossArgs a) {
         const float th = s_pred[lane];
         const float tau = ((float)lane + 0.5f) / (float)n;
         for (int j = wave; j < n; j += 4) {
-            const float u = s_t[j] - th;
-            const float wt = fabsf(tau - (u < 0.f ? 1.f : 0.f));
             float gt, rt;
-            if (kappa > 0.f) {
-                const float au = fabsf(u);
-                const float l = au <= kappa ? 0.5f * (u * u) : kappa * (au - 0.5f * kappa);
-                rt = wt * l / kappa;
-                gt = wt * fminf(fmaxf(u, -kappa), kappa) / kappa;
-            } else {
-                rt = wt * fabsf(u);
-                gt = tau - (u < 0.f ? 1.f : 0.f);
-            }
+            quantile_huber_term(s_t[j] - th, tau, kappa, gt, rt);
             g += gt;
             r += rt;
         }
@@ -608,8 +548,7 @@ __global__ __launch_bounds__(256) void qrdqn_loss_kernel(const QrLossArgs a) {
     s_r[wave][lane] = r;
     __syncthreads();
     // every wave combines the four partial sums in the same fixed order (a wave without terms left an exact 0)
-    const float gs = ((s_g[0][lane] + s_g[1][lane]) + s_g[2][lane]) + s_g[3][lane];
-    const float rs = ((s_r[0][lane] + s_r[1][lane]) + s_r[2][lane]) + s_r[3][lane];
+    const float gs = combine4(s_g, lane), rs = combine4(s_r, lane);
     const float wgt = (a.is_weights ? a.is_weights[b] : 1.f) / (float)a.batch;
     const float d_lane = lane < n ? -(wgt / (float)n * gs) : 0.f;          // d loss / d theta(act, lane)
     float* dl = a.dtheta + b * R;
@@ -649,20 +588,35 @@ extern "C" int arl_dqn_act(const float* q, const int32_t* override_or_null, int6
     return arl::check_launch("dqn_act_kernel");
 }
 
+// The checks and fields that arl_dqn_loss and arl_mdqn_loss share, in the order both state them; `fn` names the entry
+// point in the message.  ptrs_ok: every mandatory pointer of the caller is non-null.
+static int fill_dqn_loss(DqnLossArgs& a, const char* fn, bool ptrs_ok, const float* q, const float* tgt_next_q,
+                         const uint8_t* actions, const float* returns, const uint8_t* terminals,
+                         const float* is_weights_or_null, int64_t batch, int32_t n_actions, int32_t q_stride,
+                         int32_t dueling, float gamma_n, float delta_clip, float* dq, float* loss_rows, float* td_abs) {
+    if (!ptrs_ok) {
+        arl::set_error("%s: %s", fn, "null pointer");
+        return ARL_E_ARG;
+    }
+    int rc = check_q(batch, n_actions, q_stride, dueling);
+    if (rc) return rc;
+    a.q = q; a.tgt_next_q = tgt_next_q; a.actions = actions; a.returns = returns; a.terminals = terminals;
+    a.is_weights = is_weights_or_null; a.dq = dq; a.loss_rows = loss_rows; a.td_abs = td_abs; a.batch = batch;
+    a.n_actions = n_actions; a.stride = q_stride; a.dueling = dueling != 0; a.gamma_n = gamma_n; a.delta_clip = delta_clip;
+    return 0;
+}
+
 extern "C" int arl_dqn_loss(const float* q, const float* tgt_next_q, const float* pol_next_q_or_null,
                             const uint8_t* actions, const float* returns, const uint8_t* terminals,
                             const float* is_weights_or_null, int64_t batch, int32_t n_actions, int32_t q_stride,
                             int32_t dueling, float gamma_n, float delta_clip, float* dq, float* loss_rows,
                             float* td_abs, void* stream) {
-    ARL_REQUIRE(q && tgt_next_q && actions && returns && terminals && dq && loss_rows && td_abs, ARL_E_ARG,
-                "null pointer");
-    int rc = check_q(batch, n_actions, q_stride, dueling);
-    if (rc) return rc;
     DqnLossArgs a = {};
-    a.q = q; a.tgt_next_q = tgt_next_q; a.pol_next_q = pol_next_q_or_null; a.actions = actions; a.returns = returns;
-    a.terminals = terminals; a.is_weights = is_weights_or_null; a.dq = dq; a.loss_rows = loss_rows; a.td_abs = td_abs;
-    a.batch = batch; a.n_actions = n_actions; a.stride = q_stride; a.dueling = dueling != 0; a.gamma_n = gamma_n;
-    a.delta_clip = delta_clip;
+    int rc = fill_dqn_loss(a, __func__, q && tgt_next_q && actions && returns && terminals && dq && loss_rows && td_abs, q,
+                           tgt_next_q, actions, returns, terminals, is_weights_or_null, batch, n_actions, q_stride,
+                           dueling, gamma_n, delta_clip, dq, loss_rows, td_abs);
+    if (rc) return rc;
+    a.pol_next_q = pol_next_q_or_null;
     hipLaunchKernelGGL(dqn_loss_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     return arl::check_launch("dqn_loss_kernel");
 }
@@ -672,18 +626,15 @@ extern "C" int arl_mdqn_loss(const float* q, const float* tgt_next_q, const floa
                              int64_t batch, int32_t n_actions, int32_t q_stride, int32_t dueling, float gamma_n,
                              float delta_clip, float tau_e, float alpha, float l0, float* dq, float* loss_rows,
                              float* td_abs, void* stream) {
-    ARL_REQUIRE(q && tgt_next_q && tgt_cur_q && actions && returns && terminals && dq && loss_rows && td_abs, ARL_E_ARG,
-                "null pointer");
-    int rc = check_q(batch, n_actions, q_stride, dueling);
+    MdqnLossArgs a = {};
+    int rc = fill_dqn_loss(a, __func__, q && tgt_next_q && tgt_cur_q && actions && returns && terminals && dq && loss_rows &&
+                           td_abs, q, tgt_next_q, actions, returns, terminals, is_weights_or_null, batch, n_actions,
+                           q_stride, dueling, gamma_n, delta_clip, dq, loss_rows, td_abs);
     if (rc) return rc;
     ARL_REQUIRE(tau_e > 0.f && tau_e <= 3.0e38f, ARL_E_ARG, "tau_e must be finite and > 0");
     ARL_REQUIRE(alpha >= 0.f && alpha <= 3.0e38f, ARL_E_ARG, "alpha must be finite and >= 0");
     ARL_REQUIRE(l0 <= 0.f && l0 >= -3.0e38f, ARL_E_ARG, "l0 must be finite and <= 0");
-    MdqnLossArgs a = {};
-    a.q = q; a.tgt_next_q = tgt_next_q; a.tgt_cur_q = tgt_cur_q; a.actions = actions; a.returns = returns;
-    a.terminals = terminals; a.is_weights = is_weights_or_null; a.dq = dq; a.loss_rows = loss_rows; a.td_abs = td_abs;
-    a.batch = batch; a.n_actions = n_actions; a.stride = q_stride; a.dueling = dueling != 0; a.gamma_n = gamma_n;
-    a.delta_clip = delta_clip; a.tau_e = tau_e; a.alpha = alpha; a.l0 = l0;
+    a.pol_next_q = tgt_cur_q; a.tau_e = tau_e; a.alpha = alpha; a.l0 = l0;
     hipLaunchKernelGGL(mdqn_loss_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     return arl::check_launch("mdqn_loss_kernel");
 }

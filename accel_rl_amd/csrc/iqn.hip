@@ -13,11 +13,15 @@
 //                      soft-max of the target net's Q over the actions (max and exp sum: butterflies over the lanes)
 //
 // Plain fp32 C++ (compiled with -ffp-contract=off), wave64, no atomics: every launch is deterministic.
+// The butterflies, first_max, the quantile-Huber term, the four-way combine and the serve tail are csrc/q_loss_dev.h's.
 
 #include "arl_common.h"
 #include "philox_dev.h"
+#include "q_loss_dev.h"
 
 namespace {
+
+using namespace arlq;
 
 // cos(pi i tau) with the argument reduced in integers: |tau| = s 2^e, the angle in units of pi is i s 2^e.
 __device__ __forceinline__ float cos_pi_i_tau(uint32_t i, float tau) {
@@ -105,23 +109,6 @@ __device__ __forceinline__ float q_of_lane(const float* theta_b, int lane, int n
     return s / (float)k;
 }
 
-// first maximum of q[0 .. n_actions): every lane walks the same LDS row (broadcast reads) and gets the same answer
-__device__ __forceinline__ int first_max(const float* q, int n_actions) {
-    int best = 0;
-    float best_q = q[0];
-    for (int a = 1; a < n_actions; ++a) {
-        const float v = q[a];
-        if (v > best_q) { best_q = v; best = a; }
-    }
-    return best;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {          // butterfly: lane ^ 32, ^ 16, ... ^ 1
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 // one wave per sample, lanes are actions
 __global__ __launch_bounds__(256) void act_kernel(const float* __restrict__ theta,
                                                   const int32_t* __restrict__ override_or_null, int64_t batch,
@@ -132,13 +119,7 @@ __global__ __launch_bounds__(256) void act_kernel(const float* __restrict__ thet
     const int64_t b = (int64_t)blockIdx.x * 4 + wave;
     s_q[wave][lane] = b < batch ? q_of_lane(theta + b * k * stride, lane, n_actions, k, stride) : 0.f;
     __syncthreads();
-    if (b < batch) {
-        const int g = first_max(s_q[wave], n_actions);
-        int act = g;
-        if (override_or_null && override_or_null[b] >= 0) act = override_or_null[b];
-        if (lane < n_actions) onehot[b * n_actions + lane] = lane == act ? 1.f : 0.f;
-        if (lane == 0 && greedy) greedy[b] = (uint8_t)g;
-    }
+    if (b < batch) serve_wave(first_max(s_q[wave], n_actions), b, lane, n_actions, override_or_null, onehot, greedy);
     if (state && blockIdx.x == 0 && threadIdx.x == 0) state[1] += advance;     // this pass's draws have all been made
 }
 
@@ -160,6 +141,47 @@ struct IqnLossArgs {
     int n_actions, n, n_target, stride;
     float gamma_n, kappa;           // kappa == 0: plain quantile regression
 };
+
+// Second half of loss_kernel and mloss_kernel, entered by all 256 threads once s_t (the targets T_j), s_pred and s_tau (the
+// taken action's predicted quantiles and their fractions) are staged and the barrier is passed: the N x N' phase, the
+// four-way combine, loss and priority, the dtheta write and the counter advance.
+__device__ __forceinline__ void loss_tail(const IqnLossArgs& a, int lane, int wave, int act, const float* s_t,
+                                          const float* s_pred, const float* s_tau, float* s_d, float (*s_g)[64],
+                                          float (*s_r)[64]) {
+    const int64_t b = blockIdx.x;
+    const int n = a.n, m = a.n_target, S = a.stride;
+    const float kappa = a.kappa;
+    float g = 0.f, r = 0.f;
+    if (lane < n) {
+        const float th = s_pred[lane], tau = s_tau[lane];
+        for (int j = wave; j < m; j += 4) {
+            float gt, rt;
+            quantile_huber_term(s_t[j] - th, tau, kappa, gt, rt);
+            g += gt;
+            r += rt;
+        }
+    }
+    s_g[wave][lane] = g;
+    s_r[wave][lane] = r;
+    __syncthreads();
+    const float wgt = (a.is_weights ? a.is_weights[b] : 1.f) / (float)a.batch;
+    if (wave == 0) {
+        const float gs = combine4(s_g, lane), rs = combine4(s_r, lane);
+        s_d[lane] = lane < n ? -(wgt / (float)m * gs) : 0.f;    // d loss / d theta(lane, act)
+        const float loss_b = wave_sum(lane < n ? rs : 0.f) / (float)m;
+        if (lane == 0) {
+            a.loss_rows[b] = wgt * loss_b;
+            a.priorities[b] = fminf(fmaxf(loss_b, 1e-6f), 1e6f);
+        }
+    }
+    __syncthreads();
+    float* dl = a.dtheta + b * n * S;
+    for (int o = threadIdx.x; o < n * S; o += 256) {            // row o / S (a fraction), column o % S (an action or padding)
+        const int i = o / S;
+        dl[o] = o - i * S == act ? s_d[i] : 0.f;
+    }
+    if (a.state && b == 0 && threadIdx.x == 0) a.state[1] += a.advance;    // the update's passes have drawn
+}
 
 // One workgroup per sample.  Q phase: wave 0, lane = action, the N' rows of the selecting net read coalesced; meanwhile wave 1
 // stages the taken action's predicted quantiles and their fractions.  Then wave 0 stages T_j (lane = j).  N x N' phase: lane i =
@@ -187,74 +209,11 @@ __global__ __launch_bounds__(256) void loss_kernel(const IqnLossArgs a) {
         s_t[lane] = lane < m ? a.returns[b] + keep * (a.gamma_n * a.tgt_next[(b * m + lane) * S + a_next]) : 0.f;
     }
     __syncthreads();
-    const float kappa = a.kappa;
-    float g = 0.f, r = 0.f;
-    if (lane < n) {
-        const float th = s_pred[lane], tau = s_tau[lane];
-        for (int j = wave; j < m; j += 4) {
-            const float u = s_t[j] - th;
-            const float ind = u < 0.f ? 1.f : 0.f;
-            const float wt = fabsf(tau - ind);
-            float gt, rt;
-            if (kappa > 0.f) {
-                const float au = fabsf(u);
-                const float l = au <= kappa ? 0.5f * (u * u) : kappa * (au - 0.5f * kappa);
-                rt = wt * l / kappa;
-                gt = wt * fminf(fmaxf(u, -kappa), kappa) / kappa;
-            } else {
-                rt = wt * fabsf(u);
-                gt = tau - ind;
-            }
-            g += gt;
-            r += rt;
-        }
-    }
-    s_g[wave][lane] = g;
-    s_r[wave][lane] = r;
-    __syncthreads();
-    const float wgt = (a.is_weights ? a.is_weights[b] : 1.f) / (float)a.batch;
-    if (wave == 0) {
-        const float gs = ((s_g[0][lane] + s_g[1][lane]) + s_g[2][lane]) + s_g[3][lane];
-        const float rs = ((s_r[0][lane] + s_r[1][lane]) + s_r[2][lane]) + s_r[3][lane];
-        s_d[lane] = lane < n ? -(wgt / (float)m * gs) : 0.f;    // d loss / d theta(lane, act)
-        const float loss_b = wave_sum(lane < n ? rs : 0.f) / (float)m;
-        if (lane == 0) {
-            a.loss_rows[b] = wgt * loss_b;
-            a.priorities[b] = fminf(fmaxf(loss_b, 1e-6f), 1e6f);
-        }
-    }
-    __syncthreads();
-    float* dl = a.dtheta + b * n * S;
-    for (int o = threadIdx.x; o < n * S; o += 256) {            // row o / S (a fraction), column o % S (an action or padding)
-        const int i = o / S;
-        dl[o] = o - i * S == act ? s_d[i] : 0.f;
-    }
-    if (a.state && b == 0 && threadIdx.x == 0) a.state[1] += a.advance;    // the update's three passes have drawn
+    loss_tail(a, lane, wave, act, s_t, s_pred, s_tau, s_d, s_g, s_r);
 }
 
-__device__ __forceinline__ float wave_max(float v) {          // butterfly, as wave_sum
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-    return v;
-}
-
-struct MiqnLossArgs {
-    const float* pred;              // online net on obs                  [B][N][S]
-    const float* tau_pred;          // its fractions                      [B][N]
-    const float* tgt_next;          // target net on next_obs             [B][N'][S]
-    const float* tgt_cur;           // target net on obs                  [B][N'][S]
-    const uint8_t* actions;         // [B]
-    const float* returns;           // [B] one-step reward
-    const uint8_t* terminals;       // [B]
-    const float* is_weights;        // [B] or null
-    float* dtheta;                  // [B][N][S]
-    float* loss_rows;               // [B] per-sample (weighted) loss / B
-    float* priorities;              // [B] clip(unweighted loss, 1e-6, 1e6)
-    int64_t* state;                 // (seed, counter) or null
-    int64_t advance;
-    int64_t batch;
-    int n_actions, n, n_target, stride;
-    float gamma_n, kappa;
+// (a Munchausen target selects no action: pol_next's slot carries the target net on obs, [B][N'][S]; returns: the reward)
+struct MiqnLossArgs : IqnLossArgs {
     float tau_e, alpha, l0;         // entropy temperature (> 0), bonus scale (>= 0), clip floor (<= 0)
 };
 
@@ -264,7 +223,7 @@ constexpr int MIQN_TILE_ROW = 64 + 1;       // 64 actions, and odd: the lanes wa
 // Q phase: waves 0 and 2, lane = action, take Q^next and Q^cur (the N' rows read coalesced), wave 1 stages the taken action's
 // predicted quantiles and their fractions, and all 256 threads stage the [N'][A] tile of tgt_next in LDS.  Soft-max phase:
 // waves 0 and 2 take max and exp sum of their row as butterflies; wave 0 keeps pi_a and tau_e log pi_a, wave 2 the bonus.
-// Then wave 0, lane = j, walks its row of the tile (a ascending, from 0) and stages T_j.  The rest is loss_kernel's.
+// Then wave 0, lane = j, walks its row of the tile (a ascending, from 0) and stages T_j.  Then loss_tail.
 __global__ __launch_bounds__(256) void mloss_kernel(const MiqnLossArgs a) {
     __shared__ float s_tile[ARL_IQN_MAX_FRACTIONS * MIQN_TILE_ROW];
     __shared__ float s_q[64], s_qc[64], s_pi[64], s_lp[64], s_bonus;
@@ -281,7 +240,7 @@ __global__ __launch_bounds__(256) void mloss_kernel(const MiqnLossArgs a) {
         s_pred[lane] = lane < n ? a.pred[(b * n + lane) * S + act] : 0.f;
         s_tau[lane] = lane < n ? a.tau_pred[b * n + lane] : 0.f;
     } else if (wave == 2) {
-        s_qc[lane] = q_of_lane(a.tgt_cur + b * m * S, lane, A, m, S);
+        s_qc[lane] = q_of_lane(a.pol_next + b * m * S, lane, A, m, S);
     }
     for (int o = threadIdx.x; o < m * A; o += 256) {            // row o / A (a fraction), column o % A (an action)
         const int j = o / A;
@@ -311,50 +270,7 @@ __global__ __launch_bounds__(256) void mloss_kernel(const MiqnLossArgs a) {
         s_t[lane] = lane < m ? (a.returns[b] + s_bonus) + keep * (a.gamma_n * soft) : 0.f;
     }
     __syncthreads();
-    // from here on: loss_kernel
-    const float kappa = a.kappa;
-    float g = 0.f, r = 0.f;
-    if (lane < n) {
-        const float th = s_pred[lane], tau = s_tau[lane];
-        for (int j = wave; j < m; j += 4) {
-            const float u = s_t[j] - th;
-            const float ind = u < 0.f ? 1.f : 0.f;
-            const float wt = fabsf(tau - ind);
-            float gt, rt;
-            if (kappa > 0.f) {
-                const float au = fabsf(u);
-                const float l = au <= kappa ? 0.5f * (u * u) : kappa * (au - 0.5f * kappa);
-                rt = wt * l / kappa;
-                gt = wt * fminf(fmaxf(u, -kappa), kappa) / kappa;
-            } else {
-                rt = wt * fabsf(u);
-                gt = tau - ind;
-            }
-            g += gt;
-            r += rt;
-        }
-    }
-    s_g[wave][lane] = g;
-    s_r[wave][lane] = r;
-    __syncthreads();
-    const float wgt = (a.is_weights ? a.is_weights[b] : 1.f) / (float)a.batch;
-    if (wave == 0) {
-        const float gs = ((s_g[0][lane] + s_g[1][lane]) + s_g[2][lane]) + s_g[3][lane];
-        const float rs = ((s_r[0][lane] + s_r[1][lane]) + s_r[2][lane]) + s_r[3][lane];
-        s_d[lane] = lane < n ? -(wgt / (float)m * gs) : 0.f;
-        const float loss_b = wave_sum(lane < n ? rs : 0.f) / (float)m;
-        if (lane == 0) {
-            a.loss_rows[b] = wgt * loss_b;
-            a.priorities[b] = fminf(fmaxf(loss_b, 1e-6f), 1e6f);
-        }
-    }
-    __syncthreads();
-    float* dl = a.dtheta + b * n * S;
-    for (int o = threadIdx.x; o < n * S; o += 256) {
-        const int i = o / S;
-        dl[o] = o - i * S == act ? s_d[i] : 0.f;
-    }
-    if (a.state && b == 0 && threadIdx.x == 0) a.state[1] += a.advance;
+    loss_tail(a, lane, wave, act, s_t, s_pred, s_tau, s_d, s_g, s_r);
 }
 
 inline unsigned grid_for(int64_t n) { return (unsigned)((n + 255) / 256); }
@@ -424,21 +340,41 @@ extern "C" int arl_iqn_act(const float* theta, const int32_t* override_or_null, 
     return arl::check_launch("iqn act_kernel");
 }
 
+// The checks and fields that arl_iqn_loss and arl_miqn_loss share, in the order both state them; `fn` names the entry
+// point in the message.  ptrs_ok: every mandatory pointer of the caller is non-null.
+static int fill_iqn_loss(IqnLossArgs& a, const char* fn, bool ptrs_ok, const float* pred, const float* tau_pred,
+                         const float* tgt_next, const uint8_t* actions, const float* returns, const uint8_t* terminals,
+                         const float* is_weights_or_null, int64_t batch, int32_t n_actions, int32_t n, int32_t n_target,
+                         int32_t a_stride, float gamma_n, float kappa, float* dtheta, float* loss_rows,
+                         float* priorities, int64_t* state_or_null, int64_t advance) {
+    const char* msg = nullptr;
+    if (!ptrs_ok) msg = "null pointer";
+    else if (!(theta_sizes_ok(batch, n_actions, n, a_stride) && theta_sizes_ok(batch, n_actions, n_target, a_stride)))
+        msg = THETA_SIZES;
+    else if (!(kappa >= 0.f && kappa <= 3.0e38f)) msg = "kappa must be finite and >= 0";
+    if (msg) {
+        arl::set_error("%s: %s", fn, msg);
+        return ARL_E_ARG;
+    }
+    a.pred = pred; a.tau_pred = tau_pred; a.tgt_next = tgt_next; a.actions = actions; a.returns = returns;
+    a.terminals = terminals; a.is_weights = is_weights_or_null; a.dtheta = dtheta; a.loss_rows = loss_rows;
+    a.priorities = priorities; a.state = state_or_null; a.advance = advance; a.batch = batch; a.n_actions = n_actions;
+    a.n = n; a.n_target = n_target; a.stride = a_stride; a.gamma_n = gamma_n; a.kappa = kappa;
+    return 0;
+}
+
 extern "C" int arl_iqn_loss(const float* pred, const float* tau_pred, const float* tgt_next,
                             const float* pol_next_or_null, const uint8_t* actions, const float* returns,
                             const uint8_t* terminals, const float* is_weights_or_null, int64_t batch, int32_t n_actions,
                             int32_t n, int32_t n_target, int32_t a_stride, float gamma_n, float kappa, float* dtheta,
                             float* loss_rows, float* priorities, int64_t* state_or_null, int64_t advance, void* stream) {
-    ARL_REQUIRE(pred && tau_pred && tgt_next && actions && returns && terminals && dtheta && loss_rows && priorities,
-                ARL_E_ARG, "null pointer");
-    ARL_REQUIRE(theta_sizes_ok(batch, n_actions, n, a_stride) && theta_sizes_ok(batch, n_actions, n_target, a_stride),
-                ARL_E_ARG, THETA_SIZES);
-    ARL_REQUIRE(kappa >= 0.f && kappa <= 3.0e38f, ARL_E_ARG, "kappa must be finite and >= 0");
     IqnLossArgs a = {};
-    a.pred = pred; a.tau_pred = tau_pred; a.tgt_next = tgt_next; a.pol_next = pol_next_or_null; a.actions = actions;
-    a.returns = returns; a.terminals = terminals; a.is_weights = is_weights_or_null; a.dtheta = dtheta;
-    a.loss_rows = loss_rows; a.priorities = priorities; a.state = state_or_null; a.advance = advance; a.batch = batch;
-    a.n_actions = n_actions; a.n = n; a.n_target = n_target; a.stride = a_stride; a.gamma_n = gamma_n; a.kappa = kappa;
+    const bool ptrs_ok = pred && tau_pred && tgt_next && actions && returns && terminals && dtheta && loss_rows && priorities;
+    int rc = fill_iqn_loss(a, __func__, ptrs_ok, pred, tau_pred, tgt_next, actions, returns, terminals, is_weights_or_null,
+                           batch, n_actions, n, n_target, a_stride, gamma_n, kappa, dtheta, loss_rows, priorities,
+                           state_or_null, advance);
+    if (rc) return rc;
+    a.pol_next = pol_next_or_null;
     hipLaunchKernelGGL(loss_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, a);
     return arl::check_launch("iqn loss_kernel");
 }
@@ -449,20 +385,17 @@ extern "C" int arl_miqn_loss(const float* pred, const float* tau_pred, const flo
                              int32_t n_target, int32_t a_stride, float gamma_n, float kappa, float tau_e, float alpha,
                              float l0, float* dtheta, float* loss_rows, float* priorities, int64_t* state_or_null,
                              int64_t advance, void* stream) {
-    ARL_REQUIRE(pred && tau_pred && tgt_next && tgt_cur && actions && returns && terminals && dtheta && loss_rows &&
-                priorities, ARL_E_ARG, "null pointer");
-    ARL_REQUIRE(theta_sizes_ok(batch, n_actions, n, a_stride) && theta_sizes_ok(batch, n_actions, n_target, a_stride),
-                ARL_E_ARG, THETA_SIZES);
-    ARL_REQUIRE(kappa >= 0.f && kappa <= 3.0e38f, ARL_E_ARG, "kappa must be finite and >= 0");
+    MiqnLossArgs a = {};
+    const bool ptrs_ok = pred && tau_pred && tgt_next && tgt_cur && actions && returns && terminals && dtheta && loss_rows &&
+                         priorities;
+    int rc = fill_iqn_loss(a, __func__, ptrs_ok, pred, tau_pred, tgt_next, actions, returns, terminals, is_weights_or_null,
+                           batch, n_actions, n, n_target, a_stride, gamma_n, kappa, dtheta, loss_rows, priorities,
+                           state_or_null, advance);
+    if (rc) return rc;
     ARL_REQUIRE(tau_e > 0.f && tau_e <= 3.0e38f, ARL_E_ARG, "tau_e must be finite and > 0");
     ARL_REQUIRE(alpha >= 0.f && alpha <= 3.0e38f, ARL_E_ARG, "alpha must be finite and >= 0");
     ARL_REQUIRE(l0 <= 0.f && l0 >= -3.0e38f, ARL_E_ARG, "l0 must be finite and <= 0");
-    MiqnLossArgs a = {};
-    a.pred = pred; a.tau_pred = tau_pred; a.tgt_next = tgt_next; a.tgt_cur = tgt_cur; a.actions = actions;
-    a.returns = returns; a.terminals = terminals; a.is_weights = is_weights_or_null; a.dtheta = dtheta;
-    a.loss_rows = loss_rows; a.priorities = priorities; a.state = state_or_null; a.advance = advance; a.batch = batch;
-    a.n_actions = n_actions; a.n = n; a.n_target = n_target; a.stride = a_stride; a.gamma_n = gamma_n; a.kappa = kappa;
-    a.tau_e = tau_e; a.alpha = alpha; a.l0 = l0;
+    a.pol_next = tgt_cur; a.tau_e = tau_e; a.alpha = alpha; a.l0 = l0;
     hipLaunchKernelGGL(mloss_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, a);
     return arl::check_launch("iqn mloss_kernel");
 }

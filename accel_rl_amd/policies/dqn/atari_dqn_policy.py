@@ -98,24 +98,33 @@ class AtariDqnPolicy(QPolicyBase):
             return self._merged(self._logits(self._scaled(observations), w=self._w_target, tag="t")[0])
 
     # ---- training ------------------------------------------------------------
+    def _loss_and_backward(self, x, q, acts, hids, launch):
+        """What both losses do once their forward passes are made: launch(dq, loss_rows, td_abs) is the loss kernel, then
+        the full backward pass into flat_grads.  Returns (loss_rows, td_abs), the two rows of one (2, B) buffer."""
+        b = q.shape[0]
+        dq = self._buffer(("dlogits", b), tuple(q.shape))
+        pack = self._buffer(("loss_td", b), (2, b))         # one buffer: DqnOptimizer's statistics ring takes both rows at once
+        loss_rows, td_abs = pack[0], pack[1]
+        launch(dq, loss_rows, td_abs)
+        self._head_backward(dq, x, acts, hids)
+        if self._shared_last_bias:          # the folds have run: d loss / d (shared scalar) = the sum over the actions
+            gb = self.grads[self._k_head + 1]
+            gb[:self.n_act] = gb[:self.n_act].sum()
+        return loss_rows, td_abs
+
     def q_loss_and_grads(self, obs, next_obs, actions, returns, terminals, is_weights, gamma_n, delta_clip,
                          double_dqn=False):
         """One minibatch of DQN.build_loss (dqn.py:137-172): forward of the policy net on obs, of the target
         net (and, for double DQN, the policy net) on next_obs, the (Huber) TD loss, and the full backward
         pass into flat_grads.  Returns (loss_rows f32[B] whose sum is the loss, td_abs f32[B])."""
         with torch.no_grad():
-            b = obs.shape[0]
             x, q, acts, hids, tgt_q, pol_next = self._forward_for_loss(obs, next_obs, double_dqn)
-            dq = self._buffer(("dlogits", b), tuple(q.shape))
-            pack = self._buffer(("loss_td", b), (2, b))         # one buffer: DqnOptimizer's statistics ring takes both rows at once
-            loss_rows, td_abs = pack[0], pack[1]
-            _lib.dqn_loss(q, tgt_q, pol_next, actions, returns, terminals, is_weights, self.n_act, gamma_n,
-                          delta_clip, dq, loss_rows, td_abs, dueling=self._dueling)
-            self._head_backward(dq, x, acts, hids)
-            if self._shared_last_bias:          # the folds have run: d loss / d (shared scalar) = the sum over the actions
-                gb = self.grads[self._k_head + 1]
-                gb[:self.n_act] = gb[:self.n_act].sum()
-            return loss_rows, td_abs
+
+            def launch(dq, loss_rows, td_abs):
+                _lib.dqn_loss(q, tgt_q, pol_next, actions, returns, terminals, is_weights, self.n_act, gamma_n,
+                              delta_clip, dq, loss_rows, td_abs, dueling=self._dueling)
+
+            return self._loss_and_backward(x, q, acts, hids, launch)
 
     def munchausen_loss_and_grads(self, obs, next_obs, actions, returns, terminals, is_weights, gamma_n, delta_clip,
                                   tau_e, alpha, l0):
@@ -136,13 +145,9 @@ class AtariDqnPolicy(QPolicyBase):
                 x = self._scaled(obs)
                 tgt_cur = self._logits(x, w=self._w_target, tag="tc")[0]
             q, acts, hids = self._logits(x)
-            dq = self._buffer(("dlogits", b), tuple(q.shape))
-            pack = self._buffer(("loss_td", b), (2, b))         # one buffer: DqnOptimizer's statistics ring takes both rows at once
-            loss_rows, td_abs = pack[0], pack[1]
-            _lib.mdqn_loss(q, tgt_next, tgt_cur, actions, returns, terminals, is_weights, self.n_act, gamma_n,
-                           delta_clip, tau_e, alpha, l0, dq, loss_rows, td_abs, dueling=self._dueling)
-            self._head_backward(dq, x, acts, hids)
-            if self._shared_last_bias:          # the folds have run: d loss / d (shared scalar) = the sum over the actions
-                gb = self.grads[self._k_head + 1]
-                gb[:self.n_act] = gb[:self.n_act].sum()
-            return loss_rows, td_abs
+
+            def launch(dq, loss_rows, td_abs):
+                _lib.mdqn_loss(q, tgt_next, tgt_cur, actions, returns, terminals, is_weights, self.n_act, gamma_n,
+                               delta_clip, tau_e, alpha, l0, dq, loss_rows, td_abs, dueling=self._dueling)
+
+            return self._loss_and_backward(x, q, acts, hids, launch)

@@ -161,7 +161,7 @@ class AtariIqnPolicy(QPolicyBase):
         return tau, cosf, phi, x, hids, theta
 
     # ---- serving --------------------------------------------------------------------------------------------------
-    def _serve_rows(self, observations, override, onehot, greedy=None):
+    def _serve_obs(self, observations, override, onehot, greedy=None):
         """Epsilon-greedy / greedy actions of every row at K fractions each, in passes of at most serve_pair_rows // K
         rows.  Every pass reads the same call's stream at its rows' global indices, so the split changes no result;
         the last pass's action launch advances the counter by the number of passes."""
@@ -178,40 +178,20 @@ class AtariIqnPolicy(QPolicyBase):
                          None if greedy is None else greedy[lo:hi], state=self._iqn_state if last else None,
                          advance=len(starts) if last else 0)
 
-    def _step_overrides(self, b):
-        if b in self._overrides and self._step < self._overrides[b][1].shape[0]:
-            return self._overrides[b][1][self._step]
-        return None
-
-    def prob_value(self, observations):
-        with torch.no_grad():
-            b = observations.shape[0]
-            onehot = torch.empty((b, self.n_act), dtype=torch.float32, device=self.device)
-            self._serve_rows(observations, self._step_overrides(b), onehot)
-            if not hasattr(self, "_zero_value") or self._zero_value.numel() != b:
-                self._zero_value = torch.zeros(b, dtype=torch.float32, device=self.device)
-            return onehot, self._zero_value
-
-    def serve_group(self, observations, row0, n_envs):
-        with torch.no_grad():
-            b = observations.shape[0]
-            onehot = torch.empty((b, self.n_act), dtype=torch.float32, device=self.device)
-            table = self._overrides[n_envs][1]
-            if self._step >= table.shape[0] or row0 + b > table.shape[1]:
-                raise IndexError("serve_group: step %d / rows %d..%d outside the %s override table" %
-                                 (self._step, row0, row0 + b, tuple(table.shape)))
-            self._serve_rows(observations, table[self._step, row0:row0 + b], onehot)
-            return onehot, torch.zeros(b, dtype=torch.float32, device=self.device)
-
-    def greedy_actions(self, observations):
-        with torch.no_grad():
-            b = observations.shape[0]
-            onehot = torch.empty((b, self.n_act), dtype=torch.float32, device=self.device)
-            greedy = torch.empty(b, dtype=torch.uint8, device=self.device)
-            self._serve_rows(observations, None, onehot, greedy)
-            return greedy
-
     # ---- training -------------------------------------------------------------------------------------------------
+    def _loss_and_backward(self, x, acts, online, b, launch):
+        """What both losses do once their forward passes are made (online: _quantile_pass of the online net on obs):
+        launch(theta, tau, dtheta, loss_rows, priorities) is the loss kernel, then the full backward pass into flat_grads.
+        Returns (loss_rows, priorities), the two rows of one (2, B) buffer."""
+        tau, cosf, phi, merged, hids, theta = online
+        n = self.n_quantiles
+        dtheta = self._buffer(("dtheta", b), (b * n, self._a_stride))
+        pack = self._buffer(("loss_pri", b), (2, b))        # one buffer: DqnOptimizer's statistics ring takes both rows at once
+        loss_rows, priorities = pack[0], pack[1]
+        launch(theta, tau, dtheta, loss_rows, priorities)
+        self._pair_backward(x, acts, acts[-1].view(b, self._f), cosf, phi, merged, hids, dtheta, b, n)
+        return loss_rows, priorities
+
     def iqn_loss_and_grads(self, obs, next_obs, actions, returns, terminals, is_weights, gamma_n, kappa,
                            double_dqn=False, taus=None):
         """One minibatch of ImplicitQuantileDQN.build_loss: the online net on obs at N fractions, the target net (and,
@@ -236,19 +216,18 @@ class AtariIqnPolicy(QPolicyBase):
                 x = self._scaled(obs)
                 acts = self._convs(x)
             psi = acts[-1].view(b, f)
-            tau, cosf, phi, merged, hids, theta = self._quantile_pass(psi, n, tau_in=t_pred, call_offset=0)
+            online = self._quantile_pass(psi, n, tau_in=t_pred, call_offset=0)
             tgt = self._quantile_pass(psi_t.view(b, f), m, w=self._w_target, tag="t", tau_in=t_tgt, call_offset=1)[-1]
             pol = None
             if double_dqn:
                 pol = self._quantile_pass(psi_d.view(b, f), m, tag="d", tau_in=t_pol, call_offset=2)[-1]
-            dtheta = self._buffer(("dtheta", b), (b * n, self._a_stride))
-            pack = self._buffer(("loss_pri", b), (2, b))        # one buffer: DqnOptimizer's statistics ring takes both rows at once
-            loss_rows, priorities = pack[0], pack[1]
-            _lib.iqn_loss(theta, tau, tgt, pol, actions, returns, terminals, is_weights, self.n_act, n, m, gamma_n,
-                          kappa, dtheta, loss_rows, priorities, state=None if taus is not None else self._iqn_state,
-                          advance=3)
-            self._pair_backward(x, acts, psi, cosf, phi, merged, hids, dtheta, b, n)
-            return loss_rows, priorities
+
+            def launch(theta, tau, dtheta, loss_rows, priorities):
+                _lib.iqn_loss(theta, tau, tgt, pol, actions, returns, terminals, is_weights, self.n_act, n, m, gamma_n,
+                              kappa, dtheta, loss_rows, priorities,
+                              state=None if taus is not None else self._iqn_state, advance=3)
+
+            return self._loss_and_backward(x, acts, online, b, launch)
 
     def munchausen_loss_and_grads(self, obs, next_obs, actions, returns, terminals, is_weights, gamma_n, kappa, tau_e,
                                   alpha, l0, taus=None):
@@ -273,17 +252,16 @@ class AtariIqnPolicy(QPolicyBase):
                 psi_tc = self._convs(x, w=self._w_target, tag="tc")[-1].view(b, f)
             acts = self._convs(x)
             psi = acts[-1].view(b, f)
-            tau, cosf, phi, merged, hids, theta = self._quantile_pass(psi, n, tau_in=t_pred, call_offset=0)
+            online = self._quantile_pass(psi, n, tau_in=t_pred, call_offset=0)
             tgt_next = self._quantile_pass(psi_tn, m, w=self._w_target, tag="t", tau_in=t_next, call_offset=1)[-1]
             tgt_cur = self._quantile_pass(psi_tc, m, w=self._w_target, tag="tc", tau_in=t_cur, call_offset=2)[-1]
-            dtheta = self._buffer(("dtheta", b), (b * n, self._a_stride))
-            pack = self._buffer(("loss_pri", b), (2, b))        # one buffer: DqnOptimizer's statistics ring takes both rows at once
-            loss_rows, priorities = pack[0], pack[1]
-            _lib.miqn_loss(theta, tau, tgt_next, tgt_cur, actions, returns, terminals, is_weights, self.n_act, n, m,
-                           gamma_n, kappa, tau_e, alpha, l0, dtheta, loss_rows, priorities,
-                           state=None if taus is not None else self._iqn_state, advance=3)
-            self._pair_backward(x, acts, psi, cosf, phi, merged, hids, dtheta, b, n)
-            return loss_rows, priorities
+
+            def launch(theta, tau, dtheta, loss_rows, priorities):
+                _lib.miqn_loss(theta, tau, tgt_next, tgt_cur, actions, returns, terminals, is_weights, self.n_act, n, m,
+                               gamma_n, kappa, tau_e, alpha, l0, dtheta, loss_rows, priorities,
+                               state=None if taus is not None else self._iqn_state, advance=3)
+
+            return self._loss_and_backward(x, acts, online, b, launch)
 
     def _pair_backward(self, x, acts, psi, cosf, phi, merged, hids, dtheta, b, r):
         """Backward of one online pass at b r rows: output layer, hidden layers, the merge, the embedding layer's weight
@@ -294,12 +272,8 @@ class AtariIqnPolicy(QPolicyBase):
         dh = self._buffer(("dh", n), (n, self._hid_geom[-1][0]))
         done = self._folds.conv2d_bwd_pair(dtheta, self._w[k], hids[-1], dh, hids[-1], self._g[k], g_out,
                                            self._fold_ws(("dw", k)), dbias=self.grads[k + 1])
-        if not done:        # generic kernels: column sums as the weight gradient of an all-ones input (_head_backward)
-            ones = self._buffer(("ones4", n), (n, 4))
-            ones.fill_(1.)
-            db4 = self._buffer(("db4", n), (dtheta.shape[1], 4))
-            _lib.conv2d_bwd_weight(dtheta, ones, db4, self._ones_geom(n, dtheta.shape[1]), self._conv_ws)
-            self.grads[k + 1].copy_(db4[:, 0])
+        if not done:        # generic kernels
+            self._bias_grad_by_ones(dtheta, n, k)
         d_cur = dh
         for j in range(self._n_hid - 1, -1, -1):
             k -= 2

@@ -26,7 +26,8 @@ from accel_rl_amd.policies.atari_cnn_policy import AtariCnnPolicy, ObsRows, _nor
 
 class QPolicyBase(AtariCnnPolicy):
     """Subclasses give `_head_width` (columns of the output layer as stored), `_serve(out, override, onehot,
-    greedy)` (the action kernel) and the four `_head_*` layout hooks."""
+    greedy)` (the action kernel; or, where the network is not `_logits`, `_serve_obs`) and the four `_head_*` layout
+    hooks."""
 
     serves_rows = False         # own prob_value: the sampler keeps a contiguous copy of the current observations
     _epsilon = 1
@@ -193,17 +194,22 @@ class QPolicyBase(AtariCnnPolicy):
             self._geoms[key] = _lib.dense_geom(b, self._hid_geom[-1][0], self._head_width)
         return self._geoms[key]
 
+    def _serve_obs(self, observations, override, onehot, greedy=None):
+        """The network on `observations`, then the action kernel: what the three serving calls below share."""
+        self._serve(self._logits(self._scaled(observations))[0], override, onehot, greedy)
+
+    def _step_overrides(self, b):
+        if b in self._overrides and self._step < self._overrides[b][1].shape[0]:
+            return self._overrides[b][1][self._step]
+        return None
+
     def prob_value(self, observations):
         """The sampler's serving call: a one-hot 'prob' row for the epsilon-greedy action of this
         step (so that the categorical sampling kernel picks it) and a zero 'value'."""
         with torch.no_grad():
             b = observations.shape[0]
-            logits, _, _ = self._logits(self._scaled(observations))
             onehot = torch.empty((b, self.n_act), dtype=torch.float32, device=self.device)
-            ov = None
-            if b in self._overrides and self._step < self._overrides[b][1].shape[0]:
-                ov = self._overrides[b][1][self._step]
-            self._serve(logits, ov, onehot)
+            self._serve_obs(observations, self._step_overrides(b), onehot)
             if not hasattr(self, "_zero_value") or self._zero_value.numel() != b:
                 self._zero_value = torch.zeros(b, dtype=torch.float32, device=self.device)
             return onehot, self._zero_value
@@ -214,22 +220,20 @@ class QPolicyBase(AtariCnnPolicy):
         step's row of the override table that host_draws(horizon, n_envs) filled."""
         with torch.no_grad():
             b = observations.shape[0]
-            logits, _, _ = self._logits(self._scaled(observations))
             onehot = torch.empty((b, self.n_act), dtype=torch.float32, device=self.device)
             table = self._overrides[n_envs][1]
             if self._step >= table.shape[0] or row0 + b > table.shape[1]:
                 raise IndexError("serve_group: step %d / rows %d..%d outside the %s override table" %
                                  (self._step, row0, row0 + b, tuple(table.shape)))
-            self._serve(logits, table[self._step, row0:row0 + b], onehot)
+            self._serve_obs(observations, table[self._step, row0:row0 + b], onehot)
             return onehot, torch.zeros(b, dtype=torch.float32, device=self.device)
 
     def greedy_actions(self, observations):
         with torch.no_grad():
             b = observations.shape[0]
-            logits, _, _ = self._logits(self._scaled(observations))
             onehot = torch.empty((b, self.n_act), dtype=torch.float32, device=self.device)
             greedy = torch.empty(b, dtype=torch.uint8, device=self.device)
-            self._serve(logits, None, onehot, greedy)
+            self._serve_obs(observations, None, onehot, greedy)
             return greedy
 
     # ---- epsilon-greedy draws (host RNG, reference order) ---------------------
@@ -292,6 +296,15 @@ class QPolicyBase(AtariCnnPolicy):
         self.flat_target.copy_(self.flat_params)
 
     # ---- training: the output layer's backward, then the trunk's ---------------------
+    def _bias_grad_by_ones(self, dout, rows, k):
+        """grads[k + 1] = column sums of dout f32[rows][width], as the weight gradient of an all-ones input: the fallback
+        where the weight-gradient kernel did not carry the bias gradient along."""
+        ones = self._buffer(("ones4", rows), (rows, 4))
+        ones.fill_(1.)
+        db4 = self._buffer(("db4", rows), (dout.shape[1], 4))
+        _lib.conv2d_bwd_weight(dout, ones, db4, self._ones_geom(rows, dout.shape[1]), self._conv_ws)
+        self.grads[k + 1].copy_(db4[:, 0])
+
     def _head_backward(self, dout, x, acts, hids):
         """dW = dout^T h, db = column sums of dout (riding along in the weight-gradient kernel),
         dh = (dout W) * (h > 0) -- one launch; the folds run at the end of the trunk's backward."""
@@ -302,12 +315,8 @@ class QPolicyBase(AtariCnnPolicy):
         dh = self._buffer(("dh", b), (b, hid))
         done = self._folds.conv2d_bwd_pair(dout, self._w[k], hids[-1], dh, hids[-1], self._g[k], geom,
                                            self._fold_ws(("dw", k)), dbias=self.grads[k + 1])
-        if not done:        # ragged batch (generic kernels): column sums as the weight gradient of an all-ones input
-            ones = self._buffer(("ones4", b), (b, 4))
-            ones.fill_(1.)
-            db4 = self._buffer(("db4", b), (dout.shape[1], 4))
-            _lib.conv2d_bwd_weight(dout, ones, db4, self._ones_geom(b, dout.shape[1]), self._conv_ws)
-            self.grads[k + 1].copy_(db4[:, 0])
+        if not done:        # ragged batch (generic kernels)
+            self._bias_grad_by_ones(dout, b, k)
         self._backward_trunk(x, acts, hids, dh, masked=True)
         if self._dueling:                 # the folds have run: keep the absent blocks' gradient at exactly zero
             self.grads[k].mul_(self._duel_mask)
