@@ -218,6 +218,9 @@ _SIGNATURES = {
     "arl_iqn_loss": (_i32, [_vp] * 8 + [_i64, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "arl_miqn_loss": (_i32, [_vp] * 8 + [_i64, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp,
                              _i64, _vp]),
+    "arl_fqf_fractions": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "arl_fqf_act": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "arl_fqf_loss": (_i32, [_vp] * 13 + [_i64, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "arl_dqn_act": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "arl_dqn_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "arl_mdqn_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
@@ -1157,6 +1160,46 @@ def miqn_loss(pred, tau_pred, tgt_next, tgt_cur, actions, returns, terminals, is
                                 ptr(terminals), ptr(is_weights), batch, n_actions, n, n_target, stride, float(gamma_n),
                                 float(kappa), float(tau_e), float(alpha), float(l0), ptr(dtheta), ptr(loss_rows),
                                 ptr(priorities), ptr(state), advance, stream_ptr(stream)), "arl_miqn_loss")
+
+
+# ---- fully parameterized quantile functions (csrc/fqf.hip): logits f32[batch][n_stride], tau f32[batch][n + 1] ----
+def fqf_fractions(logits, n, tau, tau_hat, tau_mid=None, q=None, logq=None, entropy=None, stream=None):
+    """Soft-max of the n logits of every row -> tau (n + 1 per row, 0 .. 1), tau_hat (midpoints) and, where given, the
+    compact inner fractions tau_mid (n - 1 per row), q, log q and the entropy."""
+    batch = tau_hat.numel() // n
+    n_stride = logits.numel() // batch
+    assert tau.numel() == batch * (n + 1) and tau_hat.numel() == batch * n, "tau / tau_hat size"
+    assert tau_mid is None or tau_mid.numel() == batch * (n - 1), "tau_mid size"
+    assert all(t is None or t.numel() == batch * n for t in (q, logq)) and (entropy is None or entropy.numel() == batch), \
+        "q / logq / entropy size"
+    _check(load().arl_fqf_fractions(ptr(logits), batch, n, n_stride, ptr(tau), ptr(tau_hat), ptr(tau_mid), ptr(q),
+                                    ptr(logq), ptr(entropy), stream_ptr(stream)), "arl_fqf_fractions")
+
+
+def fqf_act(theta, tau, override, n_actions, k, onehot, greedy=None, stream=None):
+    batch = onehot.shape[0]
+    stride = theta.numel() // (batch * k)
+    assert tau.numel() == batch * (k + 1), "tau size"
+    _check(load().arl_fqf_act(ptr(theta), ptr(tau), ptr(override), batch, n_actions, k, stride, ptr(onehot), ptr(greedy),
+                              stream_ptr(stream)), "arl_fqf_act")
+
+
+def fqf_loss(pred, pred_mid, tau, tau_hat, q, logq, entropy, tgt_next, pol_next, actions, returns, terminals, is_weights,
+             n_actions, n, gamma_n, kappa, ent_coef, dtheta, loss_rows, priorities, dlogits, frac_rows, stream=None):
+    """pred / tgt_next / pol_next: the nets at tau_hat; pred_mid: the online net at tau_1 .. tau_{n-1} (None when n == 1).
+    kappa 0: plain quantile regression.  frac_rows is a surrogate (right gradient, not W1's value)."""
+    batch = actions.numel()
+    stride = pred.numel() // (batch * n)
+    n_stride = dlogits.numel() // batch
+    assert tau.numel() == batch * (n + 1) and tau_hat.numel() == q.numel() == logq.numel() == batch * n, "fraction sizes"
+    assert tgt_next.numel() == pred.numel() == dtheta.numel() and entropy.numel() == batch, "tgt_next / dtheta / entropy size"
+    assert pol_next is None or pol_next.numel() == tgt_next.numel(), "pol_next size"
+    assert (pred_mid is None and n == 1) or pred_mid.numel() == batch * (n - 1) * stride, "pred_mid size"
+    _check(load().arl_fqf_loss(ptr(pred), ptr(pred_mid), ptr(tau), ptr(tau_hat), ptr(q), ptr(logq), ptr(entropy),
+                               ptr(tgt_next), ptr(pol_next), ptr(actions), ptr(returns), ptr(terminals), ptr(is_weights),
+                               batch, n_actions, n, stride, n_stride, float(gamma_n), float(kappa), float(ent_coef),
+                               ptr(dtheta), ptr(loss_rows), ptr(priorities), ptr(dlogits), ptr(frac_rows),
+                               stream_ptr(stream)), "arl_fqf_loss")
 
 
 def dqn_act(q, override, n_actions, onehot, greedy=None, dueling=False, stream=None):

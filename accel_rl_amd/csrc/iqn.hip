@@ -13,7 +13,9 @@
 //                      soft-max of the target net's Q over the actions (max and exp sum: butterflies over the lanes)
 //
 // Plain fp32 C++ (compiled with -ffp-contract=off), wave64, no atomics: every launch is deterministic.
-// The butterflies, first_max, the quantile-Huber term, the four-way combine and the serve tail are csrc/q_loss_dev.h's.
+// The butterflies, first_max, the quantile-Huber term, the four-way combine and the serve tail are csrc/q_loss_dev.h's, and
+// so are IqnLossArgs, its host-side checks (theta_sizes_ok, fill_iqn_loss), the staging of the taken action's quantiles and
+// of T_j, and loss_tail: csrc/fqf.hip runs the same quantile part.
 
 #include "arl_common.h"
 #include "philox_dev.h"
@@ -123,66 +125,6 @@ __global__ __launch_bounds__(256) void act_kernel(const float* __restrict__ thet
     if (state && blockIdx.x == 0 && threadIdx.x == 0) state[1] += advance;     // this pass's draws have all been made
 }
 
-struct IqnLossArgs {
-    const float* pred;              // online net on obs                  [B][N][S]
-    const float* tau_pred;          // its fractions                      [B][N]
-    const float* tgt_next;          // target net on next_obs             [B][N'][S]
-    const float* pol_next;          // online net on next_obs (double DQN) or null
-    const uint8_t* actions;         // [B]
-    const float* returns;           // [B] n-step discounted return
-    const uint8_t* terminals;       // [B]
-    const float* is_weights;        // [B] or null
-    float* dtheta;                  // [B][N][S]
-    float* loss_rows;               // [B] per-sample (weighted) loss / B
-    float* priorities;              // [B] clip(unweighted loss, 1e-6, 1e6)
-    int64_t* state;                 // (seed, counter) or null
-    int64_t advance;
-    int64_t batch;
-    int n_actions, n, n_target, stride;
-    float gamma_n, kappa;           // kappa == 0: plain quantile regression
-};
-
-// Second half of loss_kernel and mloss_kernel, entered by all 256 threads once s_t (the targets T_j), s_pred and s_tau (the
-// taken action's predicted quantiles and their fractions) are staged and the barrier is passed: the N x N' phase, the
-// four-way combine, loss and priority, the dtheta write and the counter advance.
-__device__ __forceinline__ void loss_tail(const IqnLossArgs& a, int lane, int wave, int act, const float* s_t,
-                                          const float* s_pred, const float* s_tau, float* s_d, float (*s_g)[64],
-                                          float (*s_r)[64]) {
-    const int64_t b = blockIdx.x;
-    const int n = a.n, m = a.n_target, S = a.stride;
-    const float kappa = a.kappa;
-    float g = 0.f, r = 0.f;
-    if (lane < n) {
-        const float th = s_pred[lane], tau = s_tau[lane];
-        for (int j = wave; j < m; j += 4) {
-            float gt, rt;
-            quantile_huber_term(s_t[j] - th, tau, kappa, gt, rt);
-            g += gt;
-            r += rt;
-        }
-    }
-    s_g[wave][lane] = g;
-    s_r[wave][lane] = r;
-    __syncthreads();
-    const float wgt = (a.is_weights ? a.is_weights[b] : 1.f) / (float)a.batch;
-    if (wave == 0) {
-        const float gs = combine4(s_g, lane), rs = combine4(s_r, lane);
-        s_d[lane] = lane < n ? -(wgt / (float)m * gs) : 0.f;    // d loss / d theta(lane, act)
-        const float loss_b = wave_sum(lane < n ? rs : 0.f) / (float)m;
-        if (lane == 0) {
-            a.loss_rows[b] = wgt * loss_b;
-            a.priorities[b] = fminf(fmaxf(loss_b, 1e-6f), 1e6f);
-        }
-    }
-    __syncthreads();
-    float* dl = a.dtheta + b * n * S;
-    for (int o = threadIdx.x; o < n * S; o += 256) {            // row o / S (a fraction), column o % S (an action or padding)
-        const int i = o / S;
-        dl[o] = o - i * S == act ? s_d[i] : 0.f;
-    }
-    if (a.state && b == 0 && threadIdx.x == 0) a.state[1] += a.advance;    // the update's passes have drawn
-}
-
 // One workgroup per sample.  Q phase: wave 0, lane = action, the N' rows of the selecting net read coalesced; meanwhile wave 1
 // stages the taken action's predicted quantiles and their fractions.  Then wave 0 stages T_j (lane = j).  N x N' phase: lane i =
 // predicted fraction i in every wave, the j loop dealt to the waves (j = wave, wave + 4, ...: every lane reads the same T_j, a
@@ -199,14 +141,11 @@ __global__ __launch_bounds__(256) void loss_kernel(const IqnLossArgs a) {
         const float* sel = (a.pol_next ? a.pol_next : a.tgt_next) + b * m * S;
         s_q[lane] = q_of_lane(sel, lane, A, m, S);
     } else if (wave == 1) {
-        s_pred[lane] = lane < n ? a.pred[(b * n + lane) * S + act] : 0.f;
-        s_tau[lane] = lane < n ? a.tau_pred[b * n + lane] : 0.f;
+        stage_taken(a, lane, act, s_pred, s_tau);
     }
     __syncthreads();
     if (wave == 0) {
-        const int a_next = first_max(s_q, A);
-        const float keep = a.terminals[b] ? 0.f : 1.f;
-        s_t[lane] = lane < m ? a.returns[b] + keep * (a.gamma_n * a.tgt_next[(b * m + lane) * S + a_next]) : 0.f;
+        stage_targets(a, lane, first_max(s_q, A), s_t);
     }
     __syncthreads();
     loss_tail(a, lane, wave, act, s_t, s_pred, s_tau, s_d, s_g, s_r);
@@ -237,8 +176,7 @@ __global__ __launch_bounds__(256) void mloss_kernel(const MiqnLossArgs a) {
     if (wave == 0) {
         s_q[lane] = q_of_lane(nxt, lane, A, m, S);
     } else if (wave == 1) {
-        s_pred[lane] = lane < n ? a.pred[(b * n + lane) * S + act] : 0.f;
-        s_tau[lane] = lane < n ? a.tau_pred[b * n + lane] : 0.f;
+        stage_taken(a, lane, act, s_pred, s_tau);
     } else if (wave == 2) {
         s_qc[lane] = q_of_lane(a.pol_next + b * m * S, lane, A, m, S);
     }
@@ -274,14 +212,6 @@ __global__ __launch_bounds__(256) void mloss_kernel(const MiqnLossArgs a) {
 }
 
 inline unsigned grid_for(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-bool theta_sizes_ok(int64_t batch, int n_actions, int fractions, int stride) {
-    return batch >= 1 && batch <= 0x7fffffffLL && n_actions >= 1 && n_actions <= 64 && fractions >= 1 &&
-           fractions <= ARL_IQN_MAX_FRACTIONS && stride >= n_actions && (stride & 3) == 0 && stride <= (1 << 20);
-}
-
-const char* const THETA_SIZES = "need 1 <= batch < 2^31, 1 <= n_actions <= 64, 1 <= fractions <= 64, "
-                                "n_actions <= a_stride <= 2^20 and a_stride % 4 == 0";
 
 bool merge_sizes_ok(int64_t batch, int r, int f) {
     return batch >= 1 && batch <= 0x7fffffffLL && r >= 1 && r <= ARL_IQN_MAX_FRACTIONS && f >= 4 && (f & 3) == 0 &&
@@ -338,29 +268,6 @@ extern "C" int arl_iqn_act(const float* theta, const int32_t* override_or_null, 
     hipLaunchKernelGGL(act_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, (hipStream_t)stream, theta,
                        override_or_null, batch, n_actions, k, a_stride, onehot, greedy_or_null, state_or_null, advance);
     return arl::check_launch("iqn act_kernel");
-}
-
-// The checks and fields that arl_iqn_loss and arl_miqn_loss share, in the order both state them; `fn` names the entry
-// point in the message.  ptrs_ok: every mandatory pointer of the caller is non-null.
-static int fill_iqn_loss(IqnLossArgs& a, const char* fn, bool ptrs_ok, const float* pred, const float* tau_pred,
-                         const float* tgt_next, const uint8_t* actions, const float* returns, const uint8_t* terminals,
-                         const float* is_weights_or_null, int64_t batch, int32_t n_actions, int32_t n, int32_t n_target,
-                         int32_t a_stride, float gamma_n, float kappa, float* dtheta, float* loss_rows,
-                         float* priorities, int64_t* state_or_null, int64_t advance) {
-    const char* msg = nullptr;
-    if (!ptrs_ok) msg = "null pointer";
-    else if (!(theta_sizes_ok(batch, n_actions, n, a_stride) && theta_sizes_ok(batch, n_actions, n_target, a_stride)))
-        msg = THETA_SIZES;
-    else if (!(kappa >= 0.f && kappa <= 3.0e38f)) msg = "kappa must be finite and >= 0";
-    if (msg) {
-        arl::set_error("%s: %s", fn, msg);
-        return ARL_E_ARG;
-    }
-    a.pred = pred; a.tau_pred = tau_pred; a.tgt_next = tgt_next; a.actions = actions; a.returns = returns;
-    a.terminals = terminals; a.is_weights = is_weights_or_null; a.dtheta = dtheta; a.loss_rows = loss_rows;
-    a.priorities = priorities; a.state = state_or_null; a.advance = advance; a.batch = batch; a.n_actions = n_actions;
-    a.n = n; a.n_target = n_target; a.stride = a_stride; a.gamma_n = gamma_n; a.kappa = kappa;
-    return 0;
 }
 
 extern "C" int arl_iqn_loss(const float* pred, const float* tau_pred, const float* tgt_next,

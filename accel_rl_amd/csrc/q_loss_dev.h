@@ -1,12 +1,16 @@
-// What the value-based loss and action kernels of csrc/dqn.hip and csrc/iqn.hip share: the wave butterflies, the first
-// maximum over a staged row of Q values, one term of the pairwise quantile-Huber loss, the fixed-order combine of the four
-// waves' partial sums, and the epsilon-greedy serve tail of the wave-per-sample action kernels.  Internal; every
+// What the value-based loss and action kernels of csrc/dqn.hip, csrc/iqn.hip and csrc/fqf.hip share: the wave butterflies,
+// the first maximum over a staged row of Q values, one term of the pairwise quantile-Huber loss, the fixed-order combine of
+// the four waves' partial sums, the epsilon-greedy serve tail of the wave-per-sample action kernels, and -- for the kernels
+// whose quantiles are strided by a_stride (iqn.hip, fqf.hip) -- the argument record, its host-side checks, the staging of
+// the taken action's quantiles and of the targets T_j, and everything after them (loss_tail).  Internal; every device
 // function is inlined into its callers, which are compiled with -ffp-contract=off: the operations and their order are
 // part of the kernels' stated results (include/accel_rl_hip.h) -- do not re-associate them.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "arl_common.h"
 
 namespace arlq {
 
@@ -61,6 +65,116 @@ __device__ __forceinline__ void serve_wave(int g, int64_t b, int lane, int n_act
     if (override_or_null && override_or_null[b] >= 0) act = override_or_null[b];
     if (lane < n_actions) onehot[b * n_actions + lane] = lane == act ? 1.f : 0.f;
     if (lane == 0 && greedy) greedy[b] = (uint8_t)g;
+}
+
+// Arguments of the loss kernels whose quantiles are strided by a_stride (arl_iqn_loss; arl_miqn_loss and arl_fqf_loss
+// extend it).
+struct IqnLossArgs {
+    const float* pred;              // online net on obs                  [B][N][S]
+    const float* tau_pred;          // its fractions                      [B][N]
+    const float* tgt_next;          // target net on next_obs             [B][N'][S]
+    const float* pol_next;          // online net on next_obs (double DQN) or null
+    const uint8_t* actions;         // [B]
+    const float* returns;           // [B] n-step discounted return
+    const uint8_t* terminals;       // [B]
+    const float* is_weights;        // [B] or null
+    float* dtheta;                  // [B][N][S]
+    float* loss_rows;               // [B] per-sample (weighted) loss / B
+    float* priorities;              // [B] clip(unweighted loss, 1e-6, 1e6)
+    int64_t* state;                 // (seed, counter) or null
+    int64_t advance;
+    int64_t batch;
+    int n_actions, n, n_target, stride;
+    float gamma_n, kappa;           // kappa == 0: plain quantile regression
+};
+
+// Second half of loss_kernel, mloss_kernel (csrc/iqn.hip) and fqf_loss_kernel (csrc/fqf.hip), entered by all 256 threads
+// once s_t (the targets T_j), s_pred and s_tau (the taken action's predicted quantiles and their fractions) are staged and
+// the barrier is passed: the N x N' phase, the four-way combine, loss and priority, the dtheta write and the counter
+// advance.
+__device__ __forceinline__ void loss_tail(const IqnLossArgs& a, int lane, int wave, int act, const float* s_t,
+                                          const float* s_pred, const float* s_tau, float* s_d, float (*s_g)[64],
+                                          float (*s_r)[64]) {
+    const int64_t b = blockIdx.x;
+    const int n = a.n, m = a.n_target, S = a.stride;
+    const float kappa = a.kappa;
+    float g = 0.f, r = 0.f;
+    if (lane < n) {
+        const float th = s_pred[lane], tau = s_tau[lane];
+        for (int j = wave; j < m; j += 4) {
+            float gt, rt;
+            quantile_huber_term(s_t[j] - th, tau, kappa, gt, rt);
+            g += gt;
+            r += rt;
+        }
+    }
+    s_g[wave][lane] = g;
+    s_r[wave][lane] = r;
+    __syncthreads();
+    const float wgt = (a.is_weights ? a.is_weights[b] : 1.f) / (float)a.batch;
+    if (wave == 0) {
+        const float gs = combine4(s_g, lane), rs = combine4(s_r, lane);
+        s_d[lane] = lane < n ? -(wgt / (float)m * gs) : 0.f;    // d loss / d theta(lane, act)
+        const float loss_b = wave_sum(lane < n ? rs : 0.f) / (float)m;
+        if (lane == 0) {
+            a.loss_rows[b] = wgt * loss_b;
+            a.priorities[b] = fminf(fmaxf(loss_b, 1e-6f), 1e6f);
+        }
+    }
+    __syncthreads();
+    float* dl = a.dtheta + b * n * S;
+    for (int o = threadIdx.x; o < n * S; o += 256) {            // row o / S (a fraction), column o % S (an action or padding)
+        const int i = o / S;
+        dl[o] = o - i * S == act ? s_d[i] : 0.f;
+    }
+    if (a.state && b == 0 && threadIdx.x == 0) a.state[1] += a.advance;    // the update's passes have drawn
+}
+
+// wave 1 of the three loss kernels: the taken action's predicted quantiles and their fractions, lane = predicted fraction
+__device__ __forceinline__ void stage_taken(const IqnLossArgs& a, int lane, int act, float* s_pred, float* s_tau) {
+    const int64_t b = blockIdx.x;
+    const int n = a.n, S = a.stride;
+    s_pred[lane] = lane < n ? a.pred[(b * n + lane) * S + act] : 0.f;
+    s_tau[lane] = lane < n ? a.tau_pred[b * n + lane] : 0.f;
+}
+
+// wave 0 of loss_kernel and fqf_loss_kernel once a* is known: T_j = returns_b + keep * (gamma_n * theta_tgt(j, a*)), lane = j
+__device__ __forceinline__ void stage_targets(const IqnLossArgs& a, int lane, int a_next, float* s_t) {
+    const int64_t b = blockIdx.x;
+    const int m = a.n_target, S = a.stride;
+    const float keep = a.terminals[b] ? 0.f : 1.f;
+    s_t[lane] = lane < m ? a.returns[b] + keep * (a.gamma_n * a.tgt_next[(b * m + lane) * S + a_next]) : 0.f;
+}
+
+inline bool theta_sizes_ok(int64_t batch, int n_actions, int fractions, int stride) {
+    return batch >= 1 && batch <= 0x7fffffffLL && n_actions >= 1 && n_actions <= 64 && fractions >= 1 &&
+           fractions <= ARL_IQN_MAX_FRACTIONS && stride >= n_actions && (stride & 3) == 0 && stride <= (1 << 20);
+}
+
+const char* const THETA_SIZES = "need 1 <= batch < 2^31, 1 <= n_actions <= 64, 1 <= fractions <= 64, "
+                                "n_actions <= a_stride <= 2^20 and a_stride % 4 == 0";
+
+// The checks and fields that arl_iqn_loss and arl_miqn_loss share, in the order both state them; `fn` names the entry
+// point in the message.  ptrs_ok: every mandatory pointer of the caller is non-null.
+inline int fill_iqn_loss(IqnLossArgs& a, const char* fn, bool ptrs_ok, const float* pred, const float* tau_pred,
+                         const float* tgt_next, const uint8_t* actions, const float* returns, const uint8_t* terminals,
+                         const float* is_weights_or_null, int64_t batch, int32_t n_actions, int32_t n, int32_t n_target,
+                         int32_t a_stride, float gamma_n, float kappa, float* dtheta, float* loss_rows,
+                         float* priorities, int64_t* state_or_null, int64_t advance) {
+    const char* msg = nullptr;
+    if (!ptrs_ok) msg = "null pointer";
+    else if (!(theta_sizes_ok(batch, n_actions, n, a_stride) && theta_sizes_ok(batch, n_actions, n_target, a_stride)))
+        msg = THETA_SIZES;
+    else if (!(kappa >= 0.f && kappa <= 3.0e38f)) msg = "kappa must be finite and >= 0";
+    if (msg) {
+        arl::set_error("%s: %s", fn, msg);
+        return ARL_E_ARG;
+    }
+    a.pred = pred; a.tau_pred = tau_pred; a.tgt_next = tgt_next; a.actions = actions; a.returns = returns;
+    a.terminals = terminals; a.is_weights = is_weights_or_null; a.dtheta = dtheta; a.loss_rows = loss_rows;
+    a.priorities = priorities; a.state = state_or_null; a.advance = advance; a.batch = batch; a.n_actions = n_actions;
+    a.n = n; a.n_target = n_target; a.stride = a_stride; a.gamma_n = gamma_n; a.kappa = kappa;
+    return 0;
 }
 
 }  // namespace arlq

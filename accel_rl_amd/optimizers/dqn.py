@@ -121,3 +121,65 @@ class DqnOptimizer(BaseOptimizer):
     @property
     def parallelism_tag(self):
         return "single"
+
+
+class FqfOptimizer(DqnOptimizer):
+    """DqnOptimizer for a policy whose flat bucket ends in a fraction-proposal layer (AtariFqfPolicy.frac_offset): the
+    bucket is updated as two ranges, each with its own ArlOptState, slots, step count and norm log.  [0, frac_offset)
+    takes exactly DqnOptimizer's update; the fraction layer takes one arl_opt_step without clipping at its own
+    learning_rate / update_method / update_method_args (fraction_args; defaults: the FQF paper's RMSprop, learning rate
+    2.5e-9, rho 0.95, epsilon 1e-5).  Both updates sit inside the captured graph."""
+
+    def __init__(self, learning_rate, update_method, update_method_args=None, grad_norm_clip=None,
+                 scale_conv_grads=False, use_graph=True, fraction_args=None):
+        super().__init__(learning_rate, update_method, update_method_args=update_method_args,
+                         grad_norm_clip=grad_norm_clip, scale_conv_grads=scale_conv_grads, use_graph=use_graph)
+        from accel_rl_amd.optimizers import update_methods
+        frac = dict(learning_rate=2.5e-9, update_method=update_methods.rmsprop, update_method_args=None)
+        unknown = set(fraction_args or ()) - set(frac)
+        if unknown:
+            raise TypeError("unexpected fraction_args: %s" % sorted(unknown))
+        frac.update(fraction_args or dict())
+        self._frac_learning_rate, self._frac_method = frac["learning_rate"], frac["update_method"]
+        args = frac["update_method_args"]
+        if args is None:
+            args = dict(rho=0.95, epsilon=1e-5) if self._frac_method.name == "rmsprop" else dict()
+        self._frac_args = self._frac_method.resolve(**args)
+
+    def _setup_bucket(self, target, lr_mult, givens=None):
+        from accel_rl_amd import _lib
+        off = getattr(target, "frac_offset", None)
+        if off is None:
+            raise TypeError("FqfOptimizer updates a policy with a fraction layer (AtariFqfPolicy), got %s" %
+                            type(target).__name__)
+        super()._setup_bucket(target, lr_mult, givens)
+        n = target.flat_params.numel() - off
+        assert 0 < off and off % 4 == 0 and n > 0
+        self._frac_offset = off
+        self._opt_state.n_params = off                  # the main range: everything before the fraction layer
+        dev = target.device
+        self._frac_slot0 = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._frac_slot1 = torch.zeros(n, dtype=torch.float32, device=dev) if self._frac_method.name == "adam" else None
+        self._frac_step_count = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._frac_partials = torch.zeros(_lib.OPT_PARTIALS, dtype=torch.float64, device=dev)
+        self._frac_norm_log = torch.zeros(self._norm_log.numel(), dtype=torch.float32, device=dev)
+        st = _lib.ArlOptState()
+        st.n_params = n
+        st.params, st.grads = target.flat_params.data_ptr() + 4 * off, target.flat_grads.data_ptr() + 4 * off
+        st.slot0 = self._frac_slot0.data_ptr()
+        st.slot1 = self._frac_slot1.data_ptr() if self._frac_slot1 is not None else None
+        st.step_count, st.lr_mult = self._frac_step_count.data_ptr(), self._lr_mult.data_ptr()
+        st.partials, st.grad_norm_log = self._frac_partials.data_ptr(), self._frac_norm_log.data_ptr()
+        st.norm_log_len = 1                             # one update per call (_set_updates_per_call(1))
+        self._frac_state = st
+        a = self._frac_args
+        if self._frac_method.name == "adam":
+            self._frac_kernel_args = (a["beta1"], a["beta2"], a["epsilon"])
+        else:
+            self._frac_kernel_args = (a["rho"], 0.0, a["epsilon"])
+
+    def _apply_update(self, avg_factor=1.0):
+        from accel_rl_amd import _lib
+        super()._apply_update(avg_factor)
+        b1, b2, eps = self._frac_kernel_args
+        _lib.opt_step(self._frac_state, self._frac_method.kernel_id, self._frac_learning_rate, avg_factor, 0.0, b1, b2, eps)

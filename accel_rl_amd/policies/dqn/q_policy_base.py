@@ -301,7 +301,7 @@ class QPolicyBase(AtariCnnPolicy):
         where the weight-gradient kernel did not carry the bias gradient along."""
         ones = self._buffer(("ones4", rows), (rows, 4))
         ones.fill_(1.)
-        db4 = self._buffer(("db4", rows), (dout.shape[1], 4))
+        db4 = self._buffer(("db4", rows, dout.shape[1]), (dout.shape[1], 4))
         _lib.conv2d_bwd_weight(dout, ones, db4, self._ones_geom(rows, dout.shape[1]), self._conv_ws)
         self.grads[k + 1].copy_(db4[:, 0])
 

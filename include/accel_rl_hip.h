@@ -933,6 +933,73 @@ int arl_miqn_loss(const float* pred, const float* tau_pred, const float* tgt_nex
                   int32_t a_stride, float gamma_n, float kappa, float tau_e, float alpha, float l0, float* dtheta,
                   float* loss_rows, float* priorities, int64_t* state_or_null, int64_t advance, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Fully parameterized quantile functions (FQF)
+ * ------------------------------------------------------------------------- */
+
+/* FQF (Yang et al. 2019, "Fully Parameterized Quantile Function for Distributional RL"; the reference has none): the
+ * implicit quantile network above, with the fractions neither fixed nor drawn but proposed per state by one dense layer
+ * on the conv features (N logits per sample) and trained to minimise the 1-Wasserstein distance to the network's own
+ * quantile function (the paper's Algorithm 1: ONE set of fractions per sample, used for every pass of that sample).
+ *   logits, dlogits f32[batch][n_stride], n_stride % 4 == 0, n_stride >= N; the padding columns of logits are ignored
+ *   theta f32[batch][N][a_stride] as above; tau f32[batch][N + 1]; tau_hat, q, logq f32[batch][N]; 1 <= N <= 64
+ * The three entry points below refuse with ARL_E_ARG (-1), before any HIP call and with no output written: a NULL
+ * mandatory pointer, a size below 1, more than ARL_IQN_MAX_FRACTIONS fractions, more than 64 actions, a_stride % 4 != 0,
+ * a_stride < n_actions or > 2^20, n_stride % 4 != 0, n_stride < N or > 2^20, batch or batch x (N + 1) above 2^31 - 1,
+ * kappa or ent_coef negative or not finite.  logits / dlogits -- the operands the dense kernels read and write as
+ * vectors -- not 16-byte aligned: ARL_E_ALIGN.  Plain fp32 (expf / logf of the device library), no atomics, no
+ * generator: deterministic.
+ *
+ * Fractions of one sample from its N logits l_k (one wave per sample, lane = k):
+ *   v = max_k l_k;  c_k = l_k - v;  e_k = expf(c_k);  s = sum_k e_k
+ *       (v and s: butterflies over the 64 lanes, lane ^ 32, ^ 16, ... ^ 1; lanes >= N add 0 and take no part in the maximum)
+ *   q_k = e_k / s;  logq_k = c_k - logf(s)                       (finite where q_k underflows to 0)
+ *   tau_0 = 0;  tau_{i+1} = min(tau_i + q_i, 1), i = 0 .. N - 2, SEQUENTIALLY with i ascending (every lane walks the
+ *       same chain);  tau_N = 1 exactly
+ *   tau_hat_i = 0.5 (tau_i + tau_{i+1}), i = 0 .. N - 1;  tau_mid = (tau_1 .. tau_{N-1}), compact f32[batch][N - 1]
+ *   H = 0 - sum_k q_k logq_k                                     (the same butterfly)
+ * so tau is non-decreasing, inside [0, 1], and tau_i <= tau_hat_i <= tau_{i+1}.  N == 1: q = 1, logq = 0, H = 0,
+ * tau = (0, 1), tau_hat = 0.5, and tau_mid is not written.  tau and tau_hat are mandatory; tau_mid, q, logq, entropy
+ * (what serving does not need) may be NULL.                                                                        */
+int arl_fqf_fractions(const float* logits, int64_t batch, int32_t n, int32_t n_stride, float* tau, float* tau_hat,
+                      float* tau_mid_or_null, float* q_or_null, float* logq_or_null, float* entropy_or_null,
+                      void* stream);
+
+/* Action serving: arl_iqn_act with the probability-weighted mean Q_a = sum_k (tau_{k+1} - tau_k) * theta(k, a) in fp32, k
+ * ascending, the sum starts at 0 (a zero weight -- repeated fractions -- contributes an exact 0); first maximum,
+ * override, the one-hot row and `greedy` exactly as arl_iqn_act.  Nothing is drawn: there is no state to advance.
+ *   theta f32[batch][K][a_stride] (the net at tau_hat); tau f32[batch][K + 1]                                       */
+int arl_fqf_act(const float* theta, const float* tau, const int32_t* override_or_null, int64_t batch,
+                int32_t n_actions, int32_t k, int32_t a_stride, float* onehot, uint8_t* greedy_or_null, void* stream);
+
+/* Quantile-Huber loss at the proposed fractions and the fraction loss's gradient, in one launch.  pred
+ * f32[batch][N][a_stride]: the online net on obs at tau_hat; pred_mid f32[batch][N - 1][a_stride]: the online net on obs at
+ * tau_1 .. tau_{N-1} (NULL allowed when N == 1: never read); tgt_next, pol_next_or_null f32[batch][N][a_stride]: the
+ * target / online net on next_obs at the SAME tau_hat; tau, tau_hat, q, logq, entropy: arl_fqf_fractions' outputs.
+ * Per sample b, w_b = (is_weight_b or 1) / batch, w_j = tau_{j+1} - tau_j:
+ *   a*     = first maximum over a of sum_j w_j * sel(j, a), j ascending, the sum starts at 0 (as arl_fqf_act);
+ *            sel = pol_next if given (double DQN), else tgt_next
+ *   T_j    = returns_b + keep * (gamma_n * theta_tgt(j, a*))
+ * and from T_j on everything is arl_iqn_loss with tau_pred = tau_hat and N' = N -- the same device function: u_ij,
+ * rho_ij, dtheta, loss_rows, priorities, their summation orders, the kappa == 0 form, the actions_b >= n_actions rule.
+ * With equal inputs and an equal a*, dtheta, loss_rows and priorities equal arl_iqn_loss's bit for bit.
+ * Fraction loss (Proposition 1 of the paper; it sends no gradient into pred or pred_mid), with theta(.) the taken
+ * action's column:
+ *   g_i      = (2 * pred_mid(i) - pred(i)) - pred(i - 1),  i = 1 .. N - 1                (= d W1 / d tau_i)
+ *   G        = sum_{i=1}^{N-1} g_i * tau_i,  i ascending, the sum starts at 0
+ *   S_k      = sum_{i=k+1}^{N-1} g_i,  i ascending, the sum starts at 0                  (S_{N-1} = 0)
+ *   dlogits_k = w_b * (q_k * (S_k - G) + ent_coef * (q_k * (logq_k + H))),  k = 0 .. N - 1   (minimises W1 - ent_coef H)
+ *   frac_rows[b] = w_b * G
+ * frac_rows is a surrogate whose gradient w.r.t. the logits is the fraction loss's; its VALUE is not W1.  Columns
+ * N .. n_stride - 1 of dlogits are written as exact zeros; N == 1 gives all-zero dlogits and frac_rows = 0.  One 256-thread
+ * workgroup per sample: waves 0, 1, 3 as arl_iqn_loss, wave 2 (lane = k) takes the fraction part.                  */
+int arl_fqf_loss(const float* pred, const float* pred_mid_or_null, const float* tau, const float* tau_hat,
+                 const float* q, const float* logq, const float* entropy, const float* tgt_next,
+                 const float* pol_next_or_null, const uint8_t* actions, const float* returns, const uint8_t* terminals,
+                 const float* is_weights_or_null, int64_t batch, int32_t n_actions, int32_t n, int32_t a_stride,
+                 int32_t n_stride, float gamma_n, float kappa, float ent_coef, float* dtheta, float* loss_rows,
+                 float* priorities, float* dlogits, float* frac_rows, void* stream);
+
 /* Plain DQN action serving: greedy action = first maximum of the Q row (T.argmax), override as
  * above, one-hot row out.  Replaces AtariDqnPolicy.get_actions / actions_sym,
  * accel_rl/policies/dqn/atari_dqn_policy.py:61-63,76-79,118-130.
