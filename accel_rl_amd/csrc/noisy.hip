@@ -263,11 +263,13 @@ extern "C" int arl_noisy_noise(const int64_t* state, const arl_noisy_layer* laye
     for (int l = 0; l < n_layers; ++l) {
         const arl_noisy_layer& L = layers[l];
         ARL_REQUIRE(L.fein && L.feout && (!L.x || L.xs), ARL_E_ARG, "null pointer in a layer");
-        ARL_REQUIRE(L.fan_in > 0 && L.units > 0 && L.out_stride >= L.units && L.layer >= 0, ARL_E_ARG,
-                    "layer sizes");
+        ARL_REQUIRE(L.fan_in > 0 && L.units > 0 && L.out_stride >= L.units && L.layer >= 0 && L.layer < (1 << 30),
+                    ARL_E_ARG, "layer sizes / layer index");
         ARL_REQUIRE(L.fan_in % 4 == 0 && L.out_stride % 4 == 0, ARL_E_RANGE, "fan_in / out_stride not multiples of 4");
         ARL_REQUIRE(arl::aligned16(L.fein) && arl::aligned16(L.feout) && (!L.x || (arl::aligned16(L.x) &&
                     arl::aligned16(L.xs))), ARL_E_ALIGN, "16-byte alignment");
+        ARL_REQUIRE(rows <= ((int64_t)1 << 40) / L.fan_in && rows <= ((int64_t)1 << 40) / L.out_stride, ARL_E_RANGE,
+                    "rows x fan_in / out_stride too large");
         for (int which = 0; which < 2; ++which) {
             NoiseSeg& g = a.seg[a.n_seg++];
             g.f = which ? L.feout : L.fein;

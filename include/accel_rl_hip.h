@@ -1263,7 +1263,7 @@ typedef struct arl_noisy_layer {
     int32_t fan_in;             /* multiple of 4                                                                    */
     int32_t units;              /* width of e_out                                                                   */
     int32_t out_stride;         /* stored columns of the layer's output: multiple of 4, >= units                    */
-    int32_t layer;              /* the generator's layer index                                                      */
+    int32_t layer;              /* the generator's layer index: 0 <= layer < 2^30 (the stream id is 2 layer + which)  */
 } arl_noisy_layer;
 #define ARL_NOISY_MAX_LAYERS 8
 
@@ -1271,7 +1271,9 @@ typedef struct arl_noisy_layer {
  * seed state[0] and call counter state[1] (int64[2] in device memory -- the policy's noise state; a replayed hipGraph
  * reads the current value), f(e_in), f(e_out) and x * f(e_in) where x is given.  This launch does not advance the
  * counter: a later launch of the same pass does (arl_noisy_dense_combine's state_or_null), so eager and captured runs
- * draw the same sequence.  Replaces the rng.normal draws of noisy_layer.py:83-88,125-139.                          */
+ * draw the same sequence.  Replaces the rng.normal draws of noisy_layer.py:83-88,125-139.
+ * Refused as by arl_noisy_normals and arl_noisy_draws, nothing launched: a layer index < 0 or >= 2^30 (ARL_E_ARG);
+ * rows x fan_in or rows x out_stride above 2^40 (ARL_E_RANGE).                                                      */
 int arl_noisy_noise(const int64_t* state, const arl_noisy_layer* layers, int32_t n_layers, int64_t rows,
                     int32_t rows_per_draw, void* stream);
 
