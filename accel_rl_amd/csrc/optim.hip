@@ -123,7 +123,10 @@ __global__ __launch_bounds__(256) void opt_finish_kernel(arl_opt_state o, int n_
     }
 }
 
-int check_opt(const arl_opt_state* opt, int32_t method) {
+// what every entry point that runs an update requires of its state and its hyper-parameters (arl_corun_job_init comes
+// here through make_opt_seg); nothing is launched before it passes
+int check_opt(const arl_opt_state* opt, int32_t method, float learning_rate, float beta1_or_rho, float beta2,
+              float epsilon) {
     ARL_REQUIRE(opt, ARL_E_ARG, "null state");
     ARL_REQUIRE(opt->params && opt->grads && opt->slot0 && opt->step_count && opt->lr_mult, ARL_E_ARG,
                 "null pointer in state");
@@ -133,14 +136,23 @@ int check_opt(const arl_opt_state* opt, int32_t method) {
     ARL_REQUIRE(!opt->grad_norm_log || opt->norm_log_len > 0, ARL_E_ARG, "norm_log_len <= 0");
     ARL_REQUIRE(arl::aligned16(opt->params) && arl::aligned16(opt->grads) && arl::aligned16(opt->slot0) &&
                     (!opt->slot1 || arl::aligned16(opt->slot1)), ARL_E_ALIGN, "flat buffers must be 16-byte aligned");
+    // (written so that a NaN fails: 1 - beta^t would divide by zero, the square root would see a negative number)
+    if (method == ARL_OPT_ADAM)
+        ARL_REQUIRE(beta1_or_rho >= 0.f && beta1_or_rho < 1.f && beta2 >= 0.f && beta2 < 1.f, ARL_E_RANGE,
+                    "adam: beta1 and beta2 in [0, 1)");
+    else
+        ARL_REQUIRE(beta1_or_rho >= 0.f && beta1_or_rho <= 1.f, ARL_E_RANGE, "rmsprop: rho in [0, 1]");
+    ARL_REQUIRE(epsilon >= 0.f, ARL_E_RANGE, "epsilon negative or NaN");
+    ARL_REQUIRE(learning_rate >= 0.f, ARL_E_RANGE, "learning_rate negative or NaN");
     return 0;
 }
 
 }  // namespace
 
 namespace {
-int check_noclip(const arl_opt_state* opt, int32_t method, int32_t k, const float* step_pp, const double* norm_parts) {
-    int rc = check_opt(opt, method);
+int check_noclip(const arl_opt_state* opt, int32_t method, float learning_rate, float beta1_or_rho, float beta2,
+                 float epsilon, int32_t k, const float* step_pp, const double* norm_parts) {
+    int rc = check_opt(opt, method, learning_rate, beta1_or_rho, beta2, epsilon);
     if (rc) return rc;
     ARL_REQUIRE(step_pp && norm_parts, ARL_E_ARG, "null pointer");
     ARL_REQUIRE(k >= 0 && k < ARL_OPT_NORM_SLOTS, ARL_E_RANGE, "update index outside the call's slots");
@@ -164,7 +176,7 @@ int launch_opt_seg(const OptSeg& c, int blocks, hipStream_t s) {
 int make_opt_seg(OptSeg* c, const arl_opt_state* opt, int32_t method, float learning_rate, float avg_factor,
                  float beta1_or_rho, float beta2, float epsilon, int32_t k, float* step_pp, double* norm_parts,
                  int64_t hole_first, int64_t hole_count, int part, int* blocks) {
-    int rc = check_noclip(opt, method, k, step_pp, norm_parts);
+    int rc = check_noclip(opt, method, learning_rate, beta1_or_rho, beta2, epsilon, k, step_pp, norm_parts);
     if (rc) return rc;
     ARL_REQUIRE(hole_first >= 0 && hole_count >= 0 && hole_first + hole_count <= opt->n_params &&
                     (hole_first & 3) == 0 && (hole_count & 3) == 0, ARL_E_ARG,
@@ -217,6 +229,10 @@ extern "C" int arl_opt_finish_split(const arl_opt_state* opt, int32_t n_updates,
     ARL_REQUIRE(opt && opt->step_count && step_pp && norm_parts, ARL_E_ARG, "null pointer");
     ARL_REQUIRE(n_updates >= 1 && n_updates <= ARL_OPT_NORM_SLOTS, ARL_E_RANGE, "n_updates outside 1 .. ARL_OPT_NORM_SLOTS");
     ARL_REQUIRE(hole_count >= 0 && hole_count <= opt->n_params && (hole_count & 3) == 0, ARL_E_ARG, "hole size");
+    ARL_REQUIRE(!opt->grad_norm_log || opt->norm_log_len > 0, ARL_E_ARG, "norm_log_len <= 0");
+    // update k logs at k % norm_log_len from a workgroup of its own: two updates of one call must not share a word
+    ARL_REQUIRE(!opt->grad_norm_log || n_updates <= opt->norm_log_len, ARL_E_RANGE,
+                "n_updates above norm_log_len: two updates would log to one word");
     int rest, hole;
     arl::opt_split_plan(opt->n_params, hole_count, &rest, &hole);
     hipLaunchKernelGGL(opt_finish_kernel, dim3((unsigned)n_updates), dim3(256), 0, (hipStream_t)stream, *opt,
@@ -227,22 +243,16 @@ extern "C" int arl_opt_finish_split(const arl_opt_state* opt, int32_t n_updates,
 extern "C" int arl_opt_step(const arl_opt_state* opt, int32_t method, float learning_rate,
                             float avg_factor, float clip, float beta1_or_rho, float beta2,
                             float epsilon, void* stream) {
-    ARL_REQUIRE(opt, ARL_E_ARG, "null state");
-    ARL_REQUIRE(opt->params && opt->grads && opt->slot0 && opt->step_count && opt->lr_mult &&
-                    opt->partials, ARL_E_ARG, "null pointer in state");
-    ARL_REQUIRE(method == ARL_OPT_ADAM || method == ARL_OPT_RMSPROP, ARL_E_ARG, "unknown method");
-    ARL_REQUIRE(method != ARL_OPT_ADAM || opt->slot1, ARL_E_ARG, "adam needs slot1");
-    ARL_REQUIRE(opt->n_params > 0, ARL_E_ARG, "n_params <= 0");
-    ARL_REQUIRE(!opt->grad_norm_log || opt->norm_log_len > 0, ARL_E_ARG, "norm_log_len <= 0");
-    ARL_REQUIRE(arl::aligned16(opt->params) && arl::aligned16(opt->grads) && arl::aligned16(opt->slot0) &&
-                    (!opt->slot1 || arl::aligned16(opt->slot1)), ARL_E_ALIGN, "flat buffers must be 16-byte aligned");
+    int rc = check_opt(opt, method, learning_rate, beta1_or_rho, beta2, epsilon);
+    if (rc) return rc;
+    ARL_REQUIRE(opt->partials, ARL_E_ARG, "null pointer in state");
     hipStream_t s = (hipStream_t)stream;
     int64_t nb = ((opt->n_params >> 2) + 255) / 256;
     if (nb < 1) nb = 1;
     if (nb > ARL_OPT_PARTIALS) nb = ARL_OPT_PARTIALS;
     hipLaunchKernelGGL(sumsq_kernel, dim3((unsigned)nb), dim3(256), 0, s, opt->grads, opt->n_params,
                        opt->partials, opt->step_count);
-    int rc = arl::check_launch("sumsq_kernel");
+    rc = arl::check_launch("sumsq_kernel");
     if (rc) return rc;
     const unsigned grid = arl::stream_grid(opt->n_params >> 2, 256);
     if (method == ARL_OPT_ADAM)

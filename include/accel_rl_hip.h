@@ -1185,7 +1185,33 @@ typedef struct arl_opt_state {
  * Replaces avg_grads_from_flat + apply_grad_norm_clip + lasagne update,
  * accel_rl/optimizers/util.py:63-76, sync/sync_ppo_optimizer.py:27-34; update
  * arithmetic as in accel_rl/optimizers/update_methods_stats.py:11-33 (rmsprop)
- * and :55-87 (adam).  clip <= 0 means "no clip" (norm still logged).          */
+ * and :55-87 (adam).  clip <= 0, -0.0 and NaN mean "no clip" (norm still logged).
+ *
+ * The arithmetic, all float32, every operation rounded (the file is built without contraction; tests/optim_ref.py
+ * restates it and tests/test_optim_limits_gpu.py holds the device to it bit for bit):
+ *   lr = learning_rate * lr_mult[0];   norm = avg_factor * (float) sqrt(S), S the float64 sum of grads^2 (fixed order);
+ *   cscale = fminf(fmaxf(norm, 0), clip) / (1e-7f + norm) if clip > 0 (not 1 below the clip: Lasagne's), else 1;
+ *   gg = (g * avg_factor) * cscale;
+ *   adam:    m = b1 m + (1 - b1) gg;  v = b2 v + (1 - b2) (gg gg);  p -= (a_t m) / (sqrtf(v) + eps),
+ *            a_t = (lr sqrtf(1 - powf(b2, t))) / (1 - powf(b1, t));
+ *   rmsprop: acc = rho acc + (1 - rho) (gg gg);  p -= (lr gg) / sqrtf(acc + eps).
+ * A gradient that is not finite gives NaN where IEEE arithmetic gives NaN (with a clip: everywhere, through cscale).
+ *
+ * Limits, checked before anything is launched by EVERY entry point below that takes these arguments
+ * (arl_corun_job_init included):
+ *   ARL_E_ARG    a NULL state; NULL params, grads, slot0, step_count or lr_mult (arl_opt_step: or partials); a method
+ *                other than ARL_OPT_ADAM / ARL_OPT_RMSPROP; adam without slot1; n_params <= 0; a log with
+ *                norm_log_len <= 0;
+ *   ARL_E_ALIGN  params, grads, slot0 or slot1 not 16-byte aligned (a range inside a larger bucket starts at a multiple
+ *                of 4 elements);
+ *   ARL_E_RANGE  adam: beta1 or beta2 outside [0, 1) (1 - beta^t would be 0); rmsprop: rho outside [0, 1]; epsilon or
+ *                learning_rate negative or NaN.
+ *
+ * Lasagne's t is the float32 step_count[0]: the sum-of-squares launch adds 1 and the update reads it.  At 2^24 it stops
+ * advancing (2^24 + 1 is not a float32): every later step sees t = 2^24.  The powers have underflowed to 0 long before
+ * for any beta < 1 - 1e-5, so a_t == lr there and the update is unaffected; only the ring index stops moving.
+ * Ring index of this entry point: the norm of the step that makes t goes to grad_norm_log[((int) t - 1) % norm_log_len].
+ * grad_norm_log may be NULL (nothing else changes).                                                                  */
 int arl_opt_step(const arl_opt_state* opt, int32_t method, float learning_rate,
                  float avg_factor, float clip, float beta1_or_rho, float beta2,
                  float epsilon, void* stream);
@@ -1195,7 +1221,17 @@ int arl_opt_step(const arl_opt_state* opt, int32_t method, float learning_rate,
  * the optimizer (`optimize`, accel_rl/optimizers/single/ppo_optimizer.py:58-75) issues updates k = 0 .. n-1 and
  * then arl_opt_finish(n), which writes grad_norm_log[k % norm_log_len] for all of them and settles step_count.
  *   step_pp    f32[2] zero-initialised (Lasagne's t, ping-pong between consecutive updates)
- *   norm_parts f64[ARL_OPT_NORM_SLOTS][ARL_OPT_NORM_BLOCKS] scratch                                            */
+ *   norm_parts f64[ARL_OPT_NORM_SLOTS][ARL_OPT_NORM_BLOCKS] scratch; update k uses row k only, and every word of the
+ *              row that arl_opt_finish reads is written by the update (it need not be cleared between calls)
+ * Arithmetic and refusals as arl_opt_step with cscale = 1; t = step_pp[k & 1] + 1 (stuck at 2^24 likewise), written
+ * to step_pp[(k + 1) & 1] and step_count.  Also refused: NULL step_pp or norm_parts (ARL_E_ARG); k outside
+ * 0 .. ARL_OPT_NORM_SLOTS - 1 (ARL_E_RANGE) -- norm_parts must hold all ARL_OPT_NORM_SLOTS rows, the library cannot
+ * see its size.
+ * arl_opt_finish: n_updates outside 1 .. ARL_OPT_NORM_SLOTS: ARL_E_RANGE.  Ring index of this path: update k of the
+ * call logs at grad_norm_log[k % norm_log_len] -- by its position in the call, not by t -- each from a workgroup of
+ * its own, so with a log n_updates > norm_log_len is refused (ARL_E_RANGE: two updates would write one word in an
+ * undefined order); without a log any n_updates in range is fine.  It reads step_pp[n_updates & 1] into both words
+ * and step_count, and may be repeated.                                                                              */
 #define ARL_OPT_NORM_SLOTS  64
 #define ARL_OPT_NORM_BLOCKS 2048
 int arl_opt_step_noclip(const arl_opt_state* opt, int32_t method, float learning_rate, float avg_factor,
@@ -1211,7 +1247,11 @@ int arl_opt_finish(const arl_opt_state* opt, int32_t n_updates, float avg_factor
  * (arl_corun_job below; inside the PPO step: the host launch 42.6 -> ~48 us, the step's own update launch
  * 19.9 -> 4.9 us), and the step ends with the update of the small rest.  part 0 = everything but the hole (advances t; hole_count = 0: the
  * plain arl_opt_step_noclip), part 1 = the hole as a launch of its own.  hole_first, hole_count multiples of 4.
- * Per element the arithmetic is arl_opt_step_noclip's; a call that used a hole ends with arl_opt_finish_split.       */
+ * Per element the arithmetic is arl_opt_step_noclip's; a call that used a hole ends with arl_opt_finish_split.
+ * The hole may start at 0, end at the bucket's last float4 or be the whole bucket (part 0 then still updates the last
+ * n_params % 4 elements and advances t).  Refused with ARL_E_ARG besides arl_opt_step_noclip's refusals: hole_first or
+ * hole_count negative or no multiple of 4, a hole past the end of the bucket, part 1 with an empty hole;
+ * arl_opt_finish_split: hole_count negative, above n_params or no multiple of 4.                                     */
 int arl_opt_step_noclip_split(const arl_opt_state* opt, int32_t method, float learning_rate, float avg_factor,
                               float beta1_or_rho, float beta2, float epsilon, int32_t k, float* step_pp,
                               double* norm_parts, int64_t hole_first, int64_t hole_count, int32_t part, void* stream);
@@ -1222,7 +1262,10 @@ int arl_opt_finish_split(const arl_opt_state* opt, int32_t n_updates, float avg_
  * launch's grid gets one extra workgroup per CU (the first of the grid; ARL_CORUN_BLOCKS overrides the count, a tuning
  * aid) that streams the update while the others keep the matrix pipe busy -- and report whether they ran it;
  * arl_corun_job_run runs it as its own launch (what the caller does when no launch took it), before part 0.
- * The job is plain data owned by the caller: nothing is pending inside the library, an abandoned job costs nothing. */
+ * The job is plain data owned by the caller: nothing is pending inside the library, an abandoned job costs nothing.
+ * arl_corun_job_init refuses what part 1 of arl_opt_step_noclip_split refuses (and a NULL job: ARL_E_ARG);
+ * arl_corun_job_run(NULL): ARL_E_ARG.  A hosting launch that runs the part with fewer workgroups than it has norm
+ * slots zero-fills the others.                                                                                       */
 typedef struct arl_corun_job { int64_t opaque[40]; } arl_corun_job;
 int arl_corun_job_init(arl_corun_job* job, const arl_opt_state* opt, int32_t method, float learning_rate,
                        float avg_factor, float beta1_or_rho, float beta2, float epsilon, int32_t k, float* step_pp,
