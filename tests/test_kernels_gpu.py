@@ -86,7 +86,11 @@ def test_nstep_golden_bit_exact(L):
                                  (65, 34), (50, 35), (40, 128), (70, 136), (30, 137), (19, 544), (5, 545),
                                  (3, 1000)])
 def test_scans_vs_oracle_shapes(L, n, t):
-    """Ragged tiles, every kernel variant (LDS tiles of 256/128/64/32/8 envs, direct), both scans."""
+    """Ragged tiles, both scans, both exact promotions.  At these sizes every T <= 17 runs the 64-env LDS tile (the
+    128- and 256-env tiles need more than 65408 / 130816 envs), T = 32 and 34 the 64-env tile streamed by 256 threads,
+    T = 35 the 32-env tile, T = 137 the 8-env tile, every longer T % 4 == 0 -- (40, 128), (70, 136), (19, 544) and the
+    single three-env tile (3, 1000) -- the chunked kernel, and only (5, 545) the direct kernel.  The wide tiles, partial
+    chunks over several tiles and the rest of dispatch()'s routes are in tests/test_batch_limits_gpu.py."""
     rs = np.random.RandomState(n * 1000 + t)
     r = rs.randn(n, t).astype(np.float32)
     v = (rs.randn(n, t) * 2).astype(np.float32)
