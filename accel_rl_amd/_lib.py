@@ -197,6 +197,8 @@ _SIGNATURES = {
     "arl_relu_bwd_bias_parts": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, C.POINTER(ArlFoldItem), _vp]),
     "arl_replay_append": (_i32, [C.POINTER(ArlReplay), _vp, _vp, _vp, _vp, _i32, _i32, _f64, _i32, _vp]),
     "arl_replay_extract": (_i32, [C.POINTER(ArlReplay), _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "arl_replay_extract_shift": (_i32, [C.POINTER(ArlReplay), _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i64, _i64,
+                                        _vp, _vp, _vp, _vp, _vp, _vp]),
     "arl_sumtree_find": (_i32, [_vp, _i32, _vp, _i64, _vp, _vp]),
     "arl_sumtree_add": (_i32, [_vp, _i32, _vp, _vp, _i64, _vp]),
     "arl_sumtree_gather": (_i32, [_vp, _vp, _i64, _f64, _vp, _vp]),
@@ -223,6 +225,7 @@ _SIGNATURES = {
     "arl_fqf_loss": (_i32, [_vp] * 13 + [_i64, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "arl_dqn_act": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "arl_dqn_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "arl_drq_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "arl_mdqn_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "arl_lstm_cell_fwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "arl_lstm_cell_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp]),
@@ -951,6 +954,22 @@ def replay_extract(rb, env_idxs, step_idxs, obs, next_obs, actions, returns, ter
                                      stream_ptr(stream)), "arl_replay_extract")
 
 
+def replay_extract_shift(rb, env_idxs, step_idxs, frame_h, frame_w, pad, m_obs, k_next, seed, call, obs, next_obs,
+                         actions, returns, terminals, stream=None):
+    """replay_extract with DrQ's random shift: obs holds m_obs, next_obs k_next shifted views of every sample, view-major
+    (view v of sample j: row v * batch + j).  pad 0: no shift."""
+    _want(env_idxs, torch.int32, "env_idxs")
+    _want(step_idxs, torch.int32, "step_idxs")
+    batch = env_idxs.numel()
+    stack = rb.n_stack * rb.frame_bytes
+    assert obs.numel() == m_obs * batch * stack and next_obs.numel() == k_next * batch * stack, "obs / next_obs size"
+    assert actions.numel() == returns.numel() == terminals.numel() == batch, "actions / returns / terminals size"
+    _check(load().arl_replay_extract_shift(C.byref(rb), ptr(env_idxs), ptr(step_idxs), batch, frame_h, frame_w, pad,
+                                           m_obs, k_next, int(seed), int(call), ptr(obs), ptr(next_obs), ptr(actions),
+                                           ptr(returns), ptr(terminals), stream_ptr(stream)),
+           "arl_replay_extract_shift")
+
+
 def sumtree_find(tree, levels, uniforms, out, stream=None):
     _want(tree, torch.float64, "tree")
     _want(uniforms, torch.float64, "uniforms")
@@ -1216,6 +1235,20 @@ def dqn_loss(q, tgt_next_q, pol_next_q, actions, returns, terminals, is_weights,
                                ptr(terminals), ptr(is_weights), batch, n_actions, q.numel() // batch, int(dueling),
                                float(gamma_n), 0.0 if delta_clip is None else float(delta_clip), ptr(dq),
                                ptr(loss_rows), ptr(td_abs), stream_ptr(stream)), "arl_dqn_loss")
+
+
+def drq_loss(q, tgt_next_q, pol_next_q, actions, returns, terminals, is_weights, n_actions, gamma_n, delta_clip, m, k,
+             dq, loss_rows, td_abs, dueling=False, stream=None):
+    """DrQ: q / dq hold m, tgt_next_q / pol_next_q k view-major blocks of `batch` rows.  delta_clip None: squared loss."""
+    batch = actions.numel()
+    stride = q.numel() // (m * batch)
+    assert q.numel() == dq.numel() == m * batch * stride and tgt_next_q.numel() == k * batch * stride, "q / dq / tgt size"
+    assert pol_next_q is None or pol_next_q.numel() == tgt_next_q.numel(), "pol_next_q size"
+    assert loss_rows.numel() == td_abs.numel() == batch, "loss_rows / td_abs size"
+    _check(load().arl_drq_loss(ptr(q), ptr(tgt_next_q), ptr(pol_next_q), ptr(actions), ptr(returns), ptr(terminals),
+                               ptr(is_weights), batch, m, k, n_actions, stride, int(dueling), float(gamma_n),
+                               0.0 if delta_clip is None else float(delta_clip), ptr(dq), ptr(loss_rows), ptr(td_abs),
+                               stream_ptr(stream)), "arl_drq_loss")
 
 
 def mdqn_loss(q, tgt_next_q, tgt_cur_q, actions, returns, terminals, is_weights, n_actions, gamma_n, delta_clip, tau_e,

@@ -17,8 +17,9 @@ class DQN(RLAlgorithm):
     def __init__(self, discount=0.99, batch_size=32, min_steps_learn=int(5e4), delta_clip=1,
                  replay_size=int(1e6), training_intensity=8, target_update_steps=int(1e4), reward_horizon=1,
                  OptimizerCls=None, optimizer_args=None, eps_greedy_args=None, double_dqn=False,
-                 dueling_dqn=False, prioritized_replay=False, priority_args=None):
+                 dueling_dqn=False, prioritized_replay=False, priority_args=None, augment_args=None):
         save_args(vars(), underscore=False)
+        self._replay_augment = self._check_augment_args(augment_args)
         opt_args, eps_args, pri_args = self._get_default_sub_args()
         opt_args.update(optimizer_args or dict())
         self.optimizer = (OptimizerCls or DqnOptimizer)(**opt_args)
@@ -33,6 +34,25 @@ class DQN(RLAlgorithm):
             self._priority_args = dict(alpha=pri_args["alpha"], beta_initial=pri_args["beta_initial"],
                                        default_priority=pri_args["default_priority"])
         self.need_extra_obs = False
+
+    _multi_view = False         # DrQ alone averages its loss over several shifted views (algos/dqn/drq.py)
+
+    def _check_augment_args(self, augment_args):
+        """augment_args (not in the reference): None, or dict(pad=4, seed=0) -- random-shift replay (DrQ's augmentation)
+        for any algorithm of the family, one shifted view per observation.  -> the replay buffer's `augment`."""
+        if augment_args is None:
+            return None
+        args = dict(pad=4, seed=0, k_targets=1, m_online=1)
+        unknown = set(augment_args) - set(args)
+        if unknown:
+            raise TypeError("unexpected augment_args: %s" % sorted(unknown))
+        args.update(augment_args)
+        if not (isinstance(args["pad"], (int, np.integer)) and 0 <= args["pad"] <= 64):
+            raise ValueError("augment_args: pad must be an integer in 0 .. 64 (arl_replay_extract_shift)")
+        if (args["k_targets"], args["m_online"]) != (1, 1) and not self._multi_view:
+            raise NotImplementedError("%s trains on one shifted view per observation; k_targets / m_online above 1 are "
+                                      "DrQ's (algos/dqn/drq.py; INTEGRATION.md, section E)" % type(self).__name__)
+        return dict(pad=args["pad"], seed=args["seed"], m_obs=args["m_online"], k_next=args["k_targets"])
 
     def _get_default_sub_args(self):
         """dqn.py:62-86"""
@@ -64,6 +84,8 @@ class DQN(RLAlgorithm):
         replay_args = dict(env_spec=env_spec, size=self.replay_size, reward_horizon=self.reward_horizon,
                            sampling_horizon=horizon, n_environments=sample_size // horizon,
                            discount=self.discount, reward_dtype="float32", device=policy.device)
+        if self._replay_augment is not None:          # (absent: the buffers' own default, today's code path)
+            replay_args["augment"] = self._replay_augment
         if self.prioritized_replay:
             replay_args.update(self._priority_args)
             self.replay_buffer = PrioritizedReplayBuffer(**replay_args)

@@ -4,7 +4,11 @@ Same constructor, `append_data`, `extract_batch`, `extract_observations` as the 
 FrameReplayBuffer; the per-environment Python objects (EnvBuffer) become one struct-of-arrays
 on the device (include/accel_rl_hip.h: arl_replay) written and read by csrc/replay.hip.
 `append_data` takes the sampler's samples buffer as it is (device tensors, env-major), so a
-rollout goes from the sampler to replay memory without leaving HBM."""
+rollout goes from the sampler to replay memory without leaving HBM.
+
+`augment` (not in the reference): DrQ's random shift inside the extraction gather (arl_replay_extract_shift) -- every
+minibatch observation is padded by `pad` pixels with its own border and cropped back at a drawn offset, `m_obs` shifted
+views of obs and `k_next` of next_obs per sample."""
 import numpy as np
 import torch
 
@@ -14,9 +18,10 @@ from accel_rl_amd import _lib
 class FrameReplayBuffer(object):
 
     def __init__(self, env_spec, size, reward_horizon, sampling_horizon, n_environments, discount,
-                 reward_dtype="float32", device="cuda:0", promo=_lib.PROMO_NEP50):
+                 reward_dtype="float32", device="cuda:0", promo=_lib.PROMO_NEP50, augment=None):
         if reward_dtype != "float32":
             raise NotImplementedError("device replay stores float32 rewards (the reference's default)")
+        self._augment = self._check_augment(augment, tuple(env_spec.observation_space.shape)[1:])
         _lib.load()
         sampling_size = sampling_horizon * n_environments                 # frame.py:41-45
         n_chunks = -(-size // sampling_size)
@@ -48,6 +53,29 @@ class FrameReplayBuffer(object):
         self._rb, self._promo = rb, promo
         self.idx = 0                                                      # where the next state is written
         self._idx_host = None
+
+    @staticmethod
+    def _check_augment(augment, frame_shape):
+        """None, or dict(pad=4, seed=0, m_obs=1, k_next=1) completed and checked against arl_replay_extract_shift's
+        limits (before anything touches the device)."""
+        if augment is None:
+            return None
+        aug = dict(pad=4, seed=0, m_obs=1, k_next=1)
+        unknown = set(augment) - set(aug)
+        if unknown:
+            raise TypeError("unexpected augment keys: %s" % sorted(unknown))
+        aug.update(augment)
+        if len(frame_shape) != 2 or frame_shape[1] % 4:
+            raise NotImplementedError("augmented replay shifts 2-D frames whose width is a multiple of 4 (got %s; "
+                                      "INTEGRATION.md, section E)" % (frame_shape,))
+        if not all(isinstance(aug[k], (int, np.integer)) for k in aug):
+            raise TypeError("augment takes integers")
+        if not 0 <= aug["pad"] <= 64:
+            raise ValueError("augment: need 0 <= pad <= 64")
+        if not (1 <= aug["m_obs"] <= 8 and 1 <= aug["k_next"] <= 8):
+            raise ValueError("augment: need 1 <= m_obs, k_next <= 8")
+        aug["call"] = 0                 # advances by 1 per extract_batch: the counter words of the offsets' Philox stream
+        return aug
 
     def append_data(self, samples_data):
         """frame.py:57-60.  samples_data: the sampler's buffer (observations u8[N*T,F,H,W], actions u8,
@@ -84,7 +112,14 @@ class FrameReplayBuffer(object):
             env_idxs, step_idxs = self._upload_idxs(env_idxs, step_idxs)
         b = env_idxs.numel()
         obs, nxt, acts, rets, terms, terms_bool = self._batch_outputs(b)
-        _lib.replay_extract(self._rb, env_idxs, step_idxs, obs, nxt, acts, rets, terms)
+        aug = self._augment
+        if aug is None:
+            _lib.replay_extract(self._rb, env_idxs, step_idxs, obs, nxt, acts, rets, terms)
+        else:           # obs: m_obs, nxt: k_next shifted views of every sample, view-major
+            h, w = self.frame_shape
+            _lib.replay_extract_shift(self._rb, env_idxs, step_idxs, h, w, aug["pad"], aug["m_obs"], aug["k_next"],
+                                      aug["seed"], aug["call"], obs, nxt, acts, rets, terms)
+            aug["call"] += 1
         return obs, nxt, acts, rets, terms_bool
 
     # `reuse_outputs` (set by the DQN algorithms): every batch of one size lands in the SAME device tensors,
@@ -97,10 +132,11 @@ class FrameReplayBuffer(object):
         if self.reuse_outputs and b in cache:
             return cache[b]
         shape = (b, self.num_img_obs) + self.frame_shape
-        # one allocation, obs directly followed by next_obs: the Q policies' online pass over both (double DQN)
-        # then reads the 2b rows in place (policies/dqn/q_policy_base.py: _pair_rows)
-        both = torch.empty((2 * b,) + shape[1:], dtype=torch.uint8, device=self.device)
-        obs, nxt = both[:b], both[b:]
+        m, k = (self._augment["m_obs"], self._augment["k_next"]) if self._augment else (1, 1)
+        # one allocation, obs (m views) directly followed by next_obs (k views): the Q policies' online pass over both
+        # (double DQN) then reads the (m + k) b rows in place (policies/dqn/q_policy_base.py: _pair_rows)
+        both = torch.empty(((m + k) * b,) + shape[1:], dtype=torch.uint8, device=self.device)
+        obs, nxt = both[:m * b], both[m * b:]
         acts = torch.empty(b, dtype=torch.uint8, device=self.device)
         rets = torch.empty(b, dtype=torch.float32, device=self.device)
         terms = torch.empty(b, dtype=torch.uint8, device=self.device)
@@ -112,4 +148,15 @@ class FrameReplayBuffer(object):
         return out
 
     def extract_observations(self, env_idxs, step_idxs):
-        return self.extract_batch(env_idxs, step_idxs)[0]
+        """Never shifted (evaluation and diagnostic reads): with `augment`, the pad = 0 path into tensors of its own."""
+        if self._augment is None:
+            return self.extract_batch(env_idxs, step_idxs)[0]
+        if not isinstance(env_idxs, torch.Tensor):
+            env_idxs, step_idxs = self._upload_idxs(env_idxs, step_idxs)
+        b = env_idxs.numel()
+        both = torch.empty((2 * b, self.num_img_obs) + self.frame_shape, dtype=torch.uint8, device=self.device)
+        acts, terms = (torch.empty(b, dtype=torch.uint8, device=self.device) for _ in range(2))
+        rets = torch.empty(b, dtype=torch.float32, device=self.device)
+        h, w = self.frame_shape
+        _lib.replay_extract_shift(self._rb, env_idxs, step_idxs, h, w, 0, 1, 1, 0, 0, both[:b], both[b:], acts, rets, terms)
+        return both[:b]

@@ -16,6 +16,8 @@
 //                     (policies/dqn/atari_dqn_policy.py:61-63,118-130)
 //   arl_dqn_loss      one-step / n-step Q-learning target (max or double-DQN selection), squared or
 //                     Huber loss, clipped |TD error| priorities, d loss / d Q (algos/dqn/dqn.py:137-172)
+//   arl_drq_loss      DrQ (Kostrikov et al. 2020; not in the reference): arl_dqn_loss with the target averaged over k and
+//                     the loss over m shifted views of the sample, all inside the sample's lane
 //   arl_mdqn_loss     Munchausen DQN (Vieillard et al. 2020; not in the reference): arl_dqn_loss with the soft-max
 //                     bootstrap sum_a pi_a (q_a - tau_e log pi_a) of the target net on next_obs and the bonus
 //                     alpha clip(tau_e log pi(action | obs), l0, 0) of the target net on obs added to the reward; max,
@@ -357,12 +359,14 @@ struct DqnLossArgs {
     float gamma_n, delta_clip;      // delta_clip <= 0: squared loss, unclipped priorities
 };
 
-// Second half of dqn_loss_kernel and mdqn_loss_kernel: from sample b's target y and taken action to the (Huber) loss, its
-// gradient through the dueling merge, and the priority
-__device__ __forceinline__ void dqn_loss_tail(const DqnLossArgs& a, int64_t b, float y, int act) {
+// One TD row, shared by every loss kernel below: from the target y and the taken action to the (Huber) loss of Q row
+// `row` of a.q under the weight w, and its gradient through the dueling merge into row `row` of a.dq.  Returns the
+// weighted loss and the priority (|d|, clipped)
+struct TdTerm { float wloss, p; };
+__device__ __forceinline__ TdTerm dqn_td_row(const DqnLossArgs& a, int64_t row, float y, int act, float w) {
     const int A = a.n_actions, S = a.stride;
     const bool duel = a.dueling != 0;
-    const float* qrow = a.q + b * S;
+    const float* qrow = a.q + row * S;
     const float d = y - q_at(qrow, act, A, duel, duel ? row_mean(qrow, A) : 0.f);
     const float ad = fabsf(d), c = a.delta_clip;
     float loss = 0.5f * (d * d), slope = d;                                // d loss / d d
@@ -370,8 +374,7 @@ __device__ __forceinline__ void dqn_loss_tail(const DqnLossArgs& a, int64_t b, f
         loss = c * (ad - c / 2.f);
         slope = d > 0.f ? c : -c;
     }
-    const float w = (a.is_weights ? a.is_weights[b] : 1.f) / (float)a.batch;
-    float* dq = a.dq + b * S;
+    float* dq = a.dq + row * S;
     const float gq = -(w * slope);                                         // d = y - q, y carries no gradient
     for (int k = 0; k < S; ++k) dq[k] = 0.f;
     if (!duel) {
@@ -381,22 +384,62 @@ __device__ __forceinline__ void dqn_loss_tail(const DqnLossArgs& a, int64_t b, f
         for (int k = 0; k < A; ++k) dq[k] = k == act ? gq - share : -share;
         dq[A] = gq;
     }
-    a.loss_rows[b] = w * loss;
-    a.td_abs[b] = c > 0.f ? fminf(ad, c) : ad;                             // :165
+    return {w * loss, c > 0.f ? fminf(ad, c) : ad};                        // :165
+}
+
+// Second half of dqn_loss_kernel and mdqn_loss_kernel: sample b's row under the weight (is_weight or 1) / batch
+__device__ __forceinline__ void dqn_loss_tail(const DqnLossArgs& a, int64_t b, float y, int act) {
+    const float w = (a.is_weights ? a.is_weights[b] : 1.f) / (float)a.batch;
+    const TdTerm t = dqn_td_row(a, b, y, act, w);
+    a.loss_rows[b] = t.wloss;
+    a.td_abs[b] = t.p;
+}
+
+// dqn.py:146-150 on row `row` of the next-observation blocks: double DQN picks the action with the policy net and values
+// it with the target net
+__device__ __forceinline__ float dqn_next_q(const DqnLossArgs& a, int64_t row) {
+    const int A = a.n_actions, S = a.stride;
+    const bool duel = a.dueling != 0;
+    const float* tgt = a.tgt_next_q + row * S;
+    const int a_next = first_argmax(a.pol_next_q ? a.pol_next_q + row * S : tgt, A, duel);
+    return q_at(tgt, a_next, A, duel, duel ? row_mean(tgt, A) : 0.f);
 }
 
 __global__ __launch_bounds__(256) void dqn_loss_kernel(const DqnLossArgs a) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= a.batch) return;
-    const int A = a.n_actions, S = a.stride;
-    const float* tgt = a.tgt_next_q + b * S;
-    // dqn.py:146-150: double DQN picks the action with the policy net and values it with the target net
-    const bool duel = a.dueling != 0;
-    const int a_next = first_argmax(a.pol_next_q ? a.pol_next_q + b * S : tgt, A, duel);
-    const float next_q = q_at(tgt, a_next, A, duel, duel ? row_mean(tgt, A) : 0.f);
+    const float next_q = dqn_next_q(a, b);
     const float keep = a.terminals[b] ? 0.f : 1.f;
     const float y = a.returns[b] + keep * (a.gamma_n * next_q);            // :152-153
     dqn_loss_tail(a, b, y, a.actions[b]);
+}
+
+// ---- DrQ: dqn_loss_kernel with the target averaged over k shifted views of next_obs and the loss over m shifted views
+// of obs; rows view-major (view v of sample b: row v * batch + b); one lane per sample, every sum inside the lane ----
+struct DrqLossArgs : DqnLossArgs {
+    int k, m;
+};
+
+__global__ __launch_bounds__(256) void drq_loss_kernel(const DrqLossArgs a) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.batch) return;
+    float nbar = dqn_next_q(a, b);
+    if (a.k > 1) {
+        for (int i = 1; i < a.k; ++i) nbar += dqn_next_q(a, (int64_t)i * a.batch + b);
+        nbar = nbar / (float)a.k;
+    }
+    const float keep = a.terminals[b] ? 0.f : 1.f;
+    const float y = a.returns[b] + keep * (a.gamma_n * nbar);
+    const int act = a.actions[b];
+    const float w = ((a.is_weights ? a.is_weights[b] : 1.f) / (float)a.batch) / (float)a.m;
+    TdTerm sum = dqn_td_row(a, b, y, act, w);
+    for (int v = 1; v < a.m; ++v) {
+        const TdTerm t = dqn_td_row(a, (int64_t)v * a.batch + b, y, act, w);
+        sum.wloss += t.wloss;
+        sum.p += t.p;
+    }
+    a.loss_rows[b] = sum.wloss;
+    a.td_abs[b] = sum.p / (float)a.m;
 }
 
 // ---- Munchausen DQN: dqn_loss_kernel with a soft-max bootstrap and the clipped log-policy bonus; one lane per sample ----
@@ -619,6 +662,24 @@ extern "C" int arl_dqn_loss(const float* q, const float* tgt_next_q, const float
     a.pol_next_q = pol_next_q_or_null;
     hipLaunchKernelGGL(dqn_loss_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     return arl::check_launch("dqn_loss_kernel");
+}
+
+extern "C" int arl_drq_loss(const float* q, const float* tgt_next_q, const float* pol_next_q_or_null,
+                            const uint8_t* actions, const float* returns, const uint8_t* terminals,
+                            const float* is_weights_or_null, int64_t batch, int32_t m, int32_t k, int32_t n_actions,
+                            int32_t q_stride, int32_t dueling, float gamma_n, float delta_clip, float* dq,
+                            float* loss_rows, float* td_abs, void* stream) {
+    DrqLossArgs a = {};
+    int rc = fill_dqn_loss(a, __func__, q && tgt_next_q && actions && returns && terminals && dq && loss_rows && td_abs, q,
+                           tgt_next_q, actions, returns, terminals, is_weights_or_null, batch, n_actions, q_stride,
+                           dueling, gamma_n, delta_clip, dq, loss_rows, td_abs);
+    if (rc) return rc;
+    ARL_REQUIRE(k >= 1 && k <= 8 && m >= 1 && m <= 8, ARL_E_RANGE, "need 1 <= k, m <= 8 views");
+    ARL_REQUIRE(m * batch < ((int64_t)1 << 31) && k * batch < ((int64_t)1 << 31), ARL_E_RANGE,
+                "m * batch and k * batch must stay below 2^31");
+    a.pol_next_q = pol_next_q_or_null; a.k = k; a.m = m;
+    hipLaunchKernelGGL(drq_loss_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return arl::check_launch("drq_loss_kernel");
 }
 
 extern "C" int arl_mdqn_loss(const float* q, const float* tgt_next_q, const float* tgt_cur_q, const uint8_t* actions,

@@ -5,6 +5,8 @@
 //   arl_replay_append     FrameReplayBuffer.append_data / EnvBuffer.write_samples
 //                         (accel_rl/algos/dqn/replay_buffers/frame.py:57-60,121-166)
 //   arl_replay_extract    extract_batch / extract_observations            (frame.py:69-90)
+//   arl_replay_extract_shift  the same gather with DrQ's random shift (pad by the border, crop at a drawn offset)
+//                         applied on the way, several shifted views per sample (not in the reference)
 //   arl_sumtree_find      PartedSumTree.find                              (sum_tree.py:88-98)
 //   arl_sumtree_add       PartedSumTree.reconstruct (np.add.at, in input order, :54-57)
 //   arl_sumtree_gather    tree[idxs]                                      (:83,:65)
@@ -14,6 +16,7 @@
 // so a stacked observation is F consecutive slots = one contiguous F*frame_bytes run.
 
 #include "arl_common.h"
+#include "philox_dev.h"
 
 namespace {
 
@@ -104,8 +107,23 @@ struct ExtractArgs {
     int64_t batch;
 };
 
-// grid (batch, 2): one workgroup copies one stacked observation (F * frame_bytes contiguous)
-// and zeroes its leading n_blanks frames (frame.py:81-90)
+// one stacked observation (F * frame_bytes contiguous) with its leading `blanks` frames zeroed (frame.py:81-90)
+__device__ __forceinline__ void copy_stack(uint8_t* dst, const uint8_t* src, int F, int P, int blanks, int tid) {
+    const uint4* s4 = reinterpret_cast<const uint4*>(src);
+    uint4* d4 = reinterpret_cast<uint4*>(dst);
+    const int per_frame = P / 16, total = F * per_frame, zero_upto = blanks * per_frame;
+    for (int q = tid; q < total; q += 256) d4[q] = q < zero_upto ? make_uint4(0, 0, 0, 0) : s4[q];
+}
+
+// action, n-step return and terminal flag of sample j (environment e)
+__device__ __forceinline__ void copy_scalars(const ExtractArgs& a, int64_t j, int e) {
+    const int64_t at = (int64_t)e * a.rb.size + a.step_idxs[j];
+    a.actions[j] = a.rb.acts[at];
+    a.returns[j] = a.rb.returns[at];
+    a.terminals[j] = a.rb.terminals[at];
+}
+
+// grid (batch, 2): one workgroup copies one stacked observation
 __global__ __launch_bounds__(256) void replay_extract_kernel(const ExtractArgs a) {
     const int64_t j = blockIdx.x;
     const int which = blockIdx.y, tid = threadIdx.x;
@@ -116,14 +134,94 @@ __global__ __launch_bounds__(256) void replay_extract_kernel(const ExtractArgs a
     const uint8_t* src = a.rb.frames + ((int64_t)e * ring + i) * P;
     uint8_t* dst = (which ? a.next_obs : a.obs) + j * F * P;
     const int blanks = a.rb.n_blanks[(int64_t)e * ring + i];
-    const uint4* s4 = reinterpret_cast<const uint4*>(src);
-    uint4* d4 = reinterpret_cast<uint4*>(dst);
-    const int per_frame = P / 16, total = F * per_frame, zero_upto = blanks * per_frame;
-    for (int q = tid; q < total; q += 256) d4[q] = q < zero_upto ? make_uint4(0, 0, 0, 0) : s4[q];
-    if (!which && tid == 0) {
-        a.actions[j] = a.rb.acts[(int64_t)e * S + a.step_idxs[j]];
-        a.returns[j] = a.rb.returns[(int64_t)e * S + a.step_idxs[j]];
-        a.terminals[j] = a.rb.terminals[(int64_t)e * S + a.step_idxs[j]];
+    copy_stack(dst, src, F, P, blanks, tid);
+    if (!which && tid == 0) copy_scalars(a, j, e);
+}
+
+// ---- the same gather with a random shift (DrQ): out[f][y][x] = src[f][clamp(y + dy)][clamp(x + dx)] ----
+struct ShiftArgs {
+    ExtractArgs x;
+    int frame_h, frame_w, pad, m_obs;
+    uint32_t seed, call_lo, call_hi;
+};
+
+constexpr int SHIFT_TILE = 16384;          // bytes of one staged source tile (a whole 104 x 80 frame: 8 320)
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+// grid (batch, m_obs + k_next): one workgroup per stacked view.  A shift by dx moves the source run off its 16-byte
+// alignment, so a frame goes through LDS: aligned uint4 loads stage the source rows a tile of output rows needs, every
+// output dword is put together from LDS (two dwords and a byte shift inside the row, four clamped bytes at its ends),
+// and leaves as one lane's uint4 store.  Frames above SHIFT_TILE bytes are staged in tiles of whole rows, a multiple
+// of four of them, so that a tile's output stays a run of whole 16-byte chunks (frame_w % 4 == 0).
+__global__ __launch_bounds__(256) void replay_extract_shift_kernel(const ShiftArgs a) {
+    __shared__ uint4 s_tile[SHIFT_TILE / 16];
+    const int64_t j = blockIdx.x;
+    const int v = blockIdx.y, tid = threadIdx.x;
+    const bool next = v >= a.m_obs;
+    const int S = a.x.rb.size, F = a.x.rb.n_stack, P = a.x.rb.frame_bytes, ring = S + F - 1;
+    const int e = a.x.env_idxs[j];
+    int i = a.x.step_idxs[j];
+    if (next) { i += a.x.rb.reward_horizon; if (i >= S) i -= S; }
+    const uint8_t* src = a.x.rb.frames + ((int64_t)e * ring + i) * P;
+    const int64_t row = (int64_t)(next ? v - a.m_obs : v) * a.x.batch + j;        // view-major
+    uint8_t* dst = (next ? a.x.next_obs : a.x.obs) + row * F * P;
+    const int blanks = a.x.rb.n_blanks[(int64_t)e * ring + i];
+    if (v == 0 && tid == 0) copy_scalars(a.x, j, e);
+    int dx = 0, dy = 0;
+    if (a.pad > 0) {                                    // one offset pair per view, shared by its F frames
+        uint32_t c[4] = {(uint32_t)j, (uint32_t)v, a.call_lo, a.call_hi};
+        arlp::philox4x32_10(c, a.seed, ARL_AUG_PHILOX_STREAM);
+        const uint32_t span = 2u * (uint32_t)a.pad + 1u;
+        dx = (int)(((uint64_t)c[0] * span) >> 32) - a.pad;
+        dy = (int)(((uint64_t)c[1] * span) >> 32) - a.pad;
+    }
+    if (dx == 0 && dy == 0) {                           // (uniform across the workgroup)
+        copy_stack(dst, src, F, P, blanks, tid);
+        return;
+    }
+    const int H = a.frame_h, W = a.frame_w, wd = W >> 2;
+    const int tile_rows = P <= SHIFT_TILE ? H : ((SHIFT_TILE - 32) / W) & ~3;
+    const uint32_t* s32 = reinterpret_cast<const uint32_t*>(s_tile);
+    const uint8_t* s8 = reinterpret_cast<const uint8_t*>(s_tile);
+    for (int f = 0; f < F; ++f) {
+        uint4* d4 = reinterpret_cast<uint4*>(dst + (int64_t)f * P);
+        if (f < blanks) {                               // a blank frame stays all zero under any shift
+            for (int q = tid; q < P / 16; q += 256) d4[q] = make_uint4(0, 0, 0, 0);
+            continue;
+        }
+        const uint8_t* sf = src + (int64_t)f * P;
+        for (int y0 = 0; y0 < H; y0 += tile_rows) {
+            const int y1 = y0 + tile_rows < H ? y0 + tile_rows : H;
+            // output rows y0 .. y1-1 read source rows sy0 .. sy1 (the clamp is monotone): at most y1 - y0 of them
+            const int sy0 = clampi(y0 + dy, 0, H - 1), sy1 = clampi(y1 - 1 + dy, 0, H - 1);
+            const int a0 = (sy0 * W) & ~15, a1 = ((sy1 + 1) * W + 15) & ~15;      // a1 <= P: P % 16 == 0
+            __syncthreads();                            // the tile before this one has been read
+            const uint4* g4 = reinterpret_cast<const uint4*>(sf + a0);
+            for (int q = tid; q < (a1 - a0) >> 4; q += 256) s_tile[q] = g4[q];
+            __syncthreads();
+            for (int q = ((y0 * W) >> 4) + tid; q < (y1 * W) >> 4; q += 256) {
+                uint32_t o[4];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const int d = 4 * q + t;            // output dword of the frame
+                    const int y = d / wd, xd = d - y * wd;
+                    const int rb = clampi(y + dy, 0, H - 1) * W - a0;             // the source row inside the tile (% 4 == 0)
+                    const int sx = 4 * xd + dx;
+                    if (sx >= 0 && sx + 3 < W) {
+                        const int at = (rb + sx) >> 2, sh = 8 * (sx & 3);
+                        const uint32_t lo = s32[at];
+                        o[t] = sh ? (lo >> sh) | (s32[at + 1] << (32 - sh)) : lo; // (sh != 0: the next dword is in the row)
+                    } else {
+                        uint32_t w = 0;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) w |= (uint32_t)s8[rb + clampi(sx + k, 0, W - 1)] << (8 * k);
+                        o[t] = w;
+                    }
+                }
+                d4[q] = make_uint4(o[0], o[1], o[2], o[3]);
+            }
+        }
     }
 }
 
@@ -436,6 +534,33 @@ extern "C" int arl_replay_extract(const arl_replay* rb, const int32_t* env_idxs,
     a.actions = actions; a.returns = returns; a.terminals = terminals; a.batch = batch;
     hipLaunchKernelGGL(replay_extract_kernel, dim3((unsigned)batch, 2), dim3(256), 0, (hipStream_t)stream, a);
     return arl::check_launch("replay_extract_kernel");
+}
+
+extern "C" int arl_replay_extract_shift(const arl_replay* rb, const int32_t* env_idxs, const int32_t* step_idxs,
+                                        int64_t batch, int32_t frame_h, int32_t frame_w, int32_t pad, int32_t m_obs,
+                                        int32_t k_next, int64_t seed, int64_t call, uint8_t* obs, uint8_t* next_obs,
+                                        uint8_t* actions, float* returns, uint8_t* terminals, void* stream) {
+    int rc = check_replay(rb);
+    if (rc) return rc;
+    ARL_REQUIRE(env_idxs && step_idxs && obs && next_obs && actions && returns && terminals, ARL_E_ARG, "null pointer");
+    ARL_REQUIRE(batch >= 1 && batch < ((int64_t)1 << 31), ARL_E_RANGE, "need 1 <= batch < 2^31");
+    ARL_REQUIRE(frame_h > 0 && frame_w > 0 && (int64_t)frame_h * frame_w == rb->frame_bytes, ARL_E_RANGE,
+                "frame_h * frame_w must equal frame_bytes");
+    ARL_REQUIRE(frame_w % 4 == 0, ARL_E_RANGE, "frame_w must be a multiple of 4");
+    ARL_REQUIRE(rb->frame_bytes <= SHIFT_TILE || frame_w <= (SHIFT_TILE - 32) / 4, ARL_E_RANGE,
+                "frames above 16384 bytes need frame_w <= 4088");
+    ARL_REQUIRE(pad >= 0 && pad <= 64, ARL_E_RANGE, "need 0 <= pad <= 64");
+    ARL_REQUIRE(m_obs >= 1 && m_obs <= 8 && k_next >= 1 && k_next <= 8, ARL_E_RANGE, "need 1 <= m_obs, k_next <= 8");
+    ARL_REQUIRE((int64_t)(m_obs + k_next) * batch < ((int64_t)1 << 31), ARL_E_RANGE, "(m_obs + k_next) * batch >= 2^31");
+    ARL_REQUIRE(arl::aligned16(obs) && arl::aligned16(next_obs), ARL_E_ALIGN, "obs buffers must be 16-byte aligned");
+    ShiftArgs a = {};
+    a.x.rb = *rb; a.x.env_idxs = env_idxs; a.x.step_idxs = step_idxs; a.x.obs = obs; a.x.next_obs = next_obs;
+    a.x.actions = actions; a.x.returns = returns; a.x.terminals = terminals; a.x.batch = batch;
+    a.frame_h = frame_h; a.frame_w = frame_w; a.pad = pad; a.m_obs = m_obs;
+    a.seed = (uint32_t)seed; a.call_lo = (uint32_t)call; a.call_hi = (uint32_t)((uint64_t)call >> 32);
+    hipLaunchKernelGGL(replay_extract_shift_kernel, dim3((unsigned)batch, (unsigned)(m_obs + k_next)), dim3(256), 0,
+                       (hipStream_t)stream, a);
+    return arl::check_launch("replay_extract_shift_kernel");
 }
 
 extern "C" int arl_sumtree_find(const double* tree, int32_t levels, const double* uniforms, int64_t n,

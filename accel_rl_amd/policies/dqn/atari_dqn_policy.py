@@ -106,11 +106,14 @@ class AtariDqnPolicy(QPolicyBase):
         pack = self._buffer(("loss_td", b), (2, b))         # one buffer: DqnOptimizer's statistics ring takes both rows at once
         loss_rows, td_abs = pack[0], pack[1]
         launch(dq, loss_rows, td_abs)
+        self._backward_from_dq(dq, x, acts, hids)
+        return loss_rows, td_abs
+
+    def _backward_from_dq(self, dq, x, acts, hids):
         self._head_backward(dq, x, acts, hids)
         if self._shared_last_bias:          # the folds have run: d loss / d (shared scalar) = the sum over the actions
             gb = self.grads[self._k_head + 1]
             gb[:self.n_act] = gb[:self.n_act].sum()
-        return loss_rows, td_abs
 
     def q_loss_and_grads(self, obs, next_obs, actions, returns, terminals, is_weights, gamma_n, delta_clip,
                          double_dqn=False):
@@ -125,6 +128,29 @@ class AtariDqnPolicy(QPolicyBase):
                               delta_clip, dq, loss_rows, td_abs, dueling=self._dueling)
 
             return self._loss_and_backward(x, q, acts, hids, launch)
+
+    def drq_loss_and_grads(self, obs, next_obs, actions, returns, terminals, is_weights, gamma_n, delta_clip, double_dqn,
+                           m, k):
+        """One minibatch of DrQ.build_loss: obs holds m, next_obs k shifted views of each of the B samples, view-major
+        (FrameReplayBuffer(augment=...)).  Forward of the policy net on the m B obs rows (activations kept), of the target
+        net -- and, for double DQN, the policy net -- on the k B next rows (u8 rows handed out adjacent: ONE online pass
+        over the (m + k) B rows in place, _pair_rows), the K/M-averaged (Huber) TD loss of csrc/dqn.hip:arl_drq_loss, and
+        the full backward pass at m B rows into flat_grads.  Returns (loss_rows f32[B] whose sum is the loss, td_abs
+        f32[B]), the two rows of one (2, B) buffer as q_loss_and_grads'.  No host synchronisation and no allocation
+        outside _buffer: it runs inside the captured update graph."""
+        b = actions.numel()
+        if obs.shape[0] != m * b or next_obs.shape[0] != k * b:
+            raise ValueError("drq_loss_and_grads: obs / next_obs must hold m * B = %d / k * B = %d rows (got %d / %d)" %
+                             (m * b, k * b, obs.shape[0], next_obs.shape[0]))
+        with torch.no_grad():
+            x, q, acts, hids, tgt_q, pol_next = self._forward_for_loss(obs, next_obs, double_dqn)
+            dq = self._buffer(("dlogits", m * b), tuple(q.shape))
+            pack = self._buffer(("loss_td", b), (2, b))
+            loss_rows, td_abs = pack[0], pack[1]
+            _lib.drq_loss(q, tgt_q, pol_next, actions, returns, terminals, is_weights, self.n_act, gamma_n, delta_clip,
+                          m, k, dq, loss_rows, td_abs, dueling=self._dueling)
+            self._backward_from_dq(dq, x, acts, hids)
+            return loss_rows, td_abs
 
     def munchausen_loss_and_grads(self, obs, next_obs, actions, returns, terminals, is_weights, gamma_n, delta_clip,
                                   tau_e, alpha, l0):

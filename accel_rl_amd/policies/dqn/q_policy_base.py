@@ -128,17 +128,18 @@ class QPolicyBase(AtariCnnPolicy):
         return self._head_ws
 
     def _pair_rows(self, obs, next_obs):
-        """u8 [2B,C,H,W] = obs followed by next_obs: in place when the replay memory handed them out adjacent
-        (FrameReplayBuffer._batch_outputs), else through a scratch copy."""
-        b = obs.shape[0]
+        """u8 [n + n',C,H,W] = the n rows of obs followed by the n' rows of next_obs (n' = n but for DrQ's views: m B and
+        k B rows): in place when the replay memory handed them out adjacent (FrameReplayBuffer._batch_outputs), else
+        through a scratch copy."""
+        b, bn = obs.shape[0], next_obs.shape[0]
         if (obs.is_contiguous() and next_obs.is_contiguous() and
                 obs.untyped_storage().data_ptr() == next_obs.untyped_storage().data_ptr() and
                 next_obs.data_ptr() == obs.data_ptr() + obs.numel()):
-            return torch.as_strided(obs, (2 * b,) + tuple(obs.shape[1:]), obs.stride())
-        key = ("obs_pair", b)
+            return torch.as_strided(obs, (b + bn,) + tuple(obs.shape[1:]), obs.stride())
+        key = ("obs_pair", b) if bn == b else ("obs_pair", b, bn)
         both = None if torch.cuda.is_current_stream_capturing() else self._scratch.get(key)
         if both is None:
-            both = torch.empty((2 * b,) + tuple(obs.shape[1:]), dtype=torch.uint8, device=self.device)
+            both = torch.empty((b + bn,) + tuple(obs.shape[1:]), dtype=torch.uint8, device=self.device)
             if not torch.cuda.is_current_stream_capturing():
                 self._scratch[key] = both
         both[:b].copy_(obs)
@@ -152,8 +153,10 @@ class QPolicyBase(AtariCnnPolicy):
         free), whose first-half slices feed the backward pass; the target pass reads the same scaled next_obs.
         head_parts (taken on the double-DQN path from u8 rows, the one the benchmarks run; ignored elsewhere): the three
         logit entries come back as _lib.ArlLogitSrc -- the output layers' split partial sums, unfolded.
+        next_obs may hold another number of rows than obs (DrQ: k B against m B): the online pass then runs over both.
         Returns (x, out, acts, hids, target_out, online_next_out or None)."""
         b = obs.shape[0]
+        b2 = b + next_obs.shape[0]
         c, h, w = self._obs_shape
         if double_dqn and self._u8:                     # conv 1 reads the u8 rows itself: no scaled copy at all
             both = self._pair_rows(obs, next_obs)
@@ -175,7 +178,7 @@ class QPolicyBase(AtariCnnPolicy):
             x = self._scaled(obs)
             out, acts, hids = self._logits(x)
             return x, out, acts, hids, tgt, pol_next
-        x2 = self._buffer(("x2", 2 * b), (2 * b, c, h, w), channels_last=True)
+        x2 = self._buffer(("x2", b2), (b2, c, h, w), channels_last=True)
         _lib.gather_scale_obs_nhwc(obs, None, x2[:b], self._scale)
         _lib.gather_scale_obs_nhwc(next_obs, None, x2[b:], self._scale)
         tgt, _, _ = self._logits(x2[b:], w=self._w_target, tag="t")

@@ -684,6 +684,35 @@ int arl_replay_extract(const arl_replay* rb, const int32_t* env_idxs, const int3
                        int64_t batch, uint8_t* obs, uint8_t* next_obs, uint8_t* actions,
                        float* returns, uint8_t* terminals, void* stream);
 
+/* Batch extraction with DrQ's random shift (Kostrikov, Yarats, Fergus 2020; the reference has none): every observation
+ * is padded by `pad` pixels with its own border and cropped back at a drawn offset, m_obs shifted views of obs and
+ * k_next of next_obs per sample, in the one gather that reads the frames.
+ *   obs u8[m_obs * batch][n_stack][frame_h][frame_w], next_obs u8[k_next * batch][n_stack][frame_h][frame_w], both
+ *   view-major: view v of sample j is row v * batch + j (m_obs = k_next = 1: arl_replay_extract's layout);
+ *   actions, returns, terminals [batch], exactly as arl_replay_extract writes them.
+ * The source observation src is what arl_replay_extract produces for (env, step) -- (env, (step + reward_horizon) mod
+ * size) for the next views -- its leading n_blanks frames zeroed.  Views are numbered v = 0 .. m_obs - 1 (obs) and
+ * m_obs .. m_obs + k_next - 1 (next_obs); each draws ONE offset pair, shared by the n_stack frames of the stack:
+ *   words = Philox4x32-10(key = ((uint32) seed, ARL_AUG_PHILOX_STREAM),
+ *                         counter = ((uint32) j, (uint32) v, (uint32) call, (uint32)(call >> 32)))
+ *   dx = (int)(((uint64) words[0] * (2 pad + 1)) >> 32) - pad;  dy likewise from words[1]      (both in -pad .. pad)
+ *   out[f][y][x] = src[f][clamp(y + dy, 0, frame_h - 1)][clamp(x + dx, 0, frame_w - 1)]
+ * which is an edge-replicating pad by `pad` followed by a crop at (pad + dy, pad + dx).  Zeroing a blank frame commutes
+ * with the shift: it stays all zero.  pad == 0 performs no draw and its outputs equal arl_replay_extract's bit for bit.
+ * seed and call are passed by value: extraction is an eager launch outside the captured update graph (the graph only
+ * reads its static outputs), so no device-side generator state is needed; the caller advances `call` per extraction.
+ * Integer-exact, plain vector stores, no atomics: equal (seed, call) give equal outputs.
+ * Refused before any HIP call, nothing written: a NULL pointer (ARL_E_ARG); batch < 1 or >= 2^31, frame_h * frame_w !=
+ * rb->frame_bytes, frame_w % 4 != 0, pad outside 0 .. 64, m_obs or k_next outside 1 .. 8, (m_obs + k_next) * batch >=
+ * 2^31, and -- frames are staged through 16 KiB of LDS in tiles of whole rows -- frame_bytes > 16384 with
+ * frame_w > 4088 (ARL_E_RANGE); obs or next_obs not 16-byte aligned (ARL_E_ALIGN).
+ * Grid (batch, m_obs + k_next), one 256-thread workgroup per stacked view.                                          */
+#define ARL_AUG_PHILOX_STREAM 0xA5D3F1C7u   /* second key word; >= 2^31 and != ARL_IQN_PHILOX_STREAM                  */
+int arl_replay_extract_shift(const arl_replay* rb, const int32_t* env_idxs, const int32_t* step_idxs, int64_t batch,
+                             int32_t frame_h, int32_t frame_w, int32_t pad, int32_t m_obs, int32_t k_next,
+                             int64_t seed, int64_t call, uint8_t* obs, uint8_t* next_obs, uint8_t* actions,
+                             float* returns, uint8_t* terminals, void* stream);
+
 /* Parted sum tree of prioritized replay, f64[2^levels - 1], root at 0, children 2i+1 / 2i+2
  * (accel_rl/algos/dqn/replay_buffers/sum_tree.py:12-98).
  * find:   descend by prefix mass, uniforms in [0,1] scaled by the root       (:88-98)
@@ -849,6 +878,8 @@ int arl_qrdqn_loss(const float* pred, const float* tgt_next, const float* pol_ne
 #define ARL_IQN_COS 64                      /* cosine features per fraction (the paper's n = 64)               */
 #define ARL_IQN_MAX_FRACTIONS 64
 #define ARL_IQN_PHILOX_STREAM 0xC9514E31u   /* second key word; csrc/noisy.hip's streams are all below 2^31    */
+/* Philox streams by second key word: 2 layer + which (< 2^31): csrc/noisy.hip's layer noise; ARL_IQN_PHILOX_STREAM:
+ * the fractions below; ARL_AUG_PHILOX_STREAM (0xA5D3F1C7): arl_replay_extract_shift's shift offsets.              */
 
 /* Fractions and their cosine features for rows x R (sample, fraction) pairs, pair (row, r) at p = row R + r:
  *   tau f32[rows R], cosf f32[rows R][64], cosf[p][i] = cos(pi i tau[p]), i = 0 .. 63 (Eq. 4 of the paper, i = 0 included)
@@ -1021,6 +1052,27 @@ int arl_dqn_loss(const float* q, const float* tgt_next_q, const float* pol_next_
                  const float* is_weights_or_null, int64_t batch, int32_t n_actions, int32_t q_stride,
                  int32_t dueling, float gamma_n, float delta_clip, float* dq, float* loss_rows, float* td_abs,
                  void* stream);
+
+/* DrQ (Kostrikov, Yarats, Fergus 2020; the reference has none): arl_dqn_loss with the target averaged over k shifted
+ * views of next_obs and the loss over m shifted views of obs (arl_replay_extract_shift's view-major rows):
+ *   q, dq f32[m * batch][q_stride]; tgt_next_q, pol_next_q_or_null f32[k * batch][q_stride];
+ *   actions, returns, terminals, is_weights_or_null, loss_rows, td_abs [batch]
+ * One lane per sample b, everything inside the lane and in this order:
+ *   next_q_i = arl_dqn_loss's next_q of row i * batch + b (first maximum of the online row -- double DQN -- or of the
+ *              target row, valued by the target row; dueling rows merged as in arl_dqn_act), i = 0 .. k - 1
+ *   nbar     = next_q_0 if k == 1, else (((next_q_0 + next_q_1) + ...) + next_q_{k-1}) / (float) k
+ *   y        = returns_b + keep * (gamma_n * nbar)
+ *   for v = 0 .. m - 1:  d_v = y - q(v * batch + b)[actions_b];  loss_v, its slope and row v * batch + b of dq exactly
+ *              as arl_dqn_loss computes them, under the weight w = ((is_weight_b or 1) / (float) batch) / (float) m
+ *   loss_rows[b] = ((w loss_0 + w loss_1) + ...), starting from its first term
+ *   td_abs[b]    = ((p_0 + p_1) + ...) / (float) m,  p_v = |d_v| clipped as arl_dqn_loss's td_abs
+ * The device code of a row is arl_dqn_loss's own; with k == m == 1 all three outputs equal arl_dqn_loss's bit for bit.
+ * Sizes and refusals as arl_dqn_loss, plus (ARL_E_RANGE) k or m outside 1 .. 8 and m * batch or k * batch >= 2^31.
+ * A refused call launches nothing.                                                                                  */
+int arl_drq_loss(const float* q, const float* tgt_next_q, const float* pol_next_q_or_null, const uint8_t* actions,
+                 const float* returns, const uint8_t* terminals, const float* is_weights_or_null, int64_t batch,
+                 int32_t m, int32_t k, int32_t n_actions, int32_t q_stride, int32_t dueling, float gamma_n,
+                 float delta_clip, float* dq, float* loss_rows, float* td_abs, void* stream);
 
 /* Munchausen DQN (Vieillard, Pietquin, Geist 2020): arl_dqn_loss with a soft-max bootstrap and the scaled, clipped
  * log-policy bonus added to the reward.  tgt_next_q, tgt_cur_q f32[batch][q_stride]: the TARGET net on next_obs and on

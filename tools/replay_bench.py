@@ -1,6 +1,8 @@
 """BASELINE config 5 shape: 1M-transition device replay (Seaquest frames 4 x 104 x 80), event-timed
 append / extract / sum-tree operations with their algorithmic HBM bytes.
-usage: python tools/replay_bench.py [n_env] [size]"""
+usage: python tools/replay_bench.py [n_env] [size] [--shift PAD]
+--shift PAD: after every "extract batch" line, one more for arl_replay_extract_shift (DrQ's random shift inside the
+gather; 1 x 1 views, pad PAD) on the same indices and outputs."""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -34,8 +36,13 @@ def ev(fn, reps=20, warm=3):
 
 
 def main():
-    n_env = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-    size = int(sys.argv[2]) if len(sys.argv) > 2 else 1000000
+    argv, shift = list(sys.argv), None
+    if "--shift" in argv:
+        at = argv.index("--shift")
+        shift = int(argv[at + 1])
+        del argv[at:at + 2]
+    n_env = int(argv[1]) if len(argv) > 1 else 256
+    size = int(argv[2]) if len(argv) > 2 else 1000000
     t, h_r, frame = 4, 3, 104 * 80
     buf = PrioritizedReplayBuffer(alpha=0.6, beta_initial=0.4, default_priority=1., env_spec=_Spec(), size=size,
                                   reward_horizon=h_r, sampling_horizon=t, n_environments=n_env, discount=0.99,
@@ -66,6 +73,11 @@ def main():
         us = ev(lambda: _lib.replay_extract(buf._rb, e_idx, s_idx, outs[0], outs[1], a, r, tm))
         nbytes = b * 2 * 2 * 4 * frame
         print("extract batch %4d: %7.1f us  %7.1f GB/s algorithmic (%.1f MB read + written)" % (b, us, nbytes / us / 1e3, nbytes / 1e6))
+        if shift is not None:
+            calls = iter(range(1 << 30))        # a new call counter per launch: new offsets, as in training
+            us = ev(lambda: _lib.replay_extract_shift(buf._rb, e_idx, s_idx, 104, 80, shift, 1, 1, 0, next(calls), outs[0],
+                                                      outs[1], a, r, tm))
+            print("extract batch %4d, shift pad %d: %7.1f us  %7.1f GB/s algorithmic" % (b, shift, us, nbytes / us / 1e3))
         u = torch.rand(b, dtype=torch.float64, device=DEV, generator=gen)
         out = torch.empty(b, dtype=torch.int32, device=DEV)
         us = ev(lambda: _lib.sumtree_find(tree.tree, tree.tree_level, u, out))
