@@ -63,7 +63,8 @@ __global__ __launch_bounds__(256) void frame_step_kernel(const arl_game g, const
                 for (int64_t i = e; i < hi; ++i) total += (RESET_ONLY && !ext_flags) ? 1 : (flags[i] != 0);
             st.noop_cursor[(parity ^ 1) * n_streams + w] = st.noop_cursor[parity * n_streams + w] + total;
         }
-        if (RESET_ONLY && flagged) st.frozen[e] = 0;
+        // (st.frozen of a reset env is cleared by reset_finish_kernel, AFTER this launch: the caller's flags may BE
+        //  st.frozen, and the other workgroups of the stream still count them for their ranks and the leader's total)
         // arl_env_step's reset forecast (will_reset): a freshly reset env starts a trajectory (Length 0, so no
         // over-length at the limits >= 1 that arl_env_step accepts); the others keep theirs
         if (RESET_ONLY && st.next_reset) {
@@ -204,6 +205,21 @@ __global__ void epoch_kernel(int32_t* epoch, int32_t* launch_count) {
     if (launch_count) launch_count[0] += 1;
 }
 
+// AFTER arl_env_reset's frame_step launch: the envs it reset leave the frozen state (worker.py:108-113), and the launch
+// epoch is bumped.  A launch of its own because the flags are usually st.frozen itself: cleared inside the reset launch,
+// by each env's workgroup as it finished, the flags of a stream changed under the workgroups still ranking their envs
+// among them -- from about 64 envs per stream on, some then took another env's start no-op draw.  Here every thread
+// reads and clears its own env's byte only.
+__global__ __launch_bounds__(256) void reset_finish_kernel(const arl_env_state st, const uint8_t* __restrict__ ext_flags,
+                                                           int32_t* launch_count) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < st.n_env && (ext_flags ? ext_flags[e] != 0 : true)) st.frozen[e] = 0;
+    if (e == 0) {
+        st.epoch[0] += 1;
+        if (launch_count) launch_count[0] += 1;
+    }
+}
+
 __global__ __launch_bounds__(256) void preprocess_kernel(const uint8_t* __restrict__ a,
                                                          const uint8_t* __restrict__ b,
                                                          uint8_t* __restrict__ out, const int resample_mode) {
@@ -336,8 +352,9 @@ extern "C" int arl_env_reset(const arl_game* game, const arl_env_state* st, cons
                        *st, *ro, flags_or_null, 0, (int)max_start_noops);
     rc = arl::check_launch("frame_step_kernel<reset>");
     if (rc) return rc;
-    hipLaunchKernelGGL(epoch_kernel, dim3(1), dim3(1), 0, s, st->epoch, st->next_reset ? st->launch_count : (int32_t*)nullptr);
-    return arl::check_launch("epoch_kernel");
+    hipLaunchKernelGGL(reset_finish_kernel, dim3((unsigned)((st->n_env + 255) / 256)), dim3(256), 0, s, *st, flags_or_null,
+                       st->next_reset ? st->launch_count : (int32_t*)nullptr);
+    return arl::check_launch("reset_finish_kernel");
 }
 
 extern "C" int arl_preprocess_frames(const uint8_t* raw_a_or_null, const uint8_t* raw_b, int64_t n,

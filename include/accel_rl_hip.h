@@ -566,7 +566,12 @@ int arl_rollout_begin_conv1(const arl_game* game, const arl_env_state* st, const
  * Replaces accel_rl/sampler/act_server/alternating/overlap/sampler.py:120-151 (serve_actions), the output layers of
  * _f_prob_value (policies/pg/atari_cnn_policy.py:63-67, pg/networks/pg_cnn.py:57-86), rllab/misc/special.py:22-27,
  * overlap/worker.py:37-59, envs/atari_env.py:65-78,93-100,151-191 and pg_cnn.py:47-52 for the next observation.
- * Needs st->next_reset, max_path_length >= 1, n_stack <= 4, 16-byte aligned observations / step_obs.               */
+ * Needs st->next_reset, max_path_length >= 1, n_stack <= 4, 16-byte aligned observations / step_obs.
+ * Limits (anything else is refused, nothing launched): head->hid a multiple of 4 and <= 1024; n_actions <=
+ * ARL_MAX_ACTIONS (18); with split partials the fold's scratch zgn * hid * 4 bytes <= 64 KiB, where zgn = 16 below the
+ * wide fold's threshold (128 splits) and 64 from it on -- i.e. any hid up to 1024 below the threshold, hid <= 256 from
+ * it on; head->hidden.total == n_env * hid, splits >= 0, part and hidden_bias 16-byte aligned.  Any n_env >= 1 and any
+ * envs_per_stream >= 1 (streams longer than n_env and a shorter last stream included).                              */
 int arl_env_step_served(const arl_game* game, const arl_env_state* st, const arl_rollout* ro,
                         const arl_serve_head* head, const arl_serve_conv1* conv1_or_null,
                         const double* uniforms, int32_t step, double max_path_length, double discount,
