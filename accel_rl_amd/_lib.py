@@ -4,6 +4,7 @@ There is NO fallback: if the shared library is missing or a call fails, the
 product raises.  PyTorch is used only as the owner of device memory and
 streams; the ABI itself sees raw pointers and sizes.
 """
+import collections
 import ctypes as C
 import os
 
@@ -265,6 +266,11 @@ _SIGNATURES = {
                                            _i32, _f32, _f32, _f32, _vp, _vp, _vp, C.POINTER(ArlDgradWt), _i32, _vp]),
 }
 
+class ArlDevLaunch(C.Structure):
+    _fields_ = [(n, _i32) for n in ("family", "wgm", "wgn", "tm", "tn", "bk", "minw", "flags", "split_mode", "splits")] + \
+               [(n, C.c_uint32) for n in ("grid_x", "grid_y", "grid_z", "lds_bytes")]
+
+
 # include/accel_rl_hip_dev.h: development hooks (tests / tools), not part of the drop-in boundary
 _DEV_SIGNATURES = {
     "arl_dev_conv_trace_buffer": (None, [_vp]),
@@ -272,6 +278,7 @@ _DEV_SIGNATURES = {
     "arl_dev_conv_variant": (None, [_i32]),
     "arl_dev_fwd_tile": (None, [_i32]),
     "arl_dev_dgrad_wt": (None, [_i32]),
+    "arl_dev_conv_launch_log": (_i32, [C.POINTER(ArlDevLaunch), _i32]),
     "arl_dev_fold_wide_from": (None, [_i32]),
     "arl_dev_scan_force_wave": (None, [_i32]),
     "arl_dev_scan_wave_groups": (None, [_i32]),
@@ -678,6 +685,27 @@ def with_route(geom, route=None):
     g = ArlConvGeom.from_buffer_copy(geom)
     g.route = default_route if route is None else route
     return g
+
+
+# arl_dev_conv_launch_log (include/accel_rl_hip_dev.h: ARL_DEV_K_*, ARL_DEV_F_*, ARL_DEV_LAUNCH_LOG_MAX)
+DEV_LAUNCH_FAMILIES = (None, "igemm", "igemm_occ", "igemm_split", "igemm_u8", "rowgather", "wgrad", "wgrad_fast",
+                       "wgrad_split", "wgrad_u8", "bwd_pair", "wgrad_group", "conv1_img", "fold", "fold_many",
+                       "dgrad_weights")
+DEV_LAUNCH_FLAGS = ("b_kc", "n16", "u8", "multi_tap", "has_pad", "direct", "corun", "tap_uniform")
+DEV_LAUNCH_LOG_MAX = 32
+ConvLaunch = collections.namedtuple("ConvLaunch", "family tile minw flags split_mode splits grid lds_bytes")
+
+
+def conv_launch_log():
+    """The launches of this thread's most recent conv / dense entry-point call, in issue order: ConvLaunch(family name,
+    (WGM, WGN, TM, TN, BK), minw, frozenset of flag names, split mode, splits, (x, y, z), dynamic LDS bytes)."""
+    rec = (ArlDevLaunch * DEV_LAUNCH_LOG_MAX)()
+    n = load().arl_dev_conv_launch_log(rec, DEV_LAUNCH_LOG_MAX)
+    if n > DEV_LAUNCH_LOG_MAX:
+        raise RuntimeError("conv launch log: %d launches, only %d kept" % (n, DEV_LAUNCH_LOG_MAX))
+    return [ConvLaunch(DEV_LAUNCH_FAMILIES[r.family], (r.wgm, r.wgn, r.tm, r.tn, r.bk), r.minw,
+                       frozenset(f for i, f in enumerate(DEV_LAUNCH_FLAGS) if r.flags >> i & 1), r.split_mode, r.splits,
+                       (r.grid_x, r.grid_y, r.grid_z), r.lds_bytes) for r in rec[:n]]
 
 
 def conv_out_hw(g):

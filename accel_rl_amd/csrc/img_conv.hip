@@ -95,6 +95,8 @@ int launch_conv1_img(const unsigned char* obs, int64_t obs_rows, const int32_t* 
     }
     const int cus = 256;
     hipLaunchKernelGGL(conv1_img_kernel, dim3((unsigned)(batch < cus ? batch : cus)), dim3(C1_NT), lds, s, a);
+    log_launch(ARL_DEV_K_CONV1_IMG, {0, 0, 0, 0, 0, 0}, launch_flags(true, false, true, false, false), 1,
+               dim3((unsigned)(batch < cus ? batch : cus)), lds);
     return arl::check_launch("conv1_img_kernel");
 }
 

@@ -7,6 +7,8 @@ using namespace arlc;
 
 namespace arlc {
 thread_local CallCtx t_ctx = {9, nullptr, false};
+thread_local LaunchLog t_launch_log = {};
+thread_local int t_launch_split = 9;
 unsigned long long* g_trace = nullptr;
 bool g_force_generic = false;
 int g_fwd_tile = -1;            // arl_dev_fwd_tile: -1 = chosen by the launch's size (fwd_impl)
@@ -121,6 +123,8 @@ int launch_fold(const float* part, int splits, int64_t total, const float* bias,
     hipLaunchKernelGGL(fold_splits_kernel, dim3((unsigned)fold_blocks(splits, total4)), dim3(FOLD_THREADS), 0, s,
                        (const float4*)part, splits, total4, (const float4*)bias, n_bias >> 2, relu,
                        (const float4*)mask, (float4*)out, g_fold_wide);
+    log_launch(ARL_DEV_K_FOLD, {splits >= g_fold_wide ? 64 : 16, 0, 0, 0, 0, 0}, 0, splits,
+               dim3((unsigned)fold_blocks(splits, total4)), 0);
     return arl::check_launch("fold_splits_kernel");
 }
 
@@ -137,6 +141,12 @@ extern "C" void arl_dev_fold_wide_from(int32_t splits) { g_fold_wide = splits > 
 extern "C" void arl_dev_fwd_tile(int32_t v) { g_fwd_tile = ((v >= 0 && v <= 2) || v == 6 || v == 7) ? v : -1; }
 
 extern "C" void arl_dev_dgrad_wt(int32_t on) { g_dgrad_wt = on != 0; }
+
+extern "C" int32_t arl_dev_conv_launch_log(arl_dev_launch* out, int32_t max) {
+    const LaunchLog& l = t_launch_log;
+    for (int i = 0; out && i < l.n && i < max && i < ARL_DEV_LAUNCH_LOG_MAX; ++i) out[i] = l.rec[i];
+    return l.n;
+}
 
 extern "C" int arl_corun_job_init(arl_corun_job* job, const arl_opt_state* opt, int32_t method, float learning_rate,
                                   float avg_factor, float beta1_or_rho, float beta2, float epsilon, int32_t k,
@@ -427,6 +437,7 @@ int launch_wgrad_plan(const WgradPlan& p, hipStream_t s) {
         const dim3 grid((a.N + bn - 1) / bn, (K + bm - 1) / bm, splits);
         if (p.cfg == 0) hipLaunchKernelGGL((wgrad_u8_kernel<1, 4, 1, 1, FBK, true>), grid, dim3(256), lds, s, a);
         else hipLaunchKernelGGL((wgrad_u8_kernel<1, 4, 1, 1, FBK, false>), grid, dim3(256), lds, s, a);
+        log_launch(ARL_DEV_K_WGRAD_U8, {1, 4, 1, 1, FBK, 0}, launch_flags(false, p.cfg == 0, true, false, false), splits, grid, lds);
         return arl::check_launch("wgrad_u8_kernel");
     }
     if (p.fast) {
@@ -619,6 +630,7 @@ void fill_u8(GatherDesc* d, const uint8_t* obs, int64_t obs_rows, const int32_t*
 extern "C" int arl_conv2d_u8_fwd(const uint8_t* obs, int64_t obs_rows, const int32_t* idx_or_null, float scale,
                                  const float* w, const float* bias_or_null, float* y, const arl_conv_geom* geom,
                                  int32_t relu, void* stream) {
+    launch_log_clear();                             // (the scope opens only after the geometry checks)
     ARL_REQUIRE(w && y, ARL_E_ARG, "null pointer");
     U8Geom g;
     int rc = check_u8(obs, obs_rows, geom, &g);
@@ -645,6 +657,7 @@ extern "C" int arl_conv2d_u8_fwd(const uint8_t* obs, int64_t obs_rows, const int
     if (a.N <= 16) {
         const size_t lds = (size_t)2 * (BM * (BK + 4) + 16 * (BK + 4)) * sizeof(float);
         hipLaunchKernelGGL((igemm_u8_kernel<4, 1, 2, 1, BK, true>), grid, dim3(256), lds, (hipStream_t)stream, a);
+        log_launch(ARL_DEV_K_IGEMM_U8, {4, 1, 2, 1, BK, 0}, launch_flags(true, true, true, false, false), 1, grid, lds);
     } else if (g_split && g.kh % (8 / (g.kw >> 2)) == 0) {
         // bf16-split products: the pixels are exact in one bf16 plane (three products), 32-deep k-tiles = whole filter rows
         return launch_igemm_split<4, 1, 2, 1, 32, true, true, 2>(a, false, false, (hipStream_t)stream);
@@ -657,10 +670,12 @@ extern "C" int arl_conv2d_u8_fwd(const uint8_t* obs, int64_t obs_rows, const int
         const size_t lds = (size_t)2 * (PBM * (PBK + 4) + 32 * (PBK + 4)) * sizeof(float);
         hipLaunchKernelGGL((igemm_occ_kernel<2, 2, 2, 1, PBK, true, false, false, true, 5, false, true>), pgrid, dim3(256),
                            lds, (hipStream_t)stream, a, none);
+        log_launch(ARL_DEV_K_IGEMM_OCC, {2, 2, 2, 1, PBK, 5}, launch_flags(true, true, true, false, false), 1, pgrid, lds);
         return arl::check_launch("igemm_occ_kernel (u8)");
     } else {
         const size_t lds = (size_t)2 * (BM * (BK + 4) + 32 * (BK + 4)) * sizeof(float);
         hipLaunchKernelGGL((igemm_u8_kernel<4, 1, 1, 1, BK, false>), grid, dim3(256), lds, (hipStream_t)stream, a);
+        log_launch(ARL_DEV_K_IGEMM_U8, {4, 1, 1, 1, BK, 0}, launch_flags(true, false, true, false, false), 1, grid, lds);
     }
     return arl::check_launch("igemm_u8_kernel");
 }
@@ -669,6 +684,7 @@ namespace {
 int wgrad_u8_impl(const float* dy, const uint8_t* obs, int64_t obs_rows, const int32_t* idx_or_null, float scale, float* dw,
                   const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes, arl_fold_item* item,
                   float* dbias_or_null, arl_fold_item* bias_item_or_null, WgradPlan* plan_only, void* stream) {
+    launch_log_clear();                             // (the scope opens only after the geometry checks)
     ARL_REQUIRE(dy && dw && workspace && item && (!dbias_or_null || bias_item_or_null), ARL_E_ARG, "null pointer");
     U8Geom g;
     int rc = check_u8(obs, obs_rows, geom, &g);
@@ -814,6 +830,7 @@ extern "C" int arl_conv2d_bwd_pair_plan(const float* dy, const float* w, const f
 // The planned weight gradients of a backward pass: the group-eligible ones (a bf16-split route, one of
 // wgrad_group_kernel's bodies, no trace buffer) in one launch, every other one on its own first.
 extern "C" int arl_conv2d_bwd_weight_group(const arl_wgrad_plan* plans, int32_t n, void* stream) {
+    launch_log_clear();                             // (one log for the whole call: the scopes below keep it)
     ARL_REQUIRE(plans || n == 0, ARL_E_ARG, "null pointer");
     ARL_REQUIRE(n >= 0 && n <= ARL_WGRAD_GROUP_MAX, ARL_E_RANGE, "0 .. ARL_WGRAD_GROUP_MAX plans");
     hipStream_t s = (hipStream_t)stream;
@@ -835,7 +852,7 @@ extern "C" int arl_conv2d_bwd_weight_group(const arl_wgrad_plan* plans, int32_t 
         bool grouped = false;
         for (int k = 0; k < n_el; ++k) grouped = grouped || el[k] == i;
         if (grouped && n_el > 1) continue;
-        const CallScope scope(pl[i]->route);
+        const CallScope scope(pl[i]->route, nullptr, true);
         const int rc = launch_wgrad_plan(*pl[i], s);
         if (rc) return rc;
     }
@@ -860,7 +877,7 @@ extern "C" int arl_conv2d_bwd_weight_group(const arl_wgrad_plan* plans, int32_t 
         groups += (g.blocks[k] + 7) / 8;
     }
     g.group_start[n_el] = groups; g.n = n_el;
-    const CallScope scope(route);
+    const CallScope scope(route, nullptr, true);
     return launch_wgrad_group(g, groups, lds, s);
 }
 
@@ -903,15 +920,18 @@ int dgrad_wt_plan(const arl_dgrad_wt* items, int32_t n, DgradWtArgs* out, int* b
 }  // namespace arlw
 
 extern "C" int arl_conv2d_dgrad_weights(const arl_dgrad_wt* items, int32_t n, void* stream) {
+    launch_log_clear();
     arlw::DgradWtArgs a;
     int blocks = 0;
     int rc = arlw::dgrad_wt_plan(items, n, &a, &blocks);
     if (rc) return rc;
     hipLaunchKernelGGL(dgrad_weights_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    log_launch(ARL_DEV_K_DGRAD_WEIGHTS, {0, 0, 0, 0, 0, 0}, 0, n, dim3((unsigned)blocks), 0);
     return arl::check_launch("dgrad_weights_kernel");
 }
 
 extern "C" int arl_fold_many(const arl_fold_item* items, int32_t n, void* stream) {
+    launch_log_clear();
     ARL_REQUIRE(items || n == 0, ARL_E_ARG, "null pointer");
     ARL_REQUIRE(n >= 0 && n <= ARL_FOLD_MAX_ITEMS, ARL_E_RANGE, "too many fold items");
     FoldManyArgs a = {};
@@ -929,5 +949,6 @@ extern "C" int arl_fold_many(const arl_fold_item* items, int32_t n, void* stream
     a.block_start[a.n] = blocks;
     a.wide_from = g_fold_wide;
     hipLaunchKernelGGL(fold_many_kernel, dim3((unsigned)blocks), dim3(FOLD_THREADS), 0, (hipStream_t)stream, a);
+    log_launch(ARL_DEV_K_FOLD_MANY, {0, 0, 0, 0, 0, 0}, 0, a.n, dim3((unsigned)blocks), 0);
     return arl::check_launch("fold_many_kernel");
 }

@@ -8,6 +8,20 @@
 
 namespace arlc {
 
+// arl_dev_conv_launch_log: what the calling thread's current (or last) entry-point call launched.  Host side only.
+struct LaunchLog { int n; arl_dev_launch rec[ARL_DEV_LAUNCH_LOG_MAX]; };
+extern thread_local LaunchLog t_launch_log;        // (mfma_conv.hip)
+extern thread_local int t_launch_split;            // the open CallScope's split mode (= t_ctx.split)
+inline void launch_log_clear() { t_launch_log.n = 0; }
+struct Tile { int wgm, wgn, tm, tn, bk, minw; };
+inline void log_launch(int family, Tile t, int flags, int splits, dim3 grid, size_t lds) {
+    LaunchLog& l = t_launch_log;
+    if (l.n < ARL_DEV_LAUNCH_LOG_MAX)
+        l.rec[l.n] = arl_dev_launch{family, t.wgm, t.wgn, t.tm, t.tn, t.bk, t.minw, flags, t_launch_split, splits,
+                                    grid.x, grid.y, grid.z, (uint32_t)lds};
+    ++l.n;
+}
+
 template <int WGM, int WGN, int TM, int TN, int BK, bool B_KC, bool TAP_UNIFORM = false>
 int launch_rowgather(const GemmArgs& a, int splits, hipStream_t s) {
     constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
@@ -15,6 +29,8 @@ int launch_rowgather(const GemmArgs& a, int splits, hipStream_t s) {
     const size_t lds = (size_t)2 * (A_SZ + B_SZ) * sizeof(float);
     dim3 grid((a.M + BM - 1) / BM, (a.N + BN - 1) / BN, splits);
     hipLaunchKernelGGL((rowgather_gemm_kernel<WGM, WGN, TM, TN, BK, B_KC, TAP_UNIFORM>), grid, dim3(256), lds, s, a);
+    log_launch(ARL_DEV_K_ROWGATHER, {WGM, WGN, TM, TN, BK, 0},
+               (B_KC ? ARL_DEV_F_B_KC : 0) | (TAP_UNIFORM ? ARL_DEV_F_TAP_UNIFORM : 0), splits, grid, lds);
     return arl::check_launch("rowgather_gemm_kernel");
 }
 
@@ -24,7 +40,14 @@ int launch_wgrad(const WgradArgs& a, int splits, hipStream_t s) {
     const size_t lds = (size_t)2 * BK * (BM + BN) * sizeof(float);
     dim3 grid((a.N + BN - 1) / BN, (a.K_out + BM - 1) / BM, splits);
     hipLaunchKernelGGL((wgrad_kernel<WGM, WGN, TM, TN, BK>), grid, dim3(256), lds, s, a);
+    log_launch(ARL_DEV_K_WGRAD, {WGM, WGN, TM, TN, BK, 0}, 0, splits, grid, lds);
     return arl::check_launch("wgrad_kernel");
+}
+
+inline int launch_flags(bool b_kc, bool n16, bool u8, bool multi_tap, bool has_pad, bool direct = false, bool corun = false) {
+    return (b_kc ? ARL_DEV_F_B_KC : 0) | (n16 ? ARL_DEV_F_N16 : 0) | (u8 ? ARL_DEV_F_U8 : 0) |
+           (multi_tap ? ARL_DEV_F_MULTI_TAP : 0) | (has_pad ? ARL_DEV_F_HAS_PAD : 0) | (direct ? ARL_DEV_F_DIRECT : 0) |
+           (corun ? ARL_DEV_F_CORUN : 0);
 }
 
 constexpr bool lds_fits(int floats) { return floats * 4 <= 65536; }
@@ -56,6 +79,7 @@ int launch_igemm(const GemmArgs& a, int splits, bool multi_tap, bool has_pad, hi
     else if (has_pad) ARL_IGEMM(false, true);
     else ARL_IGEMM(false, false);
 #undef ARL_IGEMM
+    if (!rc) log_launch(ARL_DEV_K_IGEMM, {WGM, WGN, TM, TN, BK, 0}, launch_flags(B_KC, N16, false, multi_tap, has_pad), splits, grid, lds);
     return rc ? rc : arl::check_launch("igemm_kernel");
 }
 
@@ -69,8 +93,11 @@ struct CallCtx { int split; const CorunJob* corun; bool corun_taken; };
 extern thread_local CallCtx t_ctx;                 // (mfma_conv.hip)
 #define g_split (t_ctx.split)
 struct CallScope {
-    explicit CallScope(int split, const arl_corun_job* job = nullptr) {
+    // keep_log: a further scope of the same entry-point call (arl_conv2d_bwd_weight_group: one per plan)
+    explicit CallScope(int split, const arl_corun_job* job = nullptr, bool keep_log = false) {
         t_ctx.split = split; t_ctx.corun = reinterpret_cast<const CorunJob*>(job); t_ctx.corun_taken = false;
+        t_launch_split = split;
+        if (!keep_log) launch_log_clear();
     }
     ~CallScope() { t_ctx.corun = nullptr; }
 };
@@ -105,6 +132,7 @@ int launch_igemm_occ(const GemmArgs& a, bool multi_tap, bool has_pad, hipStream_
         if (!multi_tap && corun_take(&c, &grid)) {
             if (has_pad) hipLaunchKernelGGL((igemm_occ_kernel<WGM, WGN, TM, TN, BK, B_KC, false, true, N16, MINW, true>), grid, dim3(256), lds, s, a, c);
             else hipLaunchKernelGGL((igemm_occ_kernel<WGM, WGN, TM, TN, BK, B_KC, false, false, N16, MINW, true>), grid, dim3(256), lds, s, a, c);
+            log_launch(ARL_DEV_K_IGEMM_OCC, {WGM, WGN, TM, TN, BK, MINW}, launch_flags(B_KC, N16, false, false, has_pad, false, true), splits, grid, lds);
             return arl::check_launch("igemm_occ_kernel (co-run)");
         }
     }
@@ -115,6 +143,7 @@ int launch_igemm_occ(const GemmArgs& a, bool multi_tap, bool has_pad, hipStream_
     else if (has_pad) ARL_IGEMM_OCC(false, true);
     else ARL_IGEMM_OCC(false, false);
 #undef ARL_IGEMM_OCC
+    log_launch(ARL_DEV_K_IGEMM_OCC, {WGM, WGN, TM, TN, BK, MINW}, launch_flags(B_KC, N16, false, multi_tap, has_pad), splits, grid, lds);
     return arl::check_launch("igemm_occ_kernel");
 }
 
@@ -136,6 +165,10 @@ int launch_igemm_split(const GemmArgs& a, bool multi_tap, bool has_pad, hipStrea
     dim3 grid((a.M + BM - 1) / BM, (a.N + BN - 1) / BN, a.n_par ? a.n_par : splits);
     arl::OptSeg c = {};
     int rc = 0;
+    auto note = [&](bool mt, bool hp, bool co) {    // (ad: what ARL_SPLIT_PIN below selects)
+        const bool ad = WGN == 1 && (U8 || !mt);
+        if (!rc) log_launch(ARL_DEV_K_IGEMM_SPLIT, {WGM, WGN, TM, TN, BK, MINW}, launch_flags(B_KC, false, U8, mt, hp, ad, co), splits, grid, ad ? lds_dir : lds);
+    };
 #define ARL_SPLIT_K(MT, HP, SPL, CO, AD)                                                                   \
     do {                                                                                                   \
         auto k = igemm_split_kernel<WGM, WGN, TM, TN, BK, B_KC, MT, HP, U8, SPL, MINW, CO, AD>;            \
@@ -155,11 +188,13 @@ int launch_igemm_split(const GemmArgs& a, bool multi_tap, bool has_pad, hipStrea
     } while (0)
     if constexpr (U8) {
         ARL_SPLIT_MODE(false, false, false);
+        note(false, false, false);
     } else {
         // (data gradients: k-major weights, or k-contiguous ones on the one-wave-per-row-tile shapes)
         if constexpr (!B_KC || (WGM == 4 && WGN == 1 && TM == 1)) {
             if (!multi_tap && corun_take(&c, &grid)) {
                 if (has_pad) ARL_SPLIT_MODE(false, true, true); else ARL_SPLIT_MODE(false, false, true);
+                note(false, has_pad, true);
                 return rc ? rc : arl::check_launch("igemm_split_kernel (co-run)");
             }
         }
@@ -167,6 +202,7 @@ int launch_igemm_split(const GemmArgs& a, bool multi_tap, bool has_pad, hipStrea
         else if (multi_tap) ARL_SPLIT_MODE(true, false, false);
         else if (has_pad) ARL_SPLIT_MODE(false, true, false);
         else ARL_SPLIT_MODE(false, false, false);
+        note(multi_tap, has_pad, false);
     }
 #undef ARL_SPLIT_PIN
 #undef ARL_SPLIT_MODE
@@ -189,6 +225,7 @@ int launch_wgrad_fast(const WgradArgs& a, int splits, bool has_pad, hipStream_t 
         rc = allow_big_lds(k, lds + 4096);
         if (!rc) hipLaunchKernelGGL(k, grid, dim3(256), lds, s, a);
     }
+    if (!rc) log_launch(ARL_DEV_K_WGRAD_FAST, {WGM, WGN, TM, TN, BK, 0}, launch_flags(false, M16, false, false, has_pad), splits, grid, lds);
     return rc ? rc : arl::check_launch("wgrad_fast_kernel");
 }
 
@@ -213,6 +250,7 @@ int launch_wgrad_split(const WgradArgs& a, int splits, bool has_pad, hipStream_t
         ARL_BY_MODE(ARL_WSPLIT(false, 1), ARL_WSPLIT(false, 6), ARL_WSPLIT(false, 9));
     }
 #undef ARL_WSPLIT
+    if (!rc) log_launch(ARL_DEV_K_WGRAD_SPLIT, {WGM, WGN, TM, TN, BK, MINW}, launch_flags(false, false, U8, false, !U8 && has_pad), splits, grid, lds);
     return rc ? rc : arl::check_launch("wgrad_split_kernel");
 }
 
@@ -303,6 +341,7 @@ int launch_pair(const DgradPlan& d, const WgradPlan& w, bool has_pad, hipStream_
     const int wgx = (w.a.N + WBN - 1) / WBN, wgy = (w.a.K_out + WBM - 1) / WBM, wgz = w.splits;
     const int n_ig = dgx * dgy * dgz, n_wg = wgx * wgy * wgz;
     int rc;
+    size_t lds_used = lds;
     if (g_split) {
         const size_t lds_s = (size_t)2 * planes_of(g_split) * ((DBM + DBN) > (WBM + WBN) ? (DBM + DBN) : (WBM + WBN)) * BK * 2;
 #define ARL_PSPLIT(HP, SPL)                                                                                \
@@ -314,6 +353,7 @@ int launch_pair(const DgradPlan& d, const WgradPlan& w, bool has_pad, hipStream_
         if (has_pad) ARL_BY_MODE(ARL_PSPLIT(true, 1), ARL_PSPLIT(true, 6), ARL_PSPLIT(true, 9));
         else ARL_BY_MODE(ARL_PSPLIT(false, 1), ARL_PSPLIT(false, 6), ARL_PSPLIT(false, 9));
 #undef ARL_PSPLIT
+        lds_used = lds_s;
     } else if (has_pad) {
         auto k = bwd_pair_kernel<DWGM, DWGN, DTM, DTN, WWGM, WWGN, WTM, WTN, BK, true>;
         rc = allow_big_lds(k, lds + 4096);
@@ -323,6 +363,8 @@ int launch_pair(const DgradPlan& d, const WgradPlan& w, bool has_pad, hipStream_
         rc = allow_big_lds(k, lds + 4096);
         if (!rc) hipLaunchKernelGGL(k, dim3(n_ig + n_wg), dim3(256), lds, s, d.a, w.a, dgx, dgy, n_ig, wgx, wgy);
     }
+    // (tile = the data gradient's; both halves are 128 x 128 in every instantiation; splits = the weight gradient's)
+    if (!rc) log_launch(ARL_DEV_K_BWD_PAIR, {DWGM, DWGN, DTM, DTN, BK, 0}, launch_flags(false, false, false, false, has_pad), wgz, dim3(n_ig + n_wg), lds_used);
     return rc ? rc : arl::check_launch("bwd_pair_kernel");
 }
 
@@ -390,6 +432,7 @@ int launch_wgrad_group(const WgradGroupArgs& g, int groups, size_t lds, hipStrea
     } while (0)
     ARL_BY_MODE(ARL_WGROUP(1), ARL_WGROUP(6), ARL_WGROUP(9));
 #undef ARL_WGROUP
+    if (!rc) log_launch(ARL_DEV_K_WGRAD_GROUP, {0, 0, 0, 0, 32, 0}, 0, g.n, dim3((unsigned)groups * 8), lds);
     return rc ? rc : arl::check_launch("wgrad_group_kernel");
 }
 #endif

@@ -36,8 +36,42 @@ void arl_dev_dgrad_wt(int32_t on);
 void arl_dev_fold_wide_from(int32_t splits);
 
 /* Tests / A-B measurements: bit 0 set = the image-stationary kernels (csrc/img_conv.hip) are not used; the tap-gathering
- * kernels they replace run instead (same results bit for bit).                                                      */
+ * kernels they replace run instead (32 filters: the split kernel, same results bit for bit; 16 filters: the fp32 chain's
+ * 16-wide tiles, same results to fp32 round-off).                                                                   */
 void arl_dev_conv_variant(int32_t v);
+
+/* Tests: which kernels a conv / dense entry point launched.  Host-side only: every launcher of csrc/mfma_dispatch.h and the
+ * direct launch sites of csrc/mfma_conv.hip / img_conv.hip note their template arguments, run-time flags, grid and dynamic
+ * LDS size in a fixed-size thread-local list, which the next conv entry point on that thread clears on entry.
+ *   family   ARL_DEV_K_*: the kernel template
+ *   wgm .. bk, minw   its tile parameters (0 where the kernel has none; minw = waves per SIMD it is compiled for;
+ *                     fold / fold_many: wgm = threads that share one output, 16 or 64 = the wide fold)
+ *   flags    ARL_DEV_F_* bits
+ *   split_mode   the call's route as the kernels see it: 0 = fp32 MFMA chain, 6 / 9 = bf16-split products, 1 = bf16
+ *   splits   reduction splits of the launch (fold: partial sums folded; dgrad_weights / fold_many: items)            */
+enum {
+    ARL_DEV_K_IGEMM = 1, ARL_DEV_K_IGEMM_OCC, ARL_DEV_K_IGEMM_SPLIT, ARL_DEV_K_IGEMM_U8, ARL_DEV_K_ROWGATHER,
+    ARL_DEV_K_WGRAD, ARL_DEV_K_WGRAD_FAST, ARL_DEV_K_WGRAD_SPLIT, ARL_DEV_K_WGRAD_U8, ARL_DEV_K_BWD_PAIR,
+    ARL_DEV_K_WGRAD_GROUP, ARL_DEV_K_CONV1_IMG, ARL_DEV_K_FOLD, ARL_DEV_K_FOLD_MANY, ARL_DEV_K_DGRAD_WEIGHTS
+};
+enum {
+    ARL_DEV_F_B_KC = 1,         /* weights with the reduction index contiguous (forward layout)                       */
+    ARL_DEV_F_N16 = 2,          /* 16-wide MFMA tiles (N16 of the forward / data gradient, M16 of the weight gradient) */
+    ARL_DEV_F_U8 = 4,           /* planar u8 input                                                                    */
+    ARL_DEV_F_MULTI_TAP = 8,    /* several filter taps per k-tile                                                     */
+    ARL_DEV_F_HAS_PAD = 16,     /* the padded-border variant                                                          */
+    ARL_DEV_F_DIRECT = 32,      /* the gathered operand goes straight to the fragment registers, not through LDS     */
+    ARL_DEV_F_CORUN = 64,       /* the launch hosts the call's optimiser job                                          */
+    ARL_DEV_F_TAP_UNIFORM = 128 /* generic data gradient: a k-tile never straddles two filter taps                    */
+};
+#define ARL_DEV_LAUNCH_LOG_MAX 32
+typedef struct arl_dev_launch {
+    int32_t family, wgm, wgn, tm, tn, bk, minw, flags, split_mode, splits;
+    uint32_t grid_x, grid_y, grid_z, lds_bytes;
+} arl_dev_launch;
+/* Launches of the calling thread's most recent conv entry-point call, in issue order: returns how many there were (all of
+ * them, even beyond ARL_DEV_LAUNCH_LOG_MAX) and copies the first min(that, max, ARL_DEV_LAUNCH_LOG_MAX) to `out`.     */
+int32_t arl_dev_conv_launch_log(arl_dev_launch* out, int32_t max);
 
 /* Tests: with ARL_PROMO_ASSOC run the wave suffix scan at EVERY horizon <= 512 (not only where it is the faster
  * kernel).                                                                                                          */
