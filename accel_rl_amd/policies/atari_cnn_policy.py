@@ -308,14 +308,11 @@ class AtariCnnPolicy(object):
             gs = self._geoms[key] = (conv, dense)
         return gs
 
-    def _trunk(self, x, w=None, tag=""):
-        """Explicit conv/dense stack (no autograd) on NHWC memory.  Returns (conv activations
-        [B,Ho,Wo,K], hidden activations [B,units]); every activation is post bias+relu.
-        `w`: the layers' (W, b) views to use (default: the trainable ones); `tag` keeps the scratch
-        activations of a second forward (e.g. a target network) apart."""
+    def _convs(self, x, w=None, tag=""):
+        """The conv stack of _trunk: activations [B, Ho, Wo, K] of every layer, post bias + rectifier."""
         b = x.shape[0]
         w = self._w if w is None else w
-        conv_g, dense_g = self._layer_geoms(b)
+        conv_g, _ = self._layer_geoms(b)
         acts, a = [], x
         for i, (nf, ci, sz, st, pad, ho, wo) in enumerate(self._conv_geom):
             z = self._buffer(("act" + tag, i, b), (b, ho, wo, nf))
@@ -325,7 +322,18 @@ class AtariCnnPolicy(object):
                 _lib.conv2d_fwd(a, w[2 * i], w[2 * i + 1], z, conv_g[i], True, self._conv_ws)
             acts.append(z)
             a = z
-        hids, k = [], 2 * self._n_conv
+        return acts
+
+    def _trunk(self, x, w=None, tag=""):
+        """Explicit conv/dense stack (no autograd) on NHWC memory.  Returns (conv activations
+        [B,Ho,Wo,K], hidden activations [B,units]); every activation is post bias+relu.
+        `w`: the layers' (W, b) views to use (default: the trainable ones); `tag` keeps the scratch
+        activations of a second forward (e.g. a target network) apart."""
+        b = x.shape[0]
+        w = self._w if w is None else w
+        _, dense_g = self._layer_geoms(b)
+        acts = self._convs(x, w, tag)
+        hids, k, a = [], 2 * self._n_conv, acts[-1]
         for j, (hs, fan_in) in enumerate(self._hid_geom):
             hcur = self._buffer(("hid" + tag, j, b), (b, hs))
             _lib.conv2d_fwd(a, w[k], w[k + 1], hcur, dense_g[j], True, self._conv_ws)

@@ -107,22 +107,6 @@ class AtariIqnPolicy(QPolicyBase):
     def _trunk(self, x, w=None, tag=""):
         raise NotImplementedError("an implicit quantile network has no fraction-free trunk: _convs + _quantile_pass")
 
-    def _convs(self, x, w=None, tag=""):
-        """The conv stack of _trunk: activations [B, Ho, Wo, K] of every layer, post bias + rectifier."""
-        b = x.shape[0]
-        w = self._w if w is None else w
-        conv_g, _ = self._layer_geoms(b)
-        acts, a = [], x
-        for i, (nf, ci, sz, st, pad, ho, wo) in enumerate(self._conv_geom):
-            z = self._buffer(("act" + tag, i, b), (b, ho, wo, nf))
-            if isinstance(a, ObsRows):
-                _lib.conv2d_u8_fwd(a.obs, a.idx, self._scale, w[0], w[1], z, conv_g[0], True)
-            else:
-                _lib.conv2d_fwd(a, w[2 * i], w[2 * i + 1], z, conv_g[i], True, self._conv_ws)
-            acts.append(z)
-            a = z
-        return acts
-
     def _pair_geoms(self, n):
         """Geometry records of the dense layers at n = B R rows: (embedding, [hidden ...], output)."""
         key = ("iqn", n, _lib.default_route)

@@ -4,31 +4,23 @@ through learned per-weight noise scales instead of epsilon-greedy.
 
 The reference's CatDqnCnn (accel_rl/policies/dqn/networks/catdqn_cnn.py:40-99) with every DenseLayer replaced by its
 NoisyDenseLayer (policies/dqn/layers/noisy_layer.py:15-147, factorized): the hidden layers, "action_atoms" and, dueling,
-"hidden_Val_0" and "Val".  Softmax over atoms and the dueling merge are AtariCatDqnPolicy's (csrc/dqn.hip).  The noise is
-AtariNoisyNetDqnPolicy's (csrc/noisy.hip): a device generator whose seed and call counter live in `_noise_state`, one draw
-per row (common_noise=False) or per call (True; the online network's obs + next_obs pass of 2B rows counts as two calls),
-one counter advance per pass, so a replayed hipGraph draws fresh noise, the same sequence as eager calls.  Which
+"hidden_Val_0" and "Val".  Softmax over atoms and the dueling merge are AtariCatDqnPolicy's (csrc/dqn.hip).  The noisy
+layer, its forward walk, backward pass, generator, parameter order and initial draws are NoisyLayers'
+(policies/dqn/noisy_layers.py); this file holds the dueling arms, the noise launch and the fused loss.  Which
 (layer, which, element range) of the generator each e_in / e_out is: include/accel_rl_hip.h, above arl_noisy_draw.
 
 Internal layout (AtariCatDqnPolicy / QPolicyBase): the output matrix has n_actions (+ 1 value) rows of atoms, each padded
 to `atom_stride`; dueling stacks the two streams' hidden layers into ONE 2H layer and their output layers into ONE
 block-structured matrix.  W_sigma has W's layout, padding and dueling mask (off-block and padding entries and their
-gradients stay exactly zero).  Per pass: one arl_noisy_draws launch; per noisy layer the x W and (x f(e_in)) W_sigma
-products (split partial sums left unfolded) and one combine -- the dueling hidden layer has one sigma product per stream,
-each with its own f(e_in), folded by arl_noisy_duel_combine into its own columns; the stacked output layer needs no such
-split: its block-structured W_sigma reads the advantage half of x f(e_in) for the advantage rows and the value half for
-the value row.  The update's two output-layer combines and the logits round trip can be folded into the loss launch
-(arl_noisy_catdqn_loss_parts, `loss_folds_heads`, off by default; a product past the launch's split limit takes the
-unfused pair: the combines, then arl_catdqn_loss).
+gradients stay exactly zero).  Per pass: one arl_noisy_draws launch; the dueling hidden layer has one sigma product per
+stream, each with its own f(e_in), folded by arl_noisy_duel_combine into its own columns; the stacked output layer needs
+no such split: its block-structured W_sigma reads the advantage half of x f(e_in) for the advantage rows and the value
+half for the value row.  The update's two output-layer combines and the logits round trip can be folded into the loss
+launch (arl_noisy_catdqn_loss_parts, `loss_folds_heads`, off by default; a product past the launch's split limit takes
+the unfused pair: the combines, then arl_catdqn_loss).
 
-Parameters in the reference's flat order (value branch first under dueling), W, b, W_sigma, b_sigma per layer:
-FC0W, FC0b, FC0Wsigma, FC0bsigma, ..., OutputW, Outputb, OutputWsigma, Outputbsigma; dueling FCVal0*, Val*, FC0*,
-Output*.  Initial draws: the noise seed np.random.randint(1, 123456) first, then the conv layers, then the noisy layers in
-construction order (hidden..., action_atoms; dueling hidden_0, action_atoms, hidden_Val_0, Val), each NormCInit and --
-use_mu_init -- uniform W then uniform b; both sigmas sigma_0 / sqrt(fan_in).
-
-No epsilon: get_epsilon() is 0, set_epsilon is a no-op, no action call draws from np.random; serving is arl_catdqn_act on
-the noisy logits.
+Dueling parameters in the reference's flat order (value branch first): FCVal0*, Val*, FC0*, Output*; initial draws in
+construction order hidden_0, action_atoms, hidden_Val_0, Val.  Serving is arl_catdqn_act on the noisy logits.
 """
 import os
 
@@ -38,12 +30,10 @@ import torch
 from accel_rl_amd import _lib
 from accel_rl_amd.policies.atari_cnn_policy import ObsRows
 from accel_rl_amd.policies.dqn.atari_cat_dqn_policy import AtariCatDqnPolicy
-from accel_rl_amd.policies.dqn.atari_noisy_net_dqn_policy import AtariNoisyNetDqnPolicy
-
-_Noisy = AtariNoisyNetDqnPolicy
+from accel_rl_amd.policies.dqn.noisy_layers import NoisyLayers
 
 
-class AtariNoisyNetCatDqnPolicy(AtariCatDqnPolicy):
+class AtariNoisyNetCatDqnPolicy(NoisyLayers, AtariCatDqnPolicy):
 
     # True: the update's output-layer combines and the loss run as one arl_noisy_catdqn_loss_parts launch (same bits).
     # Off by default: on the MI355X the fused launch is the slower one (LABNOTES.md, "Noisy Rainbow"): it re-folds every
@@ -54,63 +44,38 @@ class AtariNoisyNetCatDqnPolicy(AtariCatDqnPolicy):
     def __init__(self, conv_filters, conv_filter_sizes, conv_strides, conv_pads, hidden_sizes=(), pixel_scale=255.,
                  n_atoms=51, dueling=False, common_noise=False, sigma_0=0.4, use_mu_init=True, factorized=True,
                  initial_param_values=None):
-        if not factorized:
-            raise NotImplementedError("noisy layers with independent (non-factorized) noise are not built "
-                                      "(INTEGRATION.md, section E)")
+        self._set_noisy(factorized, common_noise, sigma_0, use_mu_init)
         super().__init__(conv_filters, conv_filter_sizes, conv_strides, conv_pads, hidden_sizes=hidden_sizes,
                          pixel_scale=pixel_scale, epsilon=0, n_atoms=n_atoms, dueling=dueling,
                          initial_param_values=initial_param_values)
         if not len(self.hidden_sizes):
             raise NotImplementedError("the noisy categorical network is built with at least one hidden layer")
-        self.factorized, self.common_noise = True, bool(common_noise)
-        self.sigma_0, self.use_mu_init = float(sigma_0), bool(use_mu_init)
 
     def initialize(self, env_spec, device=None, **kwargs):
-        self.noise_seed = int(np.random.randint(1, 123456))      # atari_noisy_net_dqn_policy.py:44, before any weight
         if self._dueling:
             # construction order [FC0 x4, FCVal0 x4, Output Wsigma, bsigma, Val Wsigma, bsigma, Output W, b, Val W, b]
             # -> the reference's flat order (value branch first)
             self._tail_perm = [4, 5, 6, 7, 14, 15, 10, 11, 0, 1, 2, 3, 12, 13, 8, 9]
-        else:
-            n = 4 * len(self.hidden_sizes)
-            self._tail_perm = list(range(n)) + [n + 2, n + 3, n, n + 1]
         super().initialize(env_spec, device=device, **kwargs)
-        self._noise_state = torch.tensor([self.noise_seed, 0], dtype=torch.int64, device=self.device)
-        self._sigma_ws = _lib.conv_workspace(self.device)
         self._sigma_ws2 = _lib.conv_workspace(self.device) if self._dueling else None
-        self._out_ws = dict()             # pass tag -> (W, W_sigma) workspaces of a deferred output layer
-        self._noise_of = dict()
         self.fused_max_splits = _lib.noisy_catdqn_loss_limits()[0]
 
-    # ---- parameters ------------------------------------------------------------
-    _noisy_init = _Noisy._noisy_init
-
+    # ---- parameters: the dueling arms ------------------------------------------
     def _hidden_reference_init(self, fan):
-        a_n = self.n_act * self.n_atoms
-        if self._dueling:
-            hs = self.hidden_sizes[0]
-            if hs % 4:
-                raise NotImplementedError("hidden sizes must be multiples of 4 (got %d)" % hs)
-            hid = self._noisy_init(fan, hs, 1.0)                # construction order: hidden_0, action_atoms,
-            out = self._noisy_init(hs, a_n, 0.01)               # hidden_Val_0, Val (catdqn_cnn.py:58-93)
-            hid_val = self._noisy_init(fan, hs, 1.0)
-            val = self._noisy_init(hs, self.n_atoms, 0.01)
-            self._duel_head_ref = out[:2] + val[:2]
-            self._hid_geom = [(2 * hs, fan)]
-            names = ["FC0W", "FC0b", "FC0Wsigma", "FC0bsigma", "FCVal0W", "FCVal0b", "FCVal0Wsigma", "FCVal0bsigma",
-                     "OutputWsigma", "Outputbsigma", "ValWsigma", "Valbsigma"]
-            return hid + hid_val + out[2:] + val[2:], names, 2 * hs
-        ref, names, self._hid_geom = [], [], []
-        for i, hs in enumerate(self.hidden_sizes):
-            if hs % 4:
-                raise NotImplementedError("hidden sizes must be multiples of 4 (got %d)" % hs)
-            ref += self._noisy_init(fan, hs, 1.0)
-            names += ["FC%dW" % i, "FC%db" % i, "FC%dWsigma" % i, "FC%dbsigma" % i]
-            self._hid_geom.append((hs, fan))
-            fan = hs
-        out = self._noisy_init(fan, a_n, 0.01)                   # action_atoms (catdqn_cnn.py:67-74)
-        self._out_ref = out[:2]
-        return ref + out[2:], names + ["OutputWsigma", "Outputbsigma"], fan
+        if not self._dueling:
+            return super()._hidden_reference_init(fan)        # hidden..., action_atoms (catdqn_cnn.py:67-74)
+        hs = self.hidden_sizes[0]
+        if hs % 4:
+            raise NotImplementedError("hidden sizes must be multiples of 4 (got %d)" % hs)
+        hid = self._noisy_init(fan, hs, 1.0)                # construction order: hidden_0, action_atoms,
+        out = self._noisy_init(hs, self._out_units(), 0.01)  # hidden_Val_0, Val (catdqn_cnn.py:58-93)
+        hid_val = self._noisy_init(fan, hs, 1.0)
+        val = self._noisy_init(hs, self.n_atoms, 0.01)
+        self._duel_head_ref = out[:2] + val[:2]
+        self._hid_geom = [(2 * hs, fan)]
+        names = ["FC0W", "FC0b", "FC0Wsigma", "FC0bsigma", "FCVal0W", "FCVal0b", "FCVal0Wsigma", "FCVal0bsigma",
+                 "OutputWsigma", "Outputbsigma", "ValWsigma", "Valbsigma"]
+        return hid + hid_val + out[2:] + val[2:], names, 2 * hs
 
     def _head_reference_init(self, fan, n_act):
         while (self._rows * self._atom_stride) % 32 and self._atom_stride < 64:     # AtariCatDqnPolicy's padding
@@ -119,49 +84,24 @@ class AtariNoisyNetCatDqnPolicy(AtariCatDqnPolicy):
             return list(self._duel_head_ref), ["OutputW", "Outputb", "ValW", "Valb"]
         return list(self._out_ref), ["OutputW", "Outputb"]
 
-    def _hidden_internal_shapes(self):
-        shapes = [s for hs, fan_in in self._hid_geom for s in ((hs, fan_in), (hs,), (hs, fan_in), (hs,))]
-        return shapes + self._head_internal_shapes(self._hid_geom[-1][0], self.n_act)
-
-    def _dense_to(self, w, j, to_ref):
-        if j == 0:
-            return self._conv_flat_to_reference(w) if to_ref else self._conv_flat_to_internal(w)
-        return w.T
-
     def _hidden_to_reference(self, arrs):
-        if self._dueling:
-            hs = self.hidden_sizes[0]
-            w, b, ws, bs = arrs[:4]
-            out = []
-            for rows in (slice(0, hs), slice(hs, 2 * hs)):
-                out += [self._dense_to(w[rows], 0, True), b[rows], self._dense_to(ws[rows], 0, True), bs[rows]]
-            return out + self._head_to_reference(arrs[4], arrs[5])
+        if not self._dueling:
+            return super()._hidden_to_reference(arrs)
+        hs = self.hidden_sizes[0]
+        w, b, ws, bs = arrs[:4]
         out = []
-        for j in range(len(self._hid_geom)):
-            w, b, ws, bs = arrs[4 * j:4 * j + 4]
-            out += [self._dense_to(w, j, True), b, self._dense_to(ws, j, True), bs]
-        n = 4 * len(self._hid_geom)
-        return out + self._head_to_reference(arrs[n], arrs[n + 1])
+        for rows in (slice(0, hs), slice(hs, 2 * hs)):
+            out += [self._dense_to(w[rows], 0, True), b[rows], self._dense_to(ws[rows], 0, True), bs[rows]]
+        return out + self._head_to_reference(arrs[4], arrs[5])
 
     def _hidden_to_internal(self, refs):
-        if self._dueling:
-            out = [np.concatenate([self._dense_to(refs[i], 0, False), self._dense_to(refs[i + 4], 0, False)], axis=0)
-                   if i % 2 == 0 else np.concatenate([refs[i], refs[i + 4]]) for i in range(4)]
-            return out + self._head_to_internal(refs[8:12])
-        out = []
-        for j in range(len(self._hid_geom)):
-            w, b, ws, bs = refs[4 * j:4 * j + 4]
-            out += [self._dense_to(w, j, False), b, self._dense_to(ws, j, False), bs]
-        n = 4 * len(self._hid_geom)
-        return out + self._head_to_internal(refs[n:n + 2])
+        if not self._dueling:
+            return super()._hidden_to_internal(refs)
+        out = [np.concatenate([self._dense_to(refs[i], 0, False), self._dense_to(refs[i + 4], 0, False)], axis=0)
+               if i % 2 == 0 else np.concatenate([refs[i], refs[i + 4]]) for i in range(4)]
+        return out + self._head_to_internal(refs[8:12])
 
-    _k_hidden = _Noisy._k_hidden
-    _k_out_sigma = _Noisy._k_out_sigma
-
-    # ---- forward -----------------------------------------------------------
-    _convs = _Noisy._convs
-    _rows_per_draw = _Noisy._rows_per_draw
-
+    # ---- forward: the noise launch and the dueling arms -------------------------
     def _duel_sigma_geom(self, b):
         key = ("duel_sigma", b, _lib.default_route)
         if key not in self._geoms:
@@ -170,17 +110,15 @@ class AtariNoisyNetCatDqnPolicy(AtariCatDqnPolicy):
         return self._geoms[key]
 
     def _noise_buffers(self, b, tag):
-        """This pass's noise buffers: per noisy layer of the internal network (fein, feout, xs) -- dueling: the stacked
-        hidden layer's (fein_adv, fein_val, feout, xs_adv, xs_val) and the stacked output layer's (fein, feout, xs)."""
+        """Dueling: the stacked hidden layer's (fein_adv, fein_val, feout, xs_adv, xs_val) and the stacked output
+        layer's (fein, feout, xs)."""
+        if not self._dueling:
+            return super()._noise_buffers(b, tag)
         t = "n" + tag
-        if self._dueling:
-            two_h, fan = self._hid_geom[0]
-            hid = tuple(self._buffer((t, 0, k, b), (b, n)) for k, n in enumerate((fan, fan, two_h, fan, fan)))
-            out = tuple(self._buffer((t, 1, k, b), (b, n)) for k, n in enumerate((two_h, self._head_width, two_h)))
-            return [hid, out]
-        geo = [(fan_in, hs) for hs, fan_in in self._hid_geom] + [(self._hid_geom[-1][0], self._head_width)]
-        return [tuple(self._buffer((t, l, k, b), (b, n)) for k, n in enumerate((fan_in, units, fan_in)))
-                for l, (fan_in, units) in enumerate(geo)]
+        two_h, fan = self._hid_geom[0]
+        hid = tuple(self._buffer((t, 0, k, b), (b, n)) for k, n in enumerate((fan, fan, two_h, fan, fan)))
+        out = tuple(self._buffer((t, 1, k, b), (b, n)) for k, n in enumerate((two_h, self._head_width, two_h)))
+        return [hid, out]
 
     def _draw_noise(self, x_c, layers, b, tag):
         """One arl_noisy_draws launch: every e_in / e_out of the pass (the statement: include/accel_rl_hip.h)."""
@@ -201,87 +139,31 @@ class AtariNoisyNetCatDqnPolicy(AtariCatDqnPolicy):
                           (feout, None, None, units, units, l, 1)]
         _lib.noisy_draws(self._noise_state, draws, b, self._rows_per_draw(b, tag))
 
-    def _noisy_pass(self, x, w, tag, defer_output):
-        """Convs, noise, hidden layers, the output layer's two products.  Returns (output, acts, hids): output = the
-        [B, head width] noisy logits, or -- defer_output -- (W item, W_sigma item, f(e_out), b, b_sigma) for the loss
-        launch to fold (the pass's counter then advances in its last hidden combine)."""
-        b = x.shape[0]
+    def _hidden_forward(self, a, w, layers, b, tag, defer_output):
+        """Dueling: the stacked hidden layer -- one W product, one sigma product per stream, one combine."""
+        if not self._dueling:
+            return super()._hidden_forward(a, w, layers, b, tag, defer_output)
         _, dense_g = self._layer_geoms(b)
-        acts = self._convs(x, w, tag)
-        x_c = acts[-1].view(b, -1)
-        layers = self._noise_buffers(b, tag)
-        self._draw_noise(x_c, layers, b, tag)
-        a, hids = x_c, []
-        if self._dueling:
-            fa, fv, fo_h, xa, xv = layers[0]
-            fi_o, _, xs_o = layers[1]
-            two_h, fan = self._hid_geom[0]
-            h = two_h // 2
-            k = self._k_hidden(0)
-            yw = self._buffer(("nyw" + tag, 0, b), (b, two_h))
-            ys_lo, ys_hi = (self._buffer(("nys" + tag, 0, i, b), (b, h)) for i in range(2))
-            it_w = _lib.conv2d_fwd_parts(a, w[k], w[k + 1], yw, dense_g[0], False, self._conv_ws)
-            sg = self._duel_sigma_geom(b)
-            it_lo = _lib.conv2d_fwd_parts(xa, w[k + 2][:h * fan], w[k + 3][:h], ys_lo, sg, False, self._sigma_ws)
-            it_hi = _lib.conv2d_fwd_parts(xv, w[k + 2][h * fan:], w[k + 3][h:], ys_hi, sg, False, self._sigma_ws2)
-            y = self._buffer(("hid" + tag, 0, b), (b, two_h))
-            _lib.noisy_duel_combine(it_w, w[k + 1], it_lo, it_hi, w[k + 3], fo_h, y, h, True, fein_next=fi_o,
-                                    xs_next=xs_o, state=self._noise_state if defer_output else None)
-            hids.append(y)
-            a = y
-        else:
-            for l, (hs, fan_in) in enumerate(self._hid_geom):
-                fein, feout, xs = layers[l]
-                k = self._k_hidden(l)
-                yw = self._buffer(("nyw" + tag, l, b), (b, hs))
-                ys = self._buffer(("nys" + tag, l, b), (b, hs))
-                it_w = _lib.conv2d_fwd_parts(a, w[k], w[k + 1], yw, dense_g[l], False, self._conv_ws)
-                it_s = _lib.conv2d_fwd_parts(xs, w[k + 2], w[k + 3], ys, dense_g[l], False, self._sigma_ws)
-                y = self._buffer(("hid" + tag, l, b), (b, hs))
-                last_hid = l + 1 == self._n_hid
-                _lib.noisy_dense_combine(it_w, w[k + 1], it_s, w[k + 3], feout, y, True, fein_next=layers[l + 1][0],
-                                         xs_next=layers[l + 1][2],
-                                         state=self._noise_state if (defer_output and last_hid) else None)
-                hids.append(y)
-                a = y
-        # the output layer: x W and (x f(e_in)) W_sigma; folded here or (defer_output) by the loss launch
-        _, feout, xs = layers[-1]
-        k, ks_ = self._k_head, self._k_out_sigma
-        geom = self._head_geom(b)
-        if defer_output:
-            if tag not in self._out_ws:
-                self._out_ws[tag] = (_lib.conv_workspace(self.device), _lib.conv_workspace(self.device))
-            ws_w, ws_s = self._out_ws[tag]
-        else:
-            ws_w, ws_s = self._conv_ws, self._sigma_ws
-        yw = self._buffer(("nyw" + tag, "out", b), (b, self._head_width))
-        ys = self._buffer(("nys" + tag, "out", b), (b, self._head_width))
-        it_w = _lib.conv2d_fwd_parts(a, w[k], w[k + 1], yw, geom, False, ws_w)
-        it_s = _lib.conv2d_fwd_parts(xs, w[ks_], w[ks_ + 1], ys, geom, False, ws_s)
-        self._noise_of[hids[-1].data_ptr()] = layers
-        if defer_output:
-            return (it_w, it_s, feout, w[k + 1], w[ks_ + 1]), acts, hids
-        out = self._buffer(("logits" + tag, b), (b, self._head_width))
-        _lib.noisy_dense_combine(it_w, w[k + 1], it_s, w[ks_ + 1], feout, out, False, state=self._noise_state)
-        return out, acts, hids
-
-    def _logits(self, x, w=None, tag="", parts_ws=None):
-        """[B, head width] noisy logits (+ the trunk's activations); one fresh noise draw per call."""
-        if parts_ws is not None:
-            raise NotImplementedError("the noisy output layer's products are folded by the noisy loss launch")
-        return self._noisy_pass(x, self._w if w is None else w, tag, False)
+        fa, fv, fo_h, xa, xv = layers[0]
+        fi_o, _, xs_o = layers[1]
+        two_h, fan = self._hid_geom[0]
+        h = two_h // 2
+        k = self._k_hidden(0)
+        yw = self._buffer(("nyw" + tag, 0, b), (b, two_h))
+        ys_lo, ys_hi = (self._buffer(("nys" + tag, 0, i, b), (b, h)) for i in range(2))
+        it_w = _lib.conv2d_fwd_parts(a, w[k], w[k + 1], yw, dense_g[0], False, self._conv_ws)
+        sg = self._duel_sigma_geom(b)
+        it_lo = _lib.conv2d_fwd_parts(xa, w[k + 2][:h * fan], w[k + 3][:h], ys_lo, sg, False, self._sigma_ws)
+        it_hi = _lib.conv2d_fwd_parts(xv, w[k + 2][h * fan:], w[k + 3][h:], ys_hi, sg, False, self._sigma_ws2)
+        y = self._buffer(("hid" + tag, 0, b), (b, two_h))
+        _lib.noisy_duel_combine(it_w, w[k + 1], it_lo, it_hi, w[k + 3], fo_h, y, h, True, fein_next=fi_o,
+                                xs_next=xs_o, state=self._noise_state if defer_output else None)
+        return [y]
 
     def _fold_output(self, deferred, rows, out):
         """The unfused path for a deferred output layer: its combine (the counter already advanced)."""
         it_w, it_s, feout, bias, b_sigma = deferred
         _lib.noisy_dense_combine(it_w, bias, it_s, b_sigma, feout[:rows], out, False)
-
-    # ---- acting: greedy on the noisy expected Q, no host randomness ---------------
-    host_draws = _Noisy.host_draws
-    get_actions = _Noisy.get_actions
-    get_action = _Noisy.get_action
-    get_epsilon = _Noisy.get_epsilon
-    set_epsilon = _Noisy.set_epsilon
 
     # ---- training ------------------------------------------------------------
     def fused_loss_takes(self, deferred):
@@ -328,10 +210,9 @@ class AtariNoisyNetCatDqnPolicy(AtariCatDqnPolicy):
             return loss_rows, kl
 
     def _head_backward(self, dout, x, acts, hids):
-        """The noisy layers' backward, top down (see AtariNoisyNetDqnPolicy._head_backward), then the conv stack's.
-        Dueling: the stacked hidden layer's two sigma products each get their own g2 block and data gradient."""
+        """Dueling: the stacked hidden layer's two sigma products each get their own g2 block and data gradient."""
         if not self._dueling:
-            return _Noisy._head_backward(self, dout, x, acts, hids)
+            return super()._head_backward(dout, x, acts, hids)
         b = x.shape[0]
         _, dense_g = self._layer_geoms(b)
         (fa, fv, fo_h, xa, xv), (fi_o, fo_o, xs_o) = [[t[:b] for t in lay] for lay in self._noise_of[hids[-1].data_ptr()]]
