@@ -227,6 +227,11 @@ _SIGNATURES = {
     "arl_dqn_act": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "arl_dqn_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "arl_drq_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "arl_q_regress_loss": (_i32, [_vp] * 4 + [_i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
+    "arl_qlambda_scan": (_i32, [_vp] * 4 + [_f64, _f64, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "arl_ln_bwd_workspace_bytes": (_i64, []),
+    "arl_ln_relu_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp]),
+    "arl_ln_relu_bwd": (_i32, [_vp] * 5 + [_i64, _i32, _i32, _vp, _vp, _vp, _vp, C.POINTER(ArlFoldItem), _vp]),
     "arl_mdqn_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "arl_lstm_cell_fwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "arl_lstm_cell_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp]),
@@ -955,6 +960,16 @@ class FoldList(object):
             None if wt_items is None else C.cast(wt_items, _vp), n_wt, stream_ptr(stream)),
             "arl_pg_head_loss_parts")
 
+    def ln_relu_bwd(self, dy, y, z, stats, gamma, dy_masked, dz, dgamma, dbeta, workspace, stream=None):
+        """ln_relu_bwd with its two column-sum folds (dgamma, dbeta) left to run()."""
+        rows, width = _ln_rows(z, gamma, (dy, y, dz), stats)
+        assert self._n + 2 <= FOLD_MAX_ITEMS, "too many pending folds"
+        first = C.byref(self._items[self._n])
+        self._n += 2
+        _check(load().arl_ln_relu_bwd(ptr(dy), ptr(y), ptr(z), ptr(stats), ptr(gamma), rows, width, int(bool(dy_masked)),
+                                      ptr(dz), ptr(dgamma), ptr(dbeta), ptr(workspace), first, stream_ptr(stream)),
+               "arl_ln_relu_bwd")
+
     def run(self, stream=None):
         self.run_wgrads(stream)                 # (partials that were only planned)
         n, self._n = self._n, 0
@@ -1287,6 +1302,71 @@ def mdqn_loss(q, tgt_next_q, tgt_cur_q, actions, returns, terminals, is_weights,
                                 ptr(is_weights), batch, n_actions, q.numel() // batch, int(dueling), float(gamma_n),
                                 0.0 if delta_clip is None else float(delta_clip), float(tau_e), float(alpha), float(l0),
                                 ptr(dq), ptr(loss_rows), ptr(td_abs), stream_ptr(stream)), "arl_mdqn_loss")
+
+
+def q_regress_loss(q, idx, actions, returns, n_actions, delta_clip, dq, loss_rows, td_abs, stream=None):
+    """PQN: arl_dqn_loss's TD row against returns[idx] (idx None: row i); delta_clip None: squared loss."""
+    batch = loss_rows.numel()
+    _want(q, torch.float32, "q")
+    _want(actions, torch.uint8, "actions")
+    _want(returns, torch.float32, "returns")
+    if idx is not None:
+        _want(idx, torch.int32, "idx")
+        assert idx.numel() == batch, "idx size"
+    assert q.numel() == dq.numel() and q.numel() % batch == 0 and td_abs.numel() == batch, "q / dq / td_abs size"
+    _check(load().arl_q_regress_loss(ptr(q), ptr(idx), ptr(actions), ptr(returns), batch, n_actions, q.numel() // batch,
+                                     0.0 if delta_clip is None else float(delta_clip), ptr(dq), ptr(loss_rows),
+                                     ptr(td_abs), stream_ptr(stream)), "arl_q_regress_loss")
+
+
+def qlambda_scan(q, q_last, rewards, dones, discount, q_lambda, n_env, horizon, n_actions, returns, stream=None):
+    """Q(lambda) returns (arl_qlambda_scan): q [n_env * horizon, q_stride], q_last [n_env, q_stride], rows env-major."""
+    for t, n in ((q, "q"), (q_last, "q_last"), (rewards, "rewards"), (returns, "returns")):
+        _want(t, torch.float32, n)
+    if dones.dtype not in (torch.uint8, torch.bool):
+        raise TypeError("dones must be uint8/bool")
+    stride = q_last.numel() // n_env
+    assert q.numel() == n_env * horizon * stride and q_last.numel() == n_env * stride, "q / q_last size"
+    assert rewards.numel() == dones.numel() == returns.numel() == n_env * horizon, "rewards / dones / returns size"
+    _check(load().arl_qlambda_scan(ptr(q), ptr(q_last), ptr(rewards), ptr(dones), float(discount), float(q_lambda),
+                                   n_env, horizon, n_actions, stride, ptr(returns), stream_ptr(stream)),
+           "arl_qlambda_scan")
+
+
+# ---------------------------------------------------------------------------
+# LayerNorm + rectifier (csrc/layernorm.hip)
+# ---------------------------------------------------------------------------
+
+def _ln_rows(z, gamma, same, stats):
+    """(rows, width) of a LayerNorm call on z [rows][width] (any leading shape), after the size checks."""
+    width = gamma.numel()
+    rows = z.numel() // width
+    assert rows * width == z.numel() and all(t.numel() == z.numel() for t in same), "activation sizes"
+    assert stats.numel() == 2 * rows, "stats size"
+    for t in (z, gamma, stats) + tuple(same):
+        _want(t, torch.float32, "LayerNorm tensors")
+    return rows, width
+
+
+def ln_bwd_workspace(device):
+    return torch.empty(load().arl_ln_bwd_workspace_bytes() // 4, dtype=torch.float32, device=device)
+
+
+def ln_relu_fwd(z, gamma, beta, eps, y, stats, stream=None):
+    """y = max(0, gamma * xhat(z) + beta) row-wise over z [.., width]; stats [rows, 2] = (mean, rstd); z is kept."""
+    rows, width = _ln_rows(z, gamma, (y,), stats)
+    assert beta.numel() == width, "beta size"
+    _check(load().arl_ln_relu_fwd(ptr(z), ptr(gamma), ptr(beta), rows, width, float(eps), ptr(y), ptr(stats),
+                                  stream_ptr(stream)), "arl_ln_relu_fwd")
+
+
+def ln_relu_bwd(dy, y, z, stats, gamma, dy_masked, dz, dgamma, dbeta, workspace, stream=None):
+    """dz (may be dy), dgamma, dbeta of ln_relu_fwd; the column sums are folded at once (FoldList.ln_relu_bwd defers)."""
+    rows, width = _ln_rows(z, gamma, (dy, y, dz), stats)
+    assert dgamma.numel() == dbeta.numel() == width, "dgamma / dbeta size"
+    _check(load().arl_ln_relu_bwd(ptr(dy), ptr(y), ptr(z), ptr(stats), ptr(gamma), rows, width, int(bool(dy_masked)),
+                                  ptr(dz), ptr(dgamma), ptr(dbeta), ptr(workspace), None, stream_ptr(stream)),
+           "arl_ln_relu_bwd")
 
 
 # ---------------------------------------------------------------------------

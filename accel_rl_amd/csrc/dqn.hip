@@ -442,6 +442,23 @@ __global__ __launch_bounds__(256) void drq_loss_kernel(const DrqLossArgs a) {
     a.td_abs[b] = sum.p / (float)a.m;
 }
 
+// ---- regression on given targets (PQN: Q(lambda) returns computed once per batch): dqn_loss_kernel's TD row against
+// y = returns[row], minibatch rows picked by idx; one lane per sample ----
+struct QRegressArgs : DqnLossArgs {
+    const int32_t* idx;             // [B] rows of actions / returns, or null: row b
+};
+
+__global__ __launch_bounds__(256) void q_regress_loss_kernel(const QRegressArgs a) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.batch) return;
+    const int64_t src = a.idx ? (int64_t)a.idx[b] : b;
+    int act = a.actions[src];
+    if (act >= a.n_actions) act = a.n_actions - 1;                         // (never outside the row)
+    const TdTerm t = dqn_td_row(a, b, a.returns[src], act, 1.f / (float)a.batch);
+    a.loss_rows[b] = t.wloss;
+    a.td_abs[b] = t.p;
+}
+
 // ---- Munchausen DQN: dqn_loss_kernel with a soft-max bootstrap and the clipped log-policy bonus; one lane per sample ----
 // (a Munchausen target selects no action: pol_next_q's slot carries the target net on obs, [B][S]; returns: the reward)
 struct MdqnLossArgs : DqnLossArgs {
@@ -698,6 +715,21 @@ extern "C" int arl_mdqn_loss(const float* q, const float* tgt_next_q, const floa
     a.pol_next_q = tgt_cur_q; a.tau_e = tau_e; a.alpha = alpha; a.l0 = l0;
     hipLaunchKernelGGL(mdqn_loss_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     return arl::check_launch("mdqn_loss_kernel");
+}
+
+extern "C" int arl_q_regress_loss(const float* q, const int32_t* idx_or_null, const uint8_t* actions,
+                                  const float* returns, int64_t batch, int32_t n_actions, int32_t q_stride,
+                                  float delta_clip, float* dq, float* loss_rows, float* td_abs, void* stream) {
+    ARL_REQUIRE(q && actions && returns && dq && loss_rows && td_abs, ARL_E_ARG, "null pointer");
+    int rc = check_q(batch, n_actions, q_stride, 0);
+    if (rc) return rc;
+    ARL_REQUIRE(batch <= INT32_MAX, ARL_E_RANGE, "batch must stay below 2^31");
+    QRegressArgs a = {};
+    a.q = q; a.actions = actions; a.returns = returns; a.dq = dq; a.loss_rows = loss_rows; a.td_abs = td_abs;
+    a.batch = batch; a.n_actions = n_actions; a.stride = q_stride; a.dueling = 0; a.delta_clip = delta_clip;
+    a.idx = idx_or_null;
+    hipLaunchKernelGGL(q_regress_loss_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return arl::check_launch("q_regress_loss_kernel");
 }
 
 static int check_cat(int64_t batch, int n_actions, int n_atoms, int stride) {

@@ -142,10 +142,10 @@ class AtariCnnPolicy(object):
         self._k_head = 2 * len(self._conv_geom) + self._n_hidden_internal    # index of W_head in params / grads
         self._shapes = shapes
         sizes = [int(np.prod(s)) for s in shapes]
-        self._offsets, off = [], 0
-        for n in sizes:                       # every tensor starts on a 16-byte boundary
-            self._offsets.append(off)
-            off += (n + 3) // 4 * 4
+        self._offsets, off = [0] * len(sizes), 0
+        for k in self._bucket_order(len(sizes)):      # every tensor starts on a 16-byte boundary
+            self._offsets[k] = off
+            off += (sizes[k] + 3) // 4 * 4
         self._bucket_len = off
         # everything from the first dense tensor on (dense layers, heads) is final once the dense layers'
         # backward has run: the sync optimizers all-reduce that tail under the conv layers' backward
@@ -195,6 +195,11 @@ class AtariCnnPolicy(object):
             self._hid_geom.append((hs, fan))
             fan = hs
         return ref, names, fan
+
+    def _bucket_order(self, n):
+        """The tensors' order in the flat bucket's memory: the order of `_shapes`, for every policy whose conv layers own
+        nothing but (W, b) (a subclass with more tensors per conv layer keeps them ahead of grad_split_offset)."""
+        return range(n)
 
     def _hidden_internal_shapes(self):
         return [s for hs, fan_in in self._hid_geom for s in ((hs, fan_in), (hs,))]
@@ -540,6 +545,7 @@ class AtariCnnPolicy(object):
             hs, fan_in = self._hid_geom[j]
             inp = hids[j - 1] if j > 0 else acts[-1]
             d_prev = self._buffer(("dx_hid", j, b), (b, fan_in))
+            d_cur, masked = self._through_activation(self._n_conv + j, d_cur, masked, hids[j])
             self._layer_grads(d_cur, masked, hids[j], b, hs, k, dense_g[j], inp, d_prev)
             if j == 0 and dense_w_hook is not None and self._folds.last_dw_in_place:
                 job = dense_w_hook(self._offsets[k], (self._g[k].numel() + 3) // 4 * 4)
@@ -572,6 +578,7 @@ class AtariCnnPolicy(object):
         for i in range(self._n_conv - 1, -1, -1):
             nf, ci, sz, st, pad, ho, wo = self._conv_geom[i]
             d_in = self._buffer(("dx_conv", i, b), tuple(acts[i - 1].shape)) if i > 0 else None
+            d_act, masked = self._through_activation(i, d_act, masked, acts[i])
             self._layer_grads(d_act, masked, acts[i], b * ho * wo, nf, 2 * i, conv_g[i], acts[i - 1] if i > 0 else x, d_in,
                               corun=corun if i > 0 else None,
                               wt=self._wt.get(i) if _lib.default_route != _lib.ROUTE_FP32 else None, defer=group)
@@ -601,7 +608,16 @@ class AtariCnnPolicy(object):
         else:
             done = folds.conv2d_bwd_weight(d, inp, self._g[k], geom, self._fold_ws(("dw", k)), dbias=dbias, defer=defer)
         if not done:                # generic kernels leave the bias sums to the streaming kernel (its mask is idempotent)
-            folds.relu_bwd_bias_grad(d, y, rows, channels, g[k + 1], self._fold_ws(("db", k)))
+            self._bias_grad_left(d, y, rows, channels, k)
+
+    def _bias_grad_left(self, d, y, rows, channels, k):
+        self._folds.relu_bwd_bias_grad(d, y, rows, channels, self.grads[k + 1], self._fold_ws(("db", k)))
+
+    def _through_activation(self, layer, d, masked, y):
+        """Backward through what stands between layer `layer`'s contraction (conv layers first, then the dense ones) and
+        its output y: nothing here -- the rectifier's mask is applied by _layer_grads' launches, so (d, masked) pass as
+        they came; a policy with more than bias + rectifier there turns d into the contraction output's gradient."""
+        return d, masked
 
     def _fold_ws(self, key):
         """One workspace per pending fold (the partials stay live until folds.run())."""

@@ -1098,6 +1098,82 @@ int arl_mdqn_loss(const float* q, const float* tgt_next_q, const float* tgt_cur_
                   int32_t n_actions, int32_t q_stride, int32_t dueling, float gamma_n, float delta_clip, float tau_e,
                   float alpha, float l0, float* dq, float* loss_rows, float* td_abs, void* stream);
 
+/* Regression of Q on given targets (PQN, Gallici et al. 2024, "Simplifying Deep Temporal Difference Learning"; the
+ * reference has none): arl_dqn_loss's TD row against a target that is an input.  Row i of the minibatch:
+ *   src = idx_or_null ? idx_or_null[i] : i;  a = actions[src] (read as n_actions - 1 if >= n_actions);  y = returns[src]
+ *   d = y - q[i][a]
+ * and from d on everything is arl_dqn_loss's (its device code, not a copy): 0.5 d^2 or the Huber loss with threshold
+ * delta_clip (> 0), its slope, under the weight w = 1 / (float) batch; no dueling merge, no importance weights.
+ *   q, dq f32[batch][q_stride]; actions u8[n], returns f32[n] with every src < n (the caller answers for idx)
+ *   out: dq (zero outside column a), loss_rows f32[batch] (their sum is the loss), td_abs f32[batch] (|d|, clipped to
+ *        delta_clip when that is > 0)
+ * Sizes as arl_dqn_loss (1 <= n_actions <= 255, q_stride >= n_actions and % 4 == 0, 1 <= batch < 2^31; else
+ * ARL_E_RANGE); a NULL mandatory pointer: ARL_E_ARG.  A refused call launches nothing.                              */
+int arl_q_regress_loss(const float* q, const int32_t* idx_or_null, const uint8_t* actions, const float* returns,
+                       int64_t batch, int32_t n_actions, int32_t q_stride, float delta_clip, float* dq,
+                       float* loss_rows, float* td_abs, void* stream);
+
+/* Q(lambda) returns of an on-policy Q-learner (PQN), computed backwards over a rollout from the CURRENT network.  Rows
+ * env-major as in arl_gae_scan: row e * horizon + t.
+ *   q        f32[n_env * horizon][q_stride]   the network on the rollout's observations
+ *   q_last   f32[n_env][q_stride]             the network on the observations after the last step
+ *   rewards  f32[n_env * horizon]   dones u8[n_env * horizon] (0 / non-zero)   returns f32[n_env * horizon] (out)
+ * m(row) = fp32 maximum of the row's first n_actions entries (fmaxf, exact; a NaN entry is skipped).
+ * b_t = (double) m(q row (e, t + 1)) for t < T - 1, b_{T-1} = (double) m(q_last row e).  R is carried in float64, in
+ * exactly this expression order and without contraction:
+ *   t = T - 1:  R = (double) r_t + (done_t ? 0.0 : discount * b_t)
+ *   t < T - 1:  R = (double) r_t + (done_t ? 0.0 : discount * (b_t + lambda * (R_next - b_t)))
+ * and returns[e * T + t] = (float) R at every step: equal to a float64 restatement bit for bit.  One wave per env: the
+ * row maxima in parallel, one lane walks the T steps.  Indexing is 64-bit.
+ * Refused before any HIP call, nothing written: a NULL pointer (ARL_E_ARG); n_env outside 1 .. 2^31 - 1, horizon
+ * outside 1 .. 4096, n_actions outside 1 .. 64, q_stride < n_actions, not a multiple of 4 or > 2^20 (ARL_E_RANGE);
+ * discount or lambda not finite or outside [0, 1], returns overlapping an input (ARL_E_ARG); q or q_last not 16-byte,
+ * rewards or returns not 4-byte aligned (ARL_E_ALIGN).                                                               */
+int arl_qlambda_scan(const float* q, const float* q_last, const float* rewards, const uint8_t* dones, double discount,
+                     double lambda, int64_t n_env, int32_t horizon, int32_t n_actions, int32_t q_stride,
+                     float* returns, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * LayerNorm + rectifier between the contraction launches (PQN's Q-network)
+ * ------------------------------------------------------------------------- */
+
+/* Row-wise over z f32[rows][width], contiguous (NHWC conv activation: rows = B * Ho * Wo, width = channels; dense
+ * layer: rows = B, width = units); gamma, beta f32[width].  fp32, no contraction, per row in this order:
+ *   mean = (sum_j z_j) / (float) width;  var = (sum_j (z_j - mean)^2) / (float) width  (two passes over the row in
+ *   registers, biased);  rstd = 1 / sqrtf(var + eps);  xhat_j = (z_j - mean) * rstd;
+ *   y_j = max(0, gamma_j * xhat_j + beta_j)
+ * Lanes and summation order (fixed: two launches are bit-identical; DESIGN.md 22 derives the error bound from it).
+ * A row is held by LPR consecutive lanes of one wave, V float4s per lane; lane l holds float4 number v * LPR + l:
+ *   width 4 .. 32: LPR 8, V 1 | 36 .. 64: LPR 16, V 1 | 68 .. 256: LPR 64, V 1 | 260 .. 512: LPR 64, V 2 |
+ *   516 .. 1024: LPR 64, V 4
+ * A row sum: per lane s = q_0, then s = s + q_v (v ascending), q_v = ((x + y) + z) + w of float4 v (0 past the row's
+ * end); then the butterfly s = s + s[lane ^ off], off = LPR / 2, LPR / 4, .. 1, after which every lane of the row holds
+ * the same bits.  Every element passes through at most D = 4 V + log2(LPR) additions.
+ * Forward: writes y (a second buffer: z is KEPT, y == z is refused -- the backward pass recomputes xhat from z and
+ * stats, so nothing but stats, 8 bytes per row, is stored for it beyond the activations) and stats f32[rows][2] =
+ * (mean, rstd).
+ * Backward: g_j = dy_j [y_j > 0], h_j = g_j * gamma_j, xhat_j = (z_j - mean) * rstd with the forward's stats,
+ *   m1 = (sum_j h_j) / (float) width, m2 = (sum_j h_j * xhat_j) / (float) width   (row sums as above)
+ *   dz_j = rstd * ((h_j - m1) - xhat_j * m2)                        dz may be dy itself (in place) or another buffer
+ *   dgamma_j = sum_rows g_j * xhat_j,  dbeta_j = sum_rows g_j
+ * dy_masked = 1: dy already carries the mask (masked-out entries +0, as the data-gradient launches leave them): it is
+ * taken as it comes and y is not read; the mask being idempotent, the outputs equal the dy_masked = 0 call's bit for bit.
+ * The column sums: a block of 256 threads holds RPB = 256 / LPR row slots; slot k of block b adds the terms of rows
+ * b * RPB + k + i * grid * RPB, i ascending, grid = min(256, ceil(rows / RPB)); the block adds its RPB slots in slot
+ * order into one partial row, part f32[grid][width] for dgamma followed by the same for dbeta in `workspace`
+ * (>= arl_ln_bwd_workspace_bytes()); arl_fold_many adds the partial rows in its fixed order -- at once (items2_or_null
+ * NULL: a second launch here) or later (items2_or_null: two arl_fold_item are filled in, the workspace stays live until
+ * the caller's arl_fold_many).  No atomics; bit-identical run to run.  Indexing is 64-bit.
+ * Refused before any HIP call, nothing written: a NULL pointer (items2_or_null excepted), dy_masked not 0 / 1, eps not
+ * finite or <= 0, y == z (ARL_E_ARG); rows outside 1 .. 2^31 - 1, width outside 4 .. 1024 or not a multiple of 4
+ * (ARL_E_RANGE); any pointer not 16-byte aligned (ARL_E_ALIGN).                                                      */
+int64_t arl_ln_bwd_workspace_bytes(void);
+int arl_ln_relu_fwd(const float* z, const float* gamma, const float* beta, int64_t rows, int32_t width, float eps,
+                    float* y, float* stats, void* stream);
+int arl_ln_relu_bwd(const float* dy, const float* y, const float* z, const float* stats, const float* gamma,
+                    int64_t rows, int32_t width, int32_t dy_masked, float* dz, float* dgamma, float* dbeta,
+                    void* workspace, struct arl_fold_item* items2_or_null, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * LSTM cell of the recurrent policies
  * ------------------------------------------------------------------------- */
