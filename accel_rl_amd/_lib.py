@@ -233,6 +233,9 @@ _SIGNATURES = {
     "arl_ln_relu_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp]),
     "arl_ln_relu_bwd": (_i32, [_vp] * 5 + [_i64, _i32, _i32, _vp, _vp, _vp, _vp, C.POINTER(ArlFoldItem), _vp]),
     "arl_mdqn_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "arl_sacd_act": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "arl_sacd_loss": (_i32, [_vp] * 11 + [_i64, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "arl_sacd_alpha_grad": (_i32, [_vp, _i64, _vp, _f32, _vp, _vp]),
     "arl_lstm_cell_fwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "arl_lstm_cell_bwd": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp]),
     "arl_gru_cell_fwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp]),
@@ -1302,6 +1305,38 @@ def mdqn_loss(q, tgt_next_q, tgt_cur_q, actions, returns, terminals, is_weights,
                                 ptr(is_weights), batch, n_actions, q.numel() // batch, int(dueling), float(gamma_n),
                                 0.0 if delta_clip is None else float(delta_clip), float(tau_e), float(alpha), float(l0),
                                 ptr(dq), ptr(loss_rows), ptr(td_abs), stream_ptr(stream)), "arl_mdqn_loss")
+
+
+def sacd_act(logits, override, n_actions, prob, greedy=None, deterministic=False, stream=None):
+    """SAC-Discrete serving: the actor's soft-max row, or a one-hot row (deterministic / override)."""
+    batch = prob.shape[0]
+    _want(logits, torch.float32, "logits")
+    assert logits.numel() % batch == 0 and prob.numel() == batch * n_actions, "logits / prob size"
+    _check(load().arl_sacd_act(ptr(logits), ptr(override), batch, n_actions, logits.numel() // batch,
+                               int(bool(deterministic)), ptr(prob), ptr(greedy), stream_ptr(stream)), "arl_sacd_act")
+
+
+def sacd_loss(q1, q2, q1t_next, q2t_next, logits, logits_next, actions, returns, terminals, is_weights, log_alpha,
+              n_actions, gamma_n, delta_clip, dq1, dq2, dlogits, stats, stream=None):
+    """SAC-Discrete: stats f32[4][B] = q_loss_rows | td_abs | pi_loss_rows | ent_rows.  delta_clip None: squared loss."""
+    batch = actions.numel()
+    n = q1.numel()
+    assert n % batch == 0 and all(t.numel() == n for t in (q2, q1t_next, q2t_next, logits, logits_next, dq1, dq2, dlogits)), \
+        "the nine row blocks must have one size"
+    assert stats.numel() == 4 * batch and log_alpha.numel() >= 1, "stats / log_alpha size"
+    _want(log_alpha, torch.float32, "log_alpha")
+    _check(load().arl_sacd_loss(ptr(q1), ptr(q2), ptr(q1t_next), ptr(q2t_next), ptr(logits), ptr(logits_next),
+                                ptr(actions), ptr(returns), ptr(terminals), ptr(is_weights), ptr(log_alpha), batch,
+                                n_actions, n // batch, float(gamma_n), 0.0 if delta_clip is None else float(delta_clip),
+                                ptr(dq1), ptr(dq2), ptr(dlogits), ptr(stats), stream_ptr(stream)), "arl_sacd_loss")
+
+
+def sacd_alpha_grad(ent_rows, log_alpha, target_entropy, grad_out, stream=None):
+    """grad_out f32[4]: entry 0 = exp(log_alpha) * (mean(ent_rows) - target_entropy), entries 1 .. 3 = 0."""
+    _want(ent_rows, torch.float32, "ent_rows")
+    assert grad_out.numel() >= 4 and log_alpha.numel() >= 1, "grad_out / log_alpha size"
+    _check(load().arl_sacd_alpha_grad(ptr(ent_rows), ent_rows.numel(), ptr(log_alpha), float(target_entropy),
+                                      ptr(grad_out), stream_ptr(stream)), "arl_sacd_alpha_grad")
 
 
 def q_regress_loss(q, idx, actions, returns, n_actions, delta_clip, dq, loss_rows, td_abs, stream=None):

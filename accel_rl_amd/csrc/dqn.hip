@@ -309,26 +309,7 @@ __global__ __launch_bounds__(256) void catdqn_loss_kernel(const CatLossArgs a, c
 }
 
 // ---- plain DQN: Q rows f32[batch][q_stride], the first n_actions columns valid; one lane per sample ----
-// dueling: the row holds n advantages followed by the value; q_a = val + (adv_a - mean adv)
-__device__ __forceinline__ float row_mean(const float* row, int n) {
-    float sum = 0.f;
-    for (int a = 0; a < n; ++a) sum += row[a];
-    return sum / (float)n;
-}
-__device__ __forceinline__ float q_at(const float* row, int a, int n, bool dueling, float mean) {
-    return dueling ? row[n] + (row[a] - mean) : row[a];
-}
-__device__ __forceinline__ int first_argmax(const float* row, int n, bool dueling) {
-    const float mean = dueling ? row_mean(row, n) : 0.f;
-    int best = 0;
-    float best_q = q_at(row, 0, n, dueling, mean);
-    for (int a = 1; a < n; ++a) {
-        const float q = q_at(row, a, n, dueling, mean);
-        if (q > best_q) { best_q = q; best = a; }
-    }
-    return best;
-}
-
+// (row_mean, q_at, first_argmax -- the dueling merge q_a = val + (adv_a - mean adv) -- are csrc/q_loss_dev.h's)
 __global__ __launch_bounds__(256) void dqn_act_kernel(const float* __restrict__ q,
                                                       const int32_t* __restrict__ override_or_null, int64_t batch,
                                                       int n_actions, int stride, int dueling,
@@ -368,14 +349,9 @@ __device__ __forceinline__ TdTerm dqn_td_row(const DqnLossArgs& a, int64_t row, 
     const bool duel = a.dueling != 0;
     const float* qrow = a.q + row * S;
     const float d = y - q_at(qrow, act, A, duel, duel ? row_mean(qrow, A) : 0.f);
-    const float ad = fabsf(d), c = a.delta_clip;
-    float loss = 0.5f * (d * d), slope = d;                                // d loss / d d
-    if (c > 0.f && ad > c) {                                               // Huber (:157-160)
-        loss = c * (ad - c / 2.f);
-        slope = d > 0.f ? c : -c;
-    }
+    const TdLoss t = td_loss(d, a.delta_clip);
     float* dq = a.dq + row * S;
-    const float gq = -(w * slope);                                         // d = y - q, y carries no gradient
+    const float gq = -(w * t.slope);                                       // d = y - q, y carries no gradient
     for (int k = 0; k < S; ++k) dq[k] = 0.f;
     if (!duel) {
         dq[act] = gq;
@@ -384,7 +360,7 @@ __device__ __forceinline__ TdTerm dqn_td_row(const DqnLossArgs& a, int64_t row, 
         for (int k = 0; k < A; ++k) dq[k] = k == act ? gq - share : -share;
         dq[A] = gq;
     }
-    return {w * loss, c > 0.f ? fminf(ad, c) : ad};                        // :165
+    return {w * t.loss, t.p};
 }
 
 // Second half of dqn_loss_kernel and mdqn_loss_kernel: sample b's row under the weight (is_weight or 1) / batch
@@ -465,19 +441,7 @@ struct MdqnLossArgs : DqnLossArgs {
     float tau_e, alpha, l0;         // entropy temperature (> 0), bonus scale (>= 0), clip floor (<= 0)
 };
 
-// v = max_a q_a, s = sum_a expf((q_a - v) / tau_e) (a ascending, from 0) and tl = tau_e logf(s) of one row:
-// tau_e log pi_a = (q_a - v) - tl
-struct SoftRow { float v, s, tl; };
-__device__ __forceinline__ SoftRow soft_row(const float* row, int n, bool dueling, float mean, float tau_e) {
-    SoftRow r;
-    r.v = q_at(row, 0, n, dueling, mean);
-    for (int a = 1; a < n; ++a) r.v = fmaxf(r.v, q_at(row, a, n, dueling, mean));
-    r.s = 0.f;
-    for (int a = 0; a < n; ++a) r.s += expf((q_at(row, a, n, dueling, mean) - r.v) / tau_e);
-    r.tl = tau_e * logf(r.s);
-    return r;
-}
-
+// (SoftRow / soft_row -- v = max_a q_a, s, tl = tau_e logf(s) -- are csrc/q_loss_dev.h's)
 __global__ __launch_bounds__(256) void mdqn_loss_kernel(const MdqnLossArgs a) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= a.batch) return;
@@ -631,7 +595,7 @@ __global__ __launch_bounds__(256) void qrdqn_loss_kernel(const QrLossArgs a) {
 }  // namespace
 
 static int check_q(int64_t batch, int n_actions, int stride, int dueling) {
-    if (batch <= 0 || n_actions <= 0 || n_actions > 255 || stride < n_actions + (dueling != 0) || (stride & 3)) {
+    if (!arlq::q_sizes_ok(batch, n_actions, stride, dueling)) {
         arl::set_error("dqn: need batch > 0, 1 <= n_actions <= 255, q_stride >= n_actions (+ 1 if dueling) and %% 4 == 0");
         return ARL_E_RANGE;
     }

@@ -1,5 +1,6 @@
-// What the value-based loss and action kernels of csrc/dqn.hip, csrc/iqn.hip and csrc/fqf.hip share: the wave butterflies,
-// the first maximum over a staged row of Q values, one term of the pairwise quantile-Huber loss, the fixed-order combine of
+// What the value-based loss and action kernels of csrc/dqn.hip, csrc/iqn.hip, csrc/fqf.hip and csrc/sac.hip share: the wave
+// butterflies, the first maximum over a staged row of Q values, the lane-per-sample row helpers (dueling merge, first maximum,
+// soft-max sums, the TD loss of one error), one term of the pairwise quantile-Huber loss, the fixed-order combine of
 // the four waves' partial sums, the epsilon-greedy serve tail of the wave-per-sample action kernels, and -- for the kernels
 // whose quantiles are strided by a_stride (iqn.hip, fqf.hip) -- the argument record, its host-side checks, the staging of
 // the taken action's quantiles and of the targets T_j, and everything after them (loss_tail).  Internal; every device
@@ -34,6 +35,58 @@ __device__ __forceinline__ int first_max(const float* q, int n_actions) {
         if (v > best_q) { best_q = v; best = a; }
     }
     return best;
+}
+
+// ---- rows f32[stride] of action values (csrc/dqn.hip) or of actor logits (csrc/sac.hip), the first n entries valid ----
+// dueling: the row holds n advantages followed by the value; q_a = val + (adv_a - mean adv)
+__device__ __forceinline__ float row_mean(const float* row, int n) {
+    float sum = 0.f;
+    for (int a = 0; a < n; ++a) sum += row[a];
+    return sum / (float)n;
+}
+__device__ __forceinline__ float q_at(const float* row, int a, int n, bool dueling, float mean) {
+    return dueling ? row[n] + (row[a] - mean) : row[a];
+}
+__device__ __forceinline__ int first_argmax(const float* row, int n, bool dueling) {
+    const float mean = dueling ? row_mean(row, n) : 0.f;
+    int best = 0;
+    float best_q = q_at(row, 0, n, dueling, mean);
+    for (int a = 1; a < n; ++a) {
+        const float q = q_at(row, a, n, dueling, mean);
+        if (q > best_q) { best_q = q; best = a; }
+    }
+    return best;
+}
+
+// v = max_a q_a, s = sum_a expf((q_a - v) / tau_e) (a ascending, from 0) and tl = tau_e logf(s) of one row:
+// tau_e log pi_a = (q_a - v) - tl.  (tau_e == 1: the division and the product are exact)
+struct SoftRow { float v, s, tl; };
+__device__ __forceinline__ SoftRow soft_row(const float* row, int n, bool dueling, float mean, float tau_e) {
+    SoftRow r;
+    r.v = q_at(row, 0, n, dueling, mean);
+    for (int a = 1; a < n; ++a) r.v = fmaxf(r.v, q_at(row, a, n, dueling, mean));
+    r.s = 0.f;
+    for (int a = 0; a < n; ++a) r.s += expf((q_at(row, a, n, dueling, mean) - r.v) / tau_e);
+    r.tl = tau_e * logf(r.s);
+    return r;
+}
+
+// The TD error d = y - q under the threshold c (c <= 0: squared loss): the loss 0.5 d^2 or c (|d| - c / 2), its slope in
+// d, and the priority |d| (clipped to c when c > 0)
+struct TdLoss { float loss, slope, p; };
+__device__ __forceinline__ TdLoss td_loss(float d, float c) {
+    const float ad = fabsf(d);
+    float loss = 0.5f * (d * d), slope = d;                                // d loss / d d
+    if (c > 0.f && ad > c) {                                               // Huber (:157-160)
+        loss = c * (ad - c / 2.f);
+        slope = d > 0.f ? c : -c;
+    }
+    return {loss, slope, c > 0.f ? fminf(ad, c) : ad};                     // :165
+}
+
+// the sizes arl_dqn_loss and the entry points that state "sizes as arl_dqn_loss" accept
+inline bool q_sizes_ok(int64_t batch, int n_actions, int stride, int dueling) {
+    return !(batch <= 0 || n_actions <= 0 || n_actions > 255 || stride < n_actions + (dueling != 0) || (stride & 3));
 }
 
 // One term of the pairwise quantile-Huber loss at u = T_j - theta_i and fraction tau (of theta_i): rt the loss term, gt

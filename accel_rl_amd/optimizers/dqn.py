@@ -183,3 +183,79 @@ class FqfOptimizer(DqnOptimizer):
         super()._apply_update(avg_factor)
         b1, b2, eps = self._frac_kernel_args
         _lib.opt_step(self._frac_state, self._frac_method.kernel_id, self._frac_learning_rate, avg_factor, 0.0, b1, b2, eps)
+
+
+def _method_kernel_args(method, resolved):
+    """(beta1 or rho, beta2, epsilon) as arl_opt_step takes them."""
+    if method.name == "adam":
+        return resolved["beta1"], resolved["beta2"], resolved["epsilon"]
+    return resolved["rho"], 0.0, resolved["epsilon"]
+
+
+class SacOptimizer(DqnOptimizer):
+    """DqnOptimizer for AtariSacDiscretePolicy: four ranges -- the actor's bucket, the two critics' buckets and log_alpha
+    -- each with its own ArlOptState, slots, step count and norm log, each updated by one arl_opt_step inside the
+    captured update.  learning_rate, update_method, update_method_args and grad_norm_clip apply to the three networks
+    (the clip per network, on that network's own gradient norm); the temperature takes
+    alpha_args=dict(learning_rate, update_method, update_method_args) (default: the networks' learning rate and method)
+    and is never clipped.  All four gradients were taken at the parameters as they stood before any of the four
+    updates (AtariSacDiscretePolicy.sac_loss_and_grads)."""
+
+    def __init__(self, learning_rate, update_method, update_method_args=None, grad_norm_clip=None,
+                 scale_conv_grads=False, use_graph=True, alpha_args=None):
+        if scale_conv_grads:
+            raise NotImplementedError("scale_conv_grads belongs to dueling networks, which SAC-Discrete does not build")
+        super().__init__(learning_rate, update_method, update_method_args=update_method_args,
+                         grad_norm_clip=grad_norm_clip, scale_conv_grads=False, use_graph=use_graph)
+        alpha = dict(learning_rate=learning_rate, update_method=update_method, update_method_args=None)
+        unknown = set(alpha_args or ()) - set(alpha)
+        if unknown:
+            raise TypeError("unexpected alpha_args: %s" % sorted(unknown))
+        alpha.update(alpha_args or dict())
+        self._alpha_learning_rate, self._alpha_method = alpha["learning_rate"], alpha["update_method"]
+        args = alpha["update_method_args"]
+        if args is None:                    # the networks' arguments where the method is theirs, else the method's defaults
+            args = (update_method_args or dict()) if self._alpha_method is update_method else dict()
+        self._alpha_kernel_args = _method_kernel_args(self._alpha_method, self._alpha_method.resolve(**args))
+
+    def _range_state(self, n, params, grads, method):
+        """A fresh ArlOptState (and the tensors it points to) over `n` entries of params / grads."""
+        from accel_rl_amd import _lib
+        dev = params.device
+        keep = dict(slot0=torch.zeros(max(n, 4), dtype=torch.float32, device=dev),
+                    slot1=torch.zeros(max(n, 4), dtype=torch.float32, device=dev) if method.name == "adam" else None,
+                    step_count=torch.zeros(1, dtype=torch.float32, device=dev),
+                    partials=torch.zeros(_lib.OPT_PARTIALS, dtype=torch.float64, device=dev),
+                    norm_log=torch.zeros(1, dtype=torch.float32, device=dev))
+        st = _lib.ArlOptState()
+        st.n_params = n
+        st.params, st.grads = params.data_ptr(), grads.data_ptr()
+        st.slot0 = keep["slot0"].data_ptr()
+        st.slot1 = keep["slot1"].data_ptr() if keep["slot1"] is not None else None
+        st.step_count, st.lr_mult = keep["step_count"].data_ptr(), self._lr_mult.data_ptr()
+        st.partials, st.grad_norm_log = keep["partials"].data_ptr(), keep["norm_log"].data_ptr()
+        st.norm_log_len = 1                             # one update per call (_set_updates_per_call(1))
+        return st, keep
+
+    def _setup_bucket(self, target, lr_mult, givens=None):
+        from accel_rl_amd.policies.dqn.atari_sac_discrete_policy import AtariSacDiscretePolicy
+        if not isinstance(target, AtariSacDiscretePolicy):
+            raise TypeError("SacOptimizer updates an AtariSacDiscretePolicy (actor, two critics, log_alpha), got %s" %
+                            type(target).__name__)
+        super()._setup_bucket(target, lr_mult, givens)  # the actor: DqnOptimizer's own state
+        self._ranges = [(self._opt_state, None)]
+        for critic in (target.q1, target.q2):
+            self._ranges.append(self._range_state(critic.flat_params.numel(), critic.flat_params, critic.flat_grads,
+                                                  self._update_method))
+        self._alpha_range = self._range_state(1, target.log_alpha, target.log_alpha_grad, self._alpha_method)
+
+    def _apply_update(self, avg_factor=1.0):
+        from accel_rl_amd import _lib
+        b1, b2, eps = self._kernel_args
+        for st, _ in self._ranges:
+            _lib.opt_step(st, self._update_method.kernel_id, self._learning_rate, avg_factor, self._grad_norm_clip,
+                          b1, b2, eps)
+        b1, b2, eps = self._alpha_kernel_args
+        _lib.opt_step(self._alpha_range[0], self._alpha_method.kernel_id, self._alpha_learning_rate, avg_factor, 0.0,
+                      b1, b2, eps)
+        self._n_updates += 1

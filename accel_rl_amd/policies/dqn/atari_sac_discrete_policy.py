@@ -1,0 +1,212 @@
+"""Soft actor-critic for discrete actions (SAC-Discrete, Christodoulou 2019; the reference has none): a stochastic
+policy learned off-policy from the replay memory.
+
+The object itself is the ACTOR: QPolicyBase's trunk (conv stack -> dense) and one more dense MFMA call that puts out
+n_actions logits, the row padded by AtariDqnPolicy's rule (32 columns, zero weights, zero gradients); it is served by
+csrc/sac.hip:arl_sacd_act -- the soft-max row, from which the sampler's categorical kernel draws with its own uniforms,
+or (deterministic mode) a one-hot row at the first maximum.  The actor keeps no target copy.  It owns
+
+  q1, q2          two plain AtariDqnPolicy critics built from the same network arguments with independent initial
+                  draws, each with its own target bucket, gradients and scratch;
+  log_alpha       f32[4] on the device, entry 0 in use (so that an optimiser range starts 16-byte aligned), and
+  log_alpha_grad  its gradient bucket.
+
+sac_loss_and_grads is one minibatch: five forward passes, ONE loss launch (arl_sacd_loss: both critics' TD losses against
+the soft target, the actor's loss against the smaller online critic, the entropy), the temperature's gradient
+(arl_sacd_alpha_grad) and three full backward passes, each into its own flat_grads.  All four gradients are taken at the
+parameters as they stand before the update.  The parameter vector of the snapshot / resume path
+is actor | q1 | q2 | log_alpha.
+"""
+import numpy as np
+import torch
+
+from accel_rl_amd import _lib
+from accel_rl_amd.policies.atari_cnn_policy import ObsRows, _norm_c
+from accel_rl_amd.policies.dqn.atari_dqn_policy import AtariDqnPolicy
+from accel_rl_amd.policies.dqn.q_policy_base import QPolicyBase
+
+
+def split_param_vector(flat, sizes):
+    """The chunks of `flat` of the given sizes, in order; the sizes must add up to its length."""
+    flat = np.asarray(flat, np.float32).reshape(-1)
+    if flat.size != int(sum(sizes)):
+        raise ValueError("parameter vector of %d entries, expected %d (actor | q1 | q2 | log_alpha = %s)" %
+                         (flat.size, int(sum(sizes)), list(sizes)))
+    ends = np.cumsum(sizes)
+    return [flat[e - n:e] for e, n in zip(ends, sizes)]
+
+
+class AtariSacDiscretePolicy(QPolicyBase):
+
+    def __init__(self, conv_filters, conv_filter_sizes, conv_strides, conv_pads, hidden_sizes=(), pixel_scale=255.,
+                 initial_alpha=1.0, deterministic=False, dueling=False, shared_last_bias=False,
+                 initial_param_values=None):
+        if dueling:
+            raise NotImplementedError("dueling critics are not built for SAC-Discrete (INTEGRATION.md, section E)")
+        if shared_last_bias:
+            raise NotImplementedError("shared_last_bias is not built for SAC-Discrete (INTEGRATION.md, section E)")
+        if not (np.isfinite(initial_alpha) and initial_alpha > 0):
+            raise ValueError("initial_alpha must be finite and > 0")
+        super().__init__(conv_filters, conv_filter_sizes, conv_strides, conv_pads, hidden_sizes=hidden_sizes,
+                         pixel_scale=pixel_scale, initial_param_values=initial_param_values)
+        self.initial_alpha = float(initial_alpha)
+        self._deterministic = bool(deterministic)
+        net = dict(conv_filters=conv_filters, conv_filter_sizes=conv_filter_sizes, conv_strides=conv_strides,
+                   conv_pads=conv_pads, hidden_sizes=hidden_sizes, pixel_scale=pixel_scale, epsilon=0)
+        self.q1, self.q2 = AtariDqnPolicy(**net), AtariDqnPolicy(**net)
+        self._draws = dict()              # n_envs -> the uniforms of the last host_draws, [horizon][n_envs] (serve_group)
+
+    # ---- output layer: n_actions logits, stored as AtariDqnPolicy stores its Q row -------------------------------
+    def _head_reference_init(self, fan, n_act):
+        self._q_stride = (n_act + 31) // 32 * 32
+        return [_norm_c((fan, n_act), 0.01), np.zeros(n_act, np.float32)], ["OutputW", "Outputb"]
+
+    def _head_internal_shapes(self, fan, n_act):
+        return [(self._q_stride, fan), (self._q_stride,)]
+
+    def _head_to_reference(self, wh, bh):
+        return [wh[:self.n_act].T, bh[:self.n_act]]
+
+    def _head_to_internal(self, ref_tail):
+        w = np.zeros((self._q_stride, ref_tail[0].shape[0]), np.float32)
+        b = np.zeros(self._q_stride, np.float32)
+        w[:self.n_act] = ref_tail[0].T
+        b[:self.n_act] = ref_tail[1]
+        return [w, b]
+
+    @property
+    def _head_width(self):
+        return self._q_stride
+
+    def initialize(self, env_spec, device=None, **kwargs):
+        init, self.initial_param_values = self.initial_param_values, None      # (the whole vector: set below)
+        super().initialize(env_spec, device=device, **kwargs)
+        self.initial_param_values = init
+        del self.flat_target, self._w_target                                   # the actor has no target copy
+        for critic in (self.q1, self.q2):
+            critic.initialize(env_spec, device=self.device, **kwargs)
+        self.log_alpha = torch.zeros(4, dtype=torch.float32, device=self.device)
+        self.log_alpha[0] = float(np.log(self.initial_alpha))
+        self.log_alpha_grad = torch.zeros(4, dtype=torch.float32, device=self.device)
+        self._actor_n_params = self.n_params
+        self.n_params = self._actor_n_params + self.q1.n_params + self.q2.n_params + 1
+        if init is not None:
+            self.set_param_values(init)
+
+    # ---- serving -------------------------------------------------------------------------------------------------
+    def _serve(self, out, override, onehot, greedy=None):
+        _lib.sacd_act(out, override, self.n_act, onehot, greedy, deterministic=self._deterministic)
+
+    def serve_supported(self):
+        return False
+
+    def set_deterministic(self, flag):
+        """Serve the first maximum of the logits (evaluation) instead of the soft-max row."""
+        self._deterministic = bool(flag)
+
+    def get_deterministic(self):
+        return self._deterministic
+
+    def set_epsilon(self, value):
+        pass                                  # (no epsilon-greedy: the policy is stochastic by itself)
+
+    def get_epsilon(self):
+        return 0.
+
+    def host_draws(self, horizon, n_envs, n_groups=2):
+        """One rollout's action randomness: the reference-order uniforms np.random.rand(horizon * n_envs), which the
+        sampler feeds its categorical kernel, and an override table that forces nothing (all -1)."""
+        u = np.random.rand(horizon * n_envs)
+        self._select_overrides(horizon, n_envs, lambda: (
+            torch.full((horizon, n_envs), -1, dtype=torch.int32).pin_memory(),
+            torch.full((horizon, n_envs), -1, dtype=torch.int32, device=self.device)))
+        self._draws[n_envs] = u.reshape(horizon, n_envs)
+        return u
+
+    def serve_group(self, observations, row0, n_envs):
+        """QPolicyBase.serve_group for a sampler that feeds its categorical kernel the uniform 0.5: the group's actions
+        are drawn here, from the group's slice of host_draws' uniforms, and served as one-hot rows."""
+        with torch.no_grad():
+            b = observations.shape[0]
+            u = self._draws[n_envs]
+            if self._step >= u.shape[0] or row0 + b > u.shape[1]:
+                raise IndexError("serve_group: step %d / rows %d..%d outside the %s draws" %
+                                 (self._step, row0, row0 + b, tuple(u.shape)))
+            logits = self._logits(self._scaled(observations))[0]
+            prob = torch.empty((b, self.n_act), dtype=torch.float32, device=self.device)
+            self._serve(logits, None, prob)
+            if not self._deterministic:
+                acts = torch.empty(b, dtype=torch.uint8, device=self.device)
+                _lib.sample_categorical(prob, torch.from_numpy(u[self._step, row0:row0 + b].copy()).to(self.device), acts)
+                self._serve(logits, acts.to(torch.int32), prob)
+            return prob, torch.zeros(b, dtype=torch.float32, device=self.device)
+
+    def get_actions(self, observations, deterministic=False):
+        if deterministic or self._deterministic:
+            return self.greedy_actions(observations).cpu().numpy(), dict()
+        return self._sample(self.prob_value(observations)[0]).cpu().numpy(), dict()
+
+    def get_action(self, observation, deterministic=False):
+        return int(self.get_actions(observation[None], deterministic)[0][0]), dict()
+
+    def update_target(self):
+        self.q1.update_target()
+        self.q2.update_target()
+
+    # ---- parameters: actor | q1 | q2 | log_alpha -------------------------------------------------------------------
+    def _param_sizes(self):
+        return [self._actor_n_params, self.q1.n_params, self.q2.n_params, 1]
+
+    def get_param_values(self, trainable=True):
+        return np.concatenate([self.bucket_to_reference(self.flat_params), self.q1.get_param_values(),
+                               self.q2.get_param_values(), self.log_alpha[:1].cpu().numpy()]).astype(np.float32)
+
+    def set_param_values(self, flat, trainable=True):
+        actor, q1, q2, log_alpha = split_param_vector(flat, self._param_sizes())
+        ref, pos = [], 0
+        for s in self._ref_shapes:
+            n = int(np.prod(s))
+            ref.append(actor[pos:pos + n].reshape(s))
+            pos += n
+        self._set_from_reference_arrays(ref)
+        self.q1.set_param_values(q1)
+        self.q2.set_param_values(q2)
+        self.log_alpha[:1].copy_(torch.from_numpy(log_alpha.copy()))
+
+    # ---- training ------------------------------------------------------------------------------------------------
+    def sac_loss_and_grads(self, obs, next_obs, actions, returns, terminals, is_weights, gamma_n, delta_clip,
+                           target_entropy):
+        """One minibatch of SacDiscrete.build_loss: the actor on obs and next_obs (u8 observations: ONE pass over the 2B
+        rows of _pair_rows, the first half's activations kept), each critic online on obs (activations kept) and its
+        target on next_obs, csrc/sac.hip:arl_sacd_loss and arl_sacd_alpha_grad, then three full backward passes -- into
+        flat_grads, q1.flat_grads, q2.flat_grads -- and log_alpha_grad.  Returns stats f32[4][B]: q_loss_rows | td_abs |
+        pi_loss_rows | ent_rows (the first two: the (2, B) pair DqnOptimizer's statistics ring takes at once).  No host
+        synchronisation and no allocation outside _buffer: it runs inside the captured update graph."""
+        with torch.no_grad():
+            b = obs.shape[0]
+            if self._u8:
+                both = self._pair_rows(obs, next_obs)
+                out2, acts2, hids2 = self._logits(ObsRows(both, None), tag="2")
+                x, logits, logits_next = ObsRows(both[:b], None), out2[:b], out2[b:]
+                acts, hids = [a[:b] for a in acts2], [h[:b] for h in hids2]
+                obs, next_obs = both[:b], both[b:]
+            else:
+                logits_next = self._logits(self._scaled(next_obs, tag="n"), tag="d")[0]
+                x = self._scaled(obs)
+                logits, acts, hids = self._logits(x)
+            passes = []
+            for critic in (self.q1, self.q2):
+                tgt = critic._logits(critic._scaled(next_obs, tag="n"), w=critic._w_target, tag="t")[0]
+                xq = critic._scaled(obs)
+                q, qacts, qhids = critic._logits(xq)
+                passes.append((critic, xq, q, qacts, qhids, tgt, critic._buffer(("dlogits", b), tuple(q.shape))))
+            (_, _, q1, _, _, t1, dq1), (_, _, q2, _, _, t2, dq2) = passes
+            dlogits = self._buffer(("dlogits", b), tuple(logits.shape))
+            stats = self._buffer(("sac_stats", b), (4, b))
+            _lib.sacd_loss(q1, q2, t1, t2, logits, logits_next, actions, returns, terminals, is_weights, self.log_alpha,
+                           self.n_act, gamma_n, delta_clip, dq1, dq2, dlogits, stats)
+            _lib.sacd_alpha_grad(stats[3], self.log_alpha, target_entropy, self.log_alpha_grad)
+            self._head_backward(dlogits, x, acts, hids)
+            for critic, xq, _, qacts, qhids, _, dq in passes:
+                critic._head_backward(dq, xq, qacts, qhids)
+            return stats

@@ -1113,6 +1113,67 @@ int arl_q_regress_loss(const float* q, const int32_t* idx_or_null, const uint8_t
                        int64_t batch, int32_t n_actions, int32_t q_stride, float delta_clip, float* dq,
                        float* loss_rows, float* td_abs, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Soft actor-critic for discrete actions (SAC-Discrete)
+ * ------------------------------------------------------------------------- */
+
+/* SAC-Discrete (Christodoulou 2019, "Soft Actor-Critic for Discrete Action Settings"; the reference has none): an actor
+ * that puts out one logit per action, two critics with a target copy each, and a learned temperature alpha =
+ * expf(log_alpha).  csrc/sac.hip.  Every row is f32[batch][stride] as arl_dqn_loss's: stride % 4 == 0, stride >=
+ * n_actions (<= 255); padding columns are ignored on input and written as exact zeros on output.  For a row z[0 .. A) of
+ * logits, with v, c_a, e_a, s, lp_a, pi_a as defined at arl_miqn_loss and tau_e = 1 (the device code arl_mdqn_loss runs;
+ * fp32, expf / logf of the device library):
+ *   m = max_a z_a;  e_a = expf(z_a - m);  s = sum_a e_a, a ascending, the sum starts at 0
+ *   lp_a = (z_a - m) - logf(s)   (finite where pi_a underflows to 0);   pi_a = e_a / s
+ * One lane per sample in all three entry points; every sum over the actions is taken inside the lane, a ascending, from 0.
+ *
+ * Action serving.  prob f32[batch][n_actions] (compact, as arl_dqn_act's onehot):
+ *   deterministic == 0:  prob[b][a] = pi_a -- the sampler's categorical kernel (arl_sample_categorical) draws from it
+ *   deterministic != 0:  a one-hot row at the FIRST maximum of the logits
+ *   override_or_null[b] >= 0 forces a one-hot row at that action in either mode
+ *   greedy_or_null[b] = the first maximum in either mode
+ * Sizes as arl_dqn_act without dueling, batch < 2^31 (ARL_E_RANGE); NULL logits or prob: ARL_E_ARG.                    */
+int arl_sacd_act(const float* logits, const int32_t* override_or_null, int64_t batch, int32_t n_actions,
+                 int32_t stride, int32_t deterministic, float* prob, uint8_t* greedy_or_null, void* stream);
+
+/* The critics', the actor's and the entropy's rows of one minibatch, in ONE launch.  q1, q2: the online critics on obs;
+ * q1t_next, q2t_next: the TARGET critics on next_obs; logits, logits_next: the actor on obs and on next_obs; log_alpha
+ * f32[1] on the device, read inside the kernel (a captured graph sees every update of it).  Per sample b, with
+ * alpha = expf(log_alpha[0]), w = (is_weight_b or 1) / (float) batch, keep = 1 - terminal_b, pi', lp' of logits_next and
+ * pi, lp of logits:
+ *   soft   = sum_a pi'_a * (fminf(q1t_next_a, q2t_next_a) - alpha * lp'_a)          a ascending, the sum starts at 0
+ *   y      = returns_b + keep * (gamma_n * soft)                                    (in this order)
+ *   d_i    = y - q_i[actions_b],  i = 1, 2
+ *   the loss L(d_i) (0.5 d^2, or the Huber loss with threshold delta_clip > 0), its slope into dq_i[actions_b] and the
+ *   clipped |d_i| = p_i exactly as arl_dqn_loss computes them (the same device function) under the weight w; every
+ *   other column of dq_i: exact zero
+ *   stats[0][b] = q_loss_rows = w * L(d_1) + w * L(d_2);   stats[1][b] = td_abs = (p_1 + p_2) / 2
+ *   g_a    = alpha * lp_a - fminf(q1_a, q2_a);   J = sum_a pi_a * g_a                a ascending, the sum starts at 0
+ *   dlogits[b][k] = (pi_k * (g_k - J)) / (float) batch,  k < n_actions;  exact zeros in the padding
+ *   stats[2][b] = pi_loss_rows = J / (float) batch;   stats[3][b] = ent_rows = -(sum_a pi_a * lp_a)
+ * stats is f32[4][batch], contiguous: its first two rows are the adjacent (loss rows | priorities) pair of arl_dqn_loss's
+ * callers.  The actor's loss sends no gradient into the critics and is not importance-weighted.  actions_b >= n_actions
+ * is read as n_actions - 1.  With log_alpha = -inf (alpha == 0), q2t_next == q1t_next and logits_next ahead at the
+ * maximum of q1t_next by a gap of at least 88: soft == that maximum, and dq1 and td_abs equal arl_dqn_loss's on
+ * (q1, q1t_next) (pol_next_q NULL) bit for bit.  No atomics: two launches on the same inputs give the same bits.
+ * Sizes as arl_dqn_loss without dueling, batch < 2^31 (ARL_E_RANGE); a NULL mandatory pointer, gamma_n or delta_clip not
+ * finite: ARL_E_ARG.  A refused call launches nothing and writes nothing.                                              */
+int arl_sacd_loss(const float* q1, const float* q2, const float* q1t_next, const float* q2t_next, const float* logits,
+                  const float* logits_next, const uint8_t* actions, const float* returns, const uint8_t* terminals,
+                  const float* is_weights_or_null, const float* log_alpha, int64_t batch, int32_t n_actions,
+                  int32_t stride, float gamma_n, float delta_clip, float* dq1, float* dq2, float* dlogits, float* stats,
+                  void* stream);
+
+/* Gradient of the temperature loss alpha * (H - H_target) with respect to log_alpha, H the batch mean of arl_sacd_loss's
+ * ent_rows (entropy above the target lowers alpha):
+ *   grad_out[0] = expf(log_alpha[0]) * (S / (float) batch - target_entropy);   grad_out[1 .. 3] = 0
+ * grad_out f32[4] (a 16-byte optimiser range with one entry in use).  Summation order of S, fixed and atomic-free: ONE
+ * 256-thread workgroup; thread t adds ent_rows[t], ent_rows[t + 256], ... to 0 in ascending order; the 256 partial sums
+ * p_t are then folded as p_t += p_{t + h} for t < h, h = 128, 64, ... 1, and S = p_0.  1 <= batch < 2^31 (ARL_E_RANGE);
+ * a NULL pointer or a target_entropy that is not finite: ARL_E_ARG.  A refused call launches nothing.                  */
+int arl_sacd_alpha_grad(const float* ent_rows, int64_t batch, const float* log_alpha, float target_entropy,
+                        float* grad_out, void* stream);
+
 /* Q(lambda) returns of an on-policy Q-learner (PQN), computed backwards over a rollout from the CURRENT network.  Rows
  * env-major as in arl_gae_scan: row e * horizon + t.
  *   q        f32[n_env * horizon][q_stride]   the network on the rollout's observations
