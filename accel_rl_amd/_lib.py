@@ -229,6 +229,7 @@ _SIGNATURES = {
     "arl_drq_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "arl_q_regress_loss": (_i32, [_vp] * 4 + [_i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
     "arl_qlambda_scan": (_i32, [_vp] * 4 + [_f64, _f64, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "arl_vtrace_scan": (_i32, [_vp] * 7 + [_f64] * 5 + [_i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "arl_ln_bwd_workspace_bytes": (_i64, []),
     "arl_ln_relu_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp]),
     "arl_ln_relu_bwd": (_i32, [_vp] * 5 + [_i64, _i32, _i32, _vp, _vp, _vp, _vp, C.POINTER(ArlFoldItem), _vp]),
@@ -1366,6 +1367,30 @@ def qlambda_scan(q, q_last, rewards, dones, discount, q_lambda, n_env, horizon, 
     _check(load().arl_qlambda_scan(ptr(q), ptr(q_last), ptr(rewards), ptr(dones), float(discount), float(q_lambda),
                                    n_env, horizon, n_actions, stride, ptr(returns), stream_ptr(stream)),
            "arl_qlambda_scan")
+
+
+def vtrace_scan(prob, old_prob, actions, values, last_values, rewards, dones, discount, vtrace_lambda, rho_bar, c_bar,
+                pg_rho_bar, n_env, horizon, returns, advantages, stats=None, stream=None):
+    """V-trace targets and advantages (arl_vtrace_scan): prob, old_prob [n_env * horizon, n_actions], rows env-major;
+    stats (optional) f32 [n_env, 2] = (sum of the ratios, steps with ratio > rho_bar) per env."""
+    for t, n in ((prob, "prob"), (old_prob, "old_prob"), (values, "values"), (last_values, "last_values"),
+                 (rewards, "rewards"), (returns, "returns"), (advantages, "advantages")):
+        _want(t, torch.float32, n)
+    _want(actions, torch.uint8, "actions")
+    if dones.dtype not in (torch.uint8, torch.bool):
+        raise TypeError("dones must be uint8/bool")
+    steps = n_env * horizon
+    n_actions = prob.numel() // steps
+    assert prob.numel() == old_prob.numel() == steps * n_actions, "prob / old_prob size"
+    assert actions.numel() == values.numel() == rewards.numel() == dones.numel() == steps, "per-step input sizes"
+    assert last_values.numel() == n_env and returns.numel() == advantages.numel() == steps, "last_values / output sizes"
+    if stats is not None:
+        _want(stats, torch.float32, "stats")
+        assert stats.numel() == 2 * n_env, "stats size"
+    _check(load().arl_vtrace_scan(ptr(prob), ptr(old_prob), ptr(actions), ptr(values), ptr(last_values), ptr(rewards),
+                                  ptr(dones), float(discount), float(vtrace_lambda), float(rho_bar), float(c_bar),
+                                  float(pg_rho_bar), n_env, horizon, n_actions, ptr(returns), ptr(advantages), ptr(stats),
+                                  stream_ptr(stream)), "arl_vtrace_scan")
 
 
 # ---------------------------------------------------------------------------

@@ -157,6 +157,36 @@ class PpoOptimizer(BaseOptimizer):
         return "single"
 
 
+class VtraceOptimizer(PpoOptimizer):
+    """PpoOptimizer whose every epoch starts with a call back into the algorithm: `_epoch_hook(epoch)` runs before the
+    first minibatch of each epoch, epoch 0 included (IMPALA recomputes its V-trace targets there from the parameters as
+    they stand, into the tensors the minibatches gather from).  The host side is the parent's: prepare_host draws every
+    epoch's permutations up front.  minibatch_size None = the whole batch, one update per epoch (known at the first
+    prepare_host)."""
+
+    _epoch_hook = None          # set by the algorithm (IMPALA.initialize); None: plain PpoOptimizer epochs
+
+    def prepare_host(self, data_length):
+        if self._minibatch_size is None:
+            self._minibatch_size = int(data_length)
+        super().prepare_host(data_length)
+
+    def device_updates(self, inputs):
+        data = dict(zip(self._input_names, inputs))
+        if not self._n_minibatches:
+            return [], []
+        _lib.copy_bytes(self._idx_dev, self._idx_host)
+        per_epoch = self._n_minibatches // self._epochs
+        losses = []
+        for k in range(self._n_minibatches):
+            if k % per_epoch == 0 and self._epoch_hook is not None:
+                self._epoch_hook(k // per_epoch)
+            losses.append(self._backward(self._losses, self._minibatch(data, self._idx_dev[k])))
+            self._share_grad()
+            self._apply_update(self._avg_factor())
+        return losses, self._recent_grad_norms(self._n_minibatches)
+
+
 class TrajPpoOptimizer(PpoOptimizer):
     """PPO for recurrent policies: epochs x minibatches of WHOLE trajectory segments (optimizers/util.py:21-32,
     iterate_traj_idxs; the reference's own PpoOptimizer slices rows and cuts trajectories apart).  `minibatch_size`

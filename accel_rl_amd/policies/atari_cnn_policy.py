@@ -360,6 +360,25 @@ class AtariCnnPolicy(object):
             _lib.pg_head_infer(hids[-1], self.params[-2], self.params[-1], prob, value)
             return prob, value
 
+    def prob_value_rows(self, observations, rows_per_pass=None, tag="rows"):
+        """(prob f32 [n, A], value f32 [n]): the current network on u8 observations [n, C, H, W], apart from the training
+        pass's activations; in passes of rows_per_pass rows (None: one pass) so that a whole rollout fits the scratch
+        buffers of one.  `tag` names the scratch and the results: two calls whose results must live together take two
+        tags.  The kernels and the arithmetic per row are prob_value's."""
+        if not tag:
+            raise ValueError("prob_value_rows needs a tag of its own: the empty one is the training pass's scratch")
+        with torch.no_grad():
+            n = observations.shape[0]
+            step = n if not rows_per_pass else min(n, int(rows_per_pass))
+            prob = self._buffer(("pv_prob" + tag, n), (n, self.n_act))
+            value = self._buffer(("pv_value" + tag, n), (n,))
+            for lo in range(0, n, step):
+                rows = observations[lo:min(lo + step, n)]
+                _, hids = self._trunk(self._scaled(rows, tag=tag), tag=tag)
+                _lib.pg_head_infer(hids[-1], self.params[-2], self.params[-1], prob[lo:lo + rows.shape[0]],
+                                   value[lo:lo + rows.shape[0]])
+            return prob, value
+
     # ------------------------------------------------- serving inside the env step's launch
     def serve_supported(self):
         """Can GpuVecSampler hand this policy's output layers to arl_env_step_served?  Only the plain feed-forward

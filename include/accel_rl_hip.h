@@ -1194,6 +1194,45 @@ int arl_qlambda_scan(const float* q, const float* q_last, const float* rewards, 
                      double lambda, int64_t n_env, int32_t horizon, int32_t n_actions, int32_t q_stride,
                      float* returns, void* stream);
 
+/* V-trace value targets and policy-gradient advantages (IMPALA, Espeholt et al. 2018), computed backwards over a
+ * rollout from the CURRENT network against the behaviour policy the sampler recorded.  Rows env-major as in
+ * arl_gae_scan: row e * horizon + t.
+ *   prob         f32[n_env * horizon][n_actions]   the current policy on the rollout's observations (arl_pg_head_infer)
+ *   old_prob     f32[n_env * horizon][n_actions]   the behaviour policy
+ *   actions      u8[n_env * horizon]               a byte >= n_actions is read as n_actions - 1
+ *   values       f32[n_env * horizon]              the current value head on the rollout's observations
+ *   last_values  f32[n_env]                        ... on the observations after the last step
+ *   rewards      f32[n_env * horizon]   dones u8[n_env * horizon] (0 / non-zero)
+ *   returns      f32[n_env * horizon] (out)        the value targets vs
+ *   advantages   f32[n_env * horizon] (out)        the policy-gradient advantages, importance weight included
+ *   stats_or_null f32[n_env][2] (out, optional)    [0] = the sum of ratio over the env's steps, added in float64 in walk
+ *                                                  order (t = T - 1 .. 0, from 0.0) and rounded once; [1] = the number of
+ *                                                  steps with ratio > rho_bar
+ * Everything is float64, in exactly this expression order and without contraction.  Per step, a = min(actions[row],
+ * n_actions - 1), p = prob[row][a], m = old_prob[row][a]:
+ *   ratio = ((double) p + 1e-8) / ((double) m + 1e-8)
+ *   rho = ratio < rho_bar ? ratio : rho_bar;  cw = ratio < c_bar ? ratio : c_bar;  pg = ratio < pg_rho_bar ? ratio : pg_rho_bar
+ *   g   = done_t ? 0.0 : discount
+ * The walk runs t = T - 1 .. 0 per env; acc_next and vs_next are carried as doubles, never as the rounded floats that
+ * were stored.  At t = T - 1: acc_next = 0.0, v_next = vs_next = (double) last_values[e]; below, v_next = (double) V_{t+1}.
+ *   q_v   = (double) r_t + g * v_next
+ *   delta = rho * (q_v - (double) V_t)
+ *   acc   = delta + ((g * (lambda * cw)) * acc_next)
+ *   vs    = (double) V_t + acc
+ *   adv   = pg * (((double) r_t + g * vs_next) - (double) V_t)
+ *   returns[row] = (float) vs;  advantages[row] = (float) adv
+ * equal to a float64 restatement bit for bit (float64 division is correctly rounded).  Inputs are taken as finite
+ * (probabilities >= 0): nothing is checked on the device.  One wave per env: ratios in parallel, one lane walks the T
+ * steps; no atomics, two launches give the same bits.  Indexing is 64-bit.
+ * Refused before any HIP call, nothing written: a NULL pointer other than stats_or_null (ARL_E_ARG); n_env outside
+ * 1 .. 2^31 - 1, horizon outside 1 .. 4096, n_actions outside 1 .. ARL_MAX_ACTIONS (ARL_E_RANGE); discount or lambda not
+ * finite or outside [0, 1], rho_bar, c_bar or pg_rho_bar not finite or <= 0, an output overlapping an input or another
+ * output (ARL_E_ARG); a float pointer not 4-byte aligned (ARL_E_ALIGN).                                              */
+int arl_vtrace_scan(const float* prob, const float* old_prob, const uint8_t* actions, const float* values,
+                    const float* last_values, const float* rewards, const uint8_t* dones, double discount, double lambda,
+                    double rho_bar, double c_bar, double pg_rho_bar, int64_t n_env, int32_t horizon, int32_t n_actions,
+                    float* returns, float* advantages, float* stats_or_null, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * LayerNorm + rectifier between the contraction launches (PQN's Q-network)
  * ------------------------------------------------------------------------- */
