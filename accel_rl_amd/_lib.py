@@ -233,6 +233,10 @@ _SIGNATURES = {
     "arl_ln_bwd_workspace_bytes": (_i64, []),
     "arl_ln_relu_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp]),
     "arl_ln_relu_bwd": (_i32, [_vp] * 5 + [_i64, _i32, _i32, _vp, _vp, _vp, _vp, C.POINTER(ArlFoldItem), _vp]),
+    "arl_maxpool3s2_fwd": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "arl_maxpool3s2_bwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "arl_add_relu": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "arl_gather_scale_obs_nhwc_any": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp]),
     "arl_mdqn_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "arl_sacd_act": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "arl_sacd_loss": (_i32, [_vp] * 11 + [_i64, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp]),
@@ -1427,6 +1431,72 @@ def ln_relu_bwd(dy, y, z, stats, gamma, dy_masked, dz, dgamma, dbeta, workspace,
     _check(load().arl_ln_relu_bwd(ptr(dy), ptr(y), ptr(z), ptr(stats), ptr(gamma), rows, width, int(bool(dy_masked)),
                                   ptr(dz), ptr(dgamma), ptr(dbeta), ptr(workspace), None, stream_ptr(stream)),
            "arl_ln_relu_bwd")
+
+
+# ---------------------------------------------------------------------------
+# Max pooling and the residual sum of the IMPALA residual network (csrc/resnet.hip); activations NHWC
+# ---------------------------------------------------------------------------
+
+def maxpool3s2_out_hw(in_h, in_w):
+    return (in_h - 1) // 2 + 1, (in_w - 1) // 2 + 1
+
+
+def _pool_dims(z, y):
+    """(batch, in_h, in_w, channels) of a pooling call on z [B, H, W, C] and y [B, Ho, Wo, C], after the shape checks."""
+    b, h, w, c = z.shape
+    assert tuple(y.shape) == (b,) + maxpool3s2_out_hw(h, w) + (c,), "pooled shape"
+    return b, h, w, c
+
+
+def maxpool3s2_fwd(z, y, y_relu=None, arg=None, stream=None):
+    """y = the 3 x 3 / stride 2 / pad 1 maximum of z f32[B, H, W, C]; y_relu = max(y, 0); arg u8 = the window position
+    3 ky + kx of the first maximum (maxpool3s2_bwd's input)."""
+    b, h, w, c = _pool_dims(z, y)
+    _want(z, torch.float32, "z")
+    _want(y, torch.float32, "y")
+    if y_relu is not None:
+        _want(y_relu, torch.float32, "y_relu")
+        assert y_relu.shape == y.shape, "y_relu shape"
+    if arg is not None:
+        _want(arg, torch.uint8, "arg")
+        assert arg.shape == y.shape, "arg shape"
+    _check(load().arl_maxpool3s2_fwd(ptr(z), b, h, w, c, ptr(y), ptr(y_relu), ptr(arg), stream_ptr(stream)),
+           "arl_maxpool3s2_fwd")
+
+
+def maxpool3s2_bwd(dy, arg, dz, stream=None):
+    """dz f32[B, H, W, C] = the gradient of maxpool3s2_fwd's input, given dy and arg of its output's shape."""
+    b, h, w, c = _pool_dims(dz, dy)
+    _want(dy, torch.float32, "dy")
+    _want(dz, torch.float32, "dz")
+    _want(arg, torch.uint8, "arg")
+    assert arg.shape == dy.shape, "arg shape"
+    _check(load().arl_maxpool3s2_bwd(ptr(dy), ptr(arg), b, h, w, c, ptr(dz), stream_ptr(stream)), "arl_maxpool3s2_bwd")
+
+
+def gather_scale_obs_nhwc_any(obs, idx, out, scale, stream=None):
+    """obs u8[n,C,H,W] (rows optionally picked by idx) -> out f32 with NHWC memory, [B,H,W,C rounded up to 4] contiguous,
+    the padding channels zero; any C, H, W (gather_scale_obs_nhwc: the fast path of four 16-byte-multiple planes)."""
+    _want(obs, torch.uint8, "obs")
+    _want(out, torch.float32, "out")
+    if idx is not None:
+        _want(idx, torch.int32, "idx")
+        assert idx.numel() == out.shape[0], "idx length"
+    else:
+        assert obs.shape[0] == out.shape[0], "obs rows"
+    batch = out.shape[0]
+    channels, plane = obs.shape[1], obs.shape[2] * obs.shape[3]
+    assert out.numel() == batch * plane * ((channels + 3) // 4 * 4), "out size"
+    _check(load().arl_gather_scale_obs_nhwc_any(ptr(obs), ptr(idx), batch, channels, plane, float(scale), out.data_ptr(),
+                                                stream_ptr(stream)), "arl_gather_scale_obs_nhwc_any")
+
+
+def add_relu(a, b, out, relu=None, stream=None):
+    """out = a + b (out may be a or b); relu = max(out, 0) when given."""
+    for t in (a, b, out) + (() if relu is None else (relu,)):
+        _want(t, torch.float32, "add_relu tensors")
+        assert t.numel() == a.numel(), "sizes"
+    _check(load().arl_add_relu(ptr(a), ptr(b), a.numel(), ptr(out), ptr(relu), stream_ptr(stream)), "arl_add_relu")
 
 
 # ---------------------------------------------------------------------------

@@ -121,6 +121,7 @@ class AtariCnnPolicy(object):
             ci = c if (self._u8 and not self._conv_geom) else (c + 3) // 4 * 4
             self._conv_geom.append((nf, ci, sz, st, tuple(pad), h, w))
             c = nf
+            h, w = self._next_conv_input_hw(len(self._conv_geom) - 1, h, w)
         self._conv_out = (c, h, w)
         fan = c * h * w
         hid_ref, hid_names, fan = self._hidden_reference_init(fan)
@@ -195,6 +196,11 @@ class AtariCnnPolicy(object):
             self._hid_geom.append((hs, fan))
             fan = hs
         return ref, names, fan
+
+    def _next_conv_input_hw(self, i, ho, wo):
+        """Height and width of what the conv layer after layer i reads, given layer i's output: the output itself, for
+        a plain stack (a policy with a pooling layer behind some of its conv layers says otherwise)."""
+        return ho, wo
 
     def _bucket_order(self, n):
         """The tensors' order in the flat bucket's memory: the order of `_shapes`, for every policy whose conv layers own
@@ -308,7 +314,7 @@ class AtariCnnPolicy(object):
             conv = []
             for nf, ci, sz, st, pad, ho, wo in self._conv_geom:
                 conv.append(_lib.conv_geom(b, h, w, ci, nf, sz, sz, st, pad[0], pad[1]))
-                h, w = ho, wo
+                h, w = self._next_conv_input_hw(len(conv) - 1, ho, wo)
             dense = [_lib.dense_geom(b, fan_in, hs) for hs, fan_in in self._hid_geom]
             gs = self._geoms[key] = (conv, dense)
         return gs
@@ -631,6 +637,21 @@ class AtariCnnPolicy(object):
 
     def _bias_grad_left(self, d, y, rows, channels, k):
         self._folds.relu_bwd_bias_grad(d, y, rows, channels, self.grads[k + 1], self._fold_ws(("db", k)))
+
+    def _ones_geom(self, b, width):
+        key = ("ones", b, width)
+        if key not in self._geoms:
+            self._geoms[key] = _lib.dense_geom(b, 4, width)
+        return self._geoms[key]
+
+    def _bias_grad_by_ones(self, dout, rows, k):
+        """grads[k + 1] = column sums of dout f32[rows][width], as the weight gradient of an all-ones input: the fallback
+        where the weight-gradient kernel did not carry the bias gradient along."""
+        ones = self._buffer(("ones4", rows), (rows, 4))
+        ones.fill_(1.)
+        db4 = self._buffer(("db4", rows, dout.shape[1]), (dout.shape[1], 4))
+        _lib.conv2d_bwd_weight(dout, ones, db4, self._ones_geom(rows, dout.shape[1]), self._conv_ws)
+        self.grads[k + 1].copy_(db4[:, 0])
 
     def _through_activation(self, layer, d, masked, y):
         """Backward through what stands between layer `layer`'s contraction (conv layers first, then the dense ones) and

@@ -185,12 +185,6 @@ class QPolicyBase(AtariCnnPolicy):
         out2, acts2, hids2 = self._logits(x2, tag="2")
         return x2[:b], out2[:b], [a[:b] for a in acts2], [hd[:b] for hd in hids2], tgt, out2[b:]
 
-    def _ones_geom(self, b, width):
-        key = ("ones", b, width)
-        if key not in self._geoms:
-            self._geoms[key] = _lib.dense_geom(b, 4, width)
-        return self._geoms[key]
-
     def _head_geom(self, b):
         key = ("head", b)
         if key not in self._geoms:
@@ -299,15 +293,6 @@ class QPolicyBase(AtariCnnPolicy):
         self.flat_target.copy_(self.flat_params)
 
     # ---- training: the output layer's backward, then the trunk's ---------------------
-    def _bias_grad_by_ones(self, dout, rows, k):
-        """grads[k + 1] = column sums of dout f32[rows][width], as the weight gradient of an all-ones input: the fallback
-        where the weight-gradient kernel did not carry the bias gradient along."""
-        ones = self._buffer(("ones4", rows), (rows, 4))
-        ones.fill_(1.)
-        db4 = self._buffer(("db4", rows, dout.shape[1]), (dout.shape[1], 4))
-        _lib.conv2d_bwd_weight(dout, ones, db4, self._ones_geom(rows, dout.shape[1]), self._conv_ws)
-        self.grads[k + 1].copy_(db4[:, 0])
-
     def _head_backward(self, dout, x, acts, hids):
         """dW = dout^T h, db = column sums of dout (riding along in the weight-gradient kernel),
         dh = (dout W) * (h > 0) -- one launch; the folds run at the end of the trunk's backward."""

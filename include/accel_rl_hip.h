@@ -1275,6 +1275,49 @@ int arl_ln_relu_bwd(const float* dy, const float* y, const float* z, const float
                     void* workspace, struct arl_fold_item* items2_or_null, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Max pooling and the residual sum between the contraction launches (the IMPALA residual network)
+ * ------------------------------------------------------------------------- */
+
+/* 3 x 3 window, stride 2, padding 1 on every side (the padding never wins: it counts as -inf), on an NHWC activation
+ * z f32[batch][in_h][in_w][channels]; out_h = (in_h - 1) / 2 + 1, out_w = (in_w - 1) / 2 + 1 (integer division).
+ * Forward, per output element (b, oy, ox, c): best = -inf, arg = 0; for ky = 0, 1, 2 and, inside, kx = 0, 1, 2 with
+ * iy = 2 oy - 1 + ky, ix = 2 ox - 1 + kx inside the image: v = z[b][iy][ix][c]; if (v > best) { best = v; arg = 3 ky + kx; }
+ * -- the FIRST maximum in row-major window order keeps its place (strict >), which is torch.nn.functional.max_pool2d's
+ * rule.  The window's centre always lies inside the image, so with finite inputs (they are taken as finite; nothing is
+ * checked on the device) best is an element of z.
+ *   y f32[batch][out_h][out_w][channels] = best
+ *   y_relu_or_null (same shape)          = best > 0 ? best : +0     (the next convolution's input and rectifier mask)
+ *   arg_or_null u8 (same shape)          = arg
+ * Backward, a gather with one thread per four input elements: dz[b][i][j][c] = the sum of dy[b][oy][ox][c] over the
+ * windows (oy, ox) with i / 2 <= oy <= min((i + 1) / 2, out_h - 1), j / 2 <= ox <= min((j + 1) / 2, out_w - 1) -- the at
+ * most four that contain (i, j) -- whose arg equals 3 (i - 2 oy + 1) + (j - 2 ox + 1), taken with oy ascending and, inside,
+ * ox ascending: the first such term as it is, every further one added to the sum so far; +0 where there is none.  Every
+ * element of dz is written.
+ * No atomics, no partial sums: two launches give the same bits.  Indexing is 64-bit.
+ * Refused before any HIP call, nothing written: a NULL pointer other than the two optional ones, y, y_relu or z the same
+ * buffer, dz == dy (ARL_E_ARG); batch outside 1 .. 2^20, in_h or in_w outside 1 .. 2^16, channels outside 4 .. 1024 or
+ * not a multiple of 4 (ARL_E_RANGE); a float pointer not 16-byte aligned, arg not 4-byte aligned (ARL_E_ALIGN).      */
+int arl_maxpool3s2_fwd(const float* z, int64_t batch, int32_t in_h, int32_t in_w, int32_t channels, float* y,
+                       float* y_relu_or_null, uint8_t* arg_or_null, void* stream);
+int arl_maxpool3s2_bwd(const float* dy, const uint8_t* arg, int64_t batch, int32_t in_h, int32_t in_w, int32_t channels,
+                       float* dz, void* stream);
+
+/* sum[i] = a[i] + b[i] (one fp32 addition) and, with relu_or_null, relu[i] = sum[i] > 0 ? sum[i] : +0, i < n.  sum may be
+ * a or b (a thread reads its own elements before it writes them); relu is a buffer of its own.
+ * Refused before any HIP call, nothing written: a, b or sum NULL, relu equal to a, b or sum (ARL_E_ARG); n outside
+ * 4 .. 2^40 or not a multiple of 4 (ARL_E_RANGE); a pointer not 16-byte aligned (ARL_E_ALIGN).                       */
+int arl_add_relu(const float* a, const float* b, int64_t n, float* sum, float* relu_or_null, void* stream);
+
+/* arl_gather_scale_obs_nhwc for the observations it refuses: out f32[batch][plane_bytes][cp], cp = channels rounded up
+ * to a multiple of 4, out[b][p][c] = (float) obs[r][c][p] * scale (one fp32 multiplication) with r = idx_or_null ?
+ * idx_or_null[b] : b, and +0 for c >= channels; obs u8[.][channels][plane_bytes], any plane size (a byte per load: the
+ * path of image sizes no Atari frame has).  Row numbers are taken as valid.
+ * Refused before any HIP call, nothing written: obs or out NULL (ARL_E_ARG); batch outside 1 .. 2^24, channels outside
+ * 1 .. 1024, plane_bytes outside 1 .. 2^24 (ARL_E_RANGE); idx not 4-byte or out not 16-byte aligned (ARL_E_ALIGN).    */
+int arl_gather_scale_obs_nhwc_any(const uint8_t* obs, const int32_t* idx_or_null, int64_t batch, int32_t channels,
+                                  int32_t plane_bytes, float scale, float* out, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * LSTM cell of the recurrent policies
  * ------------------------------------------------------------------------- */
 
