@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_PKG, "libaccel_rl_hip.so")
 ARL_ABI_VERSION = 4
 PROMO_NEP50, PROMO_LEGACY, PROMO_ASSOC = 0, 1, 2
 PPO_TIE_THEANO, PPO_TIE_MATH, PPO_TIE_BOTH = 0, 1, 2      # ARL_PPO_TIE_*: whose gradient min() / clip() hand on (accel_rl_hip.h)
+PPG_POLICY, PPG_AUX = 0, 1                                # ARL_PPG_*: arl_ppg_head_loss_parts' phase
 OPT_ADAM, OPT_RMSPROP = 0, 1
 MAX_ACTIONS = 18
 REPLAY_MAX_HORIZON = 16
@@ -229,6 +230,8 @@ _SIGNATURES = {
     "arl_drq_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "arl_q_regress_loss": (_i32, [_vp] * 4 + [_i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
     "arl_qlambda_scan": (_i32, [_vp] * 4 + [_f64, _f64, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "arl_ppg_head_loss_parts": (_i32, [_vp] * 10 + [_i64, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _i32] +
+                                [_vp] * 8),
     "arl_vtrace_scan": (_i32, [_vp] * 7 + [_f64] * 5 + [_i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "arl_ln_bwd_workspace_bytes": (_i64, []),
     "arl_ln_relu_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp]),
@@ -967,6 +970,23 @@ class FoldList(object):
             ptr(dh), dw_head.data_ptr(), db_head.data_ptr(), ptr(loss4), ptr(workspace), first,
             None if wt_items is None else C.cast(wt_items, _vp), n_wt, stream_ptr(stream)),
             "arl_pg_head_loss_parts")
+
+    def ppg_head_loss(self, h, w_head, b_head, actions, advantages, returns, old_prob, idx, lr_mult, inv_count,
+                      n_actions, phase, clip_param, v_loss_coeff, ent_loss_coeff, beta_clone,
+                      dout, dh, dw_head, db_head, loss4, workspace, stream=None, relu_mask_dh=False,
+                      tie_rule=PPO_TIE_THEANO):
+        """PPG's output stage (phase PPG_POLICY / PPG_AUX, csrc/ppg.hip) with its three small folds (dw_head, db_head,
+        loss4) left to run(), as pg_head_loss leaves them.  workspace: pg_head_workspace()."""
+        batch, hid = h.shape
+        assert self._n + 3 <= FOLD_MAX_ITEMS, "too many pending folds"
+        first = C.byref(self._items[self._n])
+        _check(load().arl_ppg_head_loss_parts(
+            ptr(h), ptr(w_head), ptr(b_head), ptr(actions), ptr(advantages), ptr(returns), ptr(old_prob), ptr(idx),
+            ptr(lr_mult), ptr(inv_count), batch, hid, n_actions, int(phase), int(tie_rule), float(clip_param),
+            float(v_loss_coeff), float(ent_loss_coeff), float(beta_clone), int(bool(relu_mask_dh)), ptr(dout), ptr(dh),
+            ptr(dw_head), ptr(db_head), ptr(loss4), ptr(workspace), first, stream_ptr(stream)),
+            "arl_ppg_head_loss_parts")
+        self._n += 3                # (a refused call leaves no items behind)
 
     def ln_relu_bwd(self, dy, y, z, stats, gamma, dy_masked, dz, dgamma, dbeta, workspace, stream=None):
         """ln_relu_bwd with its two column-sum folds (dgamma, dbeta) left to run()."""

@@ -1,1 +1,2 @@
 from accel_rl_amd.algos.pg.impala import IMPALA  # noqa: F401
+from accel_rl_amd.algos.pg.ppg import PPG  # noqa: F401

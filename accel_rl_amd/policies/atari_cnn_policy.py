@@ -454,21 +454,27 @@ class AtariCnnPolicy(object):
 
     # ------------------------------------------------------------- training
     def loss_and_grads(self, mb, kind, clip_param, v_loss_coeff, ent_loss_coeff, lr_mult,
-                       inv_count=None, tie_rule=_lib.PPO_TIE_THEANO):
+                       inv_count=None, tie_rule=_lib.PPO_TIE_THEANO, beta_clone=1.0):
         """One minibatch: forward, losses (a2c.py:43-46 / ppo.py:42-51 + aac_base.py:60-66)
         and the full backward pass into `flat_grads` (overwritten, not accumulated).
         mb: observations u8[n,...], idx i32[B] or None, actions, advantages, returns,
         old_prob, valids (full-batch arrays, rows selected by idx).  Returns loss4 =
         (pi_loss, v_loss, ent_loss, pi+v+ent) as a device tensor.  tie_rule (PPO): whose gradient the surrogate's
         min() / clip() hand on -- the reference's Theano graph (default) or the mathematical derivative
-        (ARL_PPO_TIE_*, accel_rl_hip.h)."""
+        (ARL_PPO_TIE_*, accel_rl_hip.h).
+        kind 2 / 3: PPG's policy / auxiliary phase (arl_ppg_head_loss_parts, csrc/ppg.hip; no valids).  2 is PPO's loss
+        with the value gradient stopped at the last hidden layer (it still trains the head's value row); 3 is
+        v_loss + beta_clone * KL(old_prob || pi) on observations, returns, old_prob alone, and returns loss4 =
+        (clone, v_loss, 0, their sum)."""
+        if kind in (2, 3) and mb.get("valids") is not None:
+            raise NotImplementedError("the PPG kinds take no valids (mid_batch_reset=False is not built for PPG)")
         with torch.no_grad():
             idx = mb.get("idx")
             rows = mb["observations"].shape[0] if idx is None else idx.shape[0]
             limit = self.rows_per_pass()
             if limit and rows >= 3 * limit:
                 return self._loss_and_grads_in_passes(mb, rows, limit, kind, clip_param, v_loss_coeff, ent_loss_coeff,
-                                                      lr_mult, inv_count, tie_rule)
+                                                      lr_mult, inv_count, tie_rule, beta_clone)
             x = self._scaled(mb["observations"], idx)
             b = x.shape[0]
             acts, hids = self._trunk(x)
@@ -477,6 +483,15 @@ class AtariCnnPolicy(object):
             dout = self._buffer(("dout", b), (b, self.n_act + 1))
             dh = self._buffer(("dh", b), (b, hid))
             loss4 = self._buffer(("loss", b), (4,))
+            if kind in (2, 3):  # (no weight copies in this launch: _backward_convs launches them, as under ARL_WT_IN_HEAD=0)
+                self._folds.ppg_head_loss(hids[-1], self.params[k_head], self.params[k_head + 1], mb.get("actions"),
+                                          mb.get("advantages"), mb["returns"], mb["old_prob"], idx, lr_mult, inv_count,
+                                          self.n_act, kind - 2, clip_param, v_loss_coeff, ent_loss_coeff, beta_clone,
+                                          dout, dh, g[k_head], g[k_head + 1], loss4, self._loss_ws,
+                                          relu_mask_dh=True, tie_rule=tie_rule)
+                self._backward_trunk(x, acts, hids, dh, masked=True, split_hook=mb.get("split_hook"),
+                                     dense_w_hook=mb.get("dense_w_hook"))
+                return loss4
             # (the head's launch also writes the data gradients' weight copies: _backward_convs then skips its own launch)
             wts = self._dgrad_weight_items(b) if os.environ.get("ARL_WT_IN_HEAD", "1") != "0" else []      # (A/B switch)
             self._folds.pg_head_loss(hids[-1], self.params[k_head], self.params[k_head + 1], mb["actions"],
@@ -512,7 +527,7 @@ class AtariCnnPolicy(object):
         return max(256, (self.CACHE_BYTES // per_row + 128) // 256 * 256)
 
     def _loss_and_grads_in_passes(self, mb, rows, limit, kind, clip_param, v_loss_coeff, ent_loss_coeff, lr_mult,
-                                  inv_count, tie_rule=_lib.PPO_TIE_THEANO):
+                                  inv_count, tie_rule=_lib.PPO_TIE_THEANO, beta_clone=1.0):
         """loss_and_grads of a minibatch larger than rows_per_pass(): passes over consecutive slices of its index list,
         every pass normalised by the WHOLE minibatch's count; gradients and the four loss sums accumulate in pass
         order (deterministic).  The co-run / split hooks of the one-pass learner do not apply (nothing is final before
@@ -537,7 +552,7 @@ class AtariCnnPolicy(object):
             for k, lo in enumerate(range(0, rows, limit)):
                 one["idx"] = idx[lo:min(lo + limit, rows)]
                 loss4 = self.loss_and_grads(one, kind, clip_param, v_loss_coeff, ent_loss_coeff, lr_mult, inv_count,
-                                            tie_rule)
+                                            tie_rule, beta_clone)
                 if k == 0:
                     acc.copy_(self.flat_grads)
                     loss_acc.copy_(loss4)

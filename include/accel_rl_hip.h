@@ -423,6 +423,52 @@ int arl_pg_head_loss_parts(const float* h, const float* w_head, const float* b_h
                            struct arl_fold_item* items3, const struct arl_dgrad_wt* wt_items_or_null, int32_t n_wt,
                            void* stream);
 
+/* Phasic policy gradient (PPG, single-network variant): arl_pg_head_loss_parts' sibling for PPG's two phases
+ * (csrc/ppg.hip).  The forward is the sibling's: o_k = sum_j h[b][j] W[k][j] + b_head[k] (lanes split j, lane l sums
+ * j = l, l + 64, ... ascending, butterfly sum over the wave), p = softmax(o[0..A)) (max over k ascending, z = sum_k
+ * exp(o_k - max) k ascending, p_k = exp(o_k - max) / z), V = o[A], TINY = 1e-8.  Rows of actions / advantages /
+ * returns / old_prob are selected by idx_or_null (NULL = identity); inv_n = inv_count_or_null ? inv_count[0] :
+ * 1 / (float) batch.  There are no valids.
+ *
+ * phase ARL_PPG_POLICY (0): pi_loss, v_loss, ent_loss, dout, dw_head, db_head are those of arl_pg_head_loss_parts
+ *   kind 1 (PPO) with the same three tie_rules and clip = clip_param * lr_mult[0], expression for expression.  The
+ *   value gradient is stopped at the last shared layer:
+ *       dh[b][c] = sum_{k < A} dout[b][k] W[k][c]                     (k ascending; the value row k = A is left out)
+ *   while dw_head = sum_b dout[b] x h[b] and db_head = sum_b dout[b] keep all A + 1 rows: the value loss trains W[A]
+ *   and b_head[A] and nothing else.  loss4 = (pi, v, ent, (pi + v) + ent).  beta_clone is ignored.
+ * phase ARL_PPG_AUX (1): actions, advantages, lr_mult may be NULL; clip_param, ent_loss_coeff, tie_rule are ignored;
+ *   old_prob f32[n_rows][A] is read whole.  With w = inv_n, c = beta_clone * w, old = old_prob[row]:
+ *       kl_b   = sum_k old_k * (log(old_k + TINY) - log(p_k + TINY))               (Categorical.kl_sym; k ascending)
+ *       clone  = sum_b c * kl_b            v_loss = sum_b (v_loss_coeff * w * (V_b - R_b)) * (V_b - R_b)
+ *       q_k    = old_k * p_k / (p_k + TINY),  S = sum_k q_k                        (k ascending)
+ *       dout[b][j] = c * (p_j * S - q_j), j < A          dout[b][A] = 2 * v_loss_coeff * w * (V_b - R_b)
+ *       dh[b][c] = sum_{k <= A} dout[b][k] W[k][c]                                 (k ascending)
+ *   loss4 = (clone, v_loss, 0, (clone + v_loss) + 0).
+ * Sums over b: wave w of workgroup g takes rows 4 g + w, + 4 * grid, ... in ascending order (grid = min(ceil(batch /
+ * 4), 256)); a workgroup adds its four waves' sums in wave order; arl_fold_many adds the workgroups' partials in its
+ * own fixed order.  The head weight gradient is summed in the launch itself while (A + 1) hid <= 3 072, else by the
+ * separate row-split kernel, exactly as for the sibling.  No atomics anywhere: two launches on the same inputs give
+ * the same bits.
+ * relu_mask_dh != 0: dh[b][c] = 0 where !(h[b][c] > 0).
+ *   out: dout f32[batch][A+1], dh f32[batch][hid]; dw_head f32[A+1][hid], db_head f32[A+1], loss4 f32[4] are described
+ *        in items3[0..2] for arl_fold_many as arl_pg_head_loss_parts describes them (16-byte aligned)
+ *   workspace >= arl_pg_head_workspace_bytes(), live until the fold has run
+ * This entry does not write the arl_dgrad_wt weight copies: the backward pass launches arl_conv2d_dgrad_weights itself.
+ * Limits (else ARL_E_RANGE): 1 <= n_actions <= 18, 1 <= hid <= 1024, 1 <= batch <= 2^31 - 1.  ARL_E_ARG: a NULL
+ * mandatory pointer, a phase outside {0, 1}, in the policy phase a tie_rule outside its three values, or a coefficient
+ * the phase reads that is not finite (policy: clip_param, v_loss_coeff, ent_loss_coeff; auxiliary: v_loss_coeff,
+ * beta_clone).  A refused call launches nothing and writes nothing.                                               */
+#define ARL_PPG_POLICY 0
+#define ARL_PPG_AUX    1
+int arl_ppg_head_loss_parts(const float* h, const float* w_head, const float* b_head,
+                            const uint8_t* actions, const float* advantages, const float* returns,
+                            const float* old_prob, const int32_t* idx_or_null, const float* lr_mult,
+                            const float* inv_count_or_null, int64_t batch, int32_t hid, int32_t n_actions,
+                            int32_t phase, int32_t tie_rule, float clip_param, float v_loss_coeff,
+                            float ent_loss_coeff, float beta_clone, int32_t relu_mask_dh, float* dout, float* dh,
+                            float* dw_head, float* db_head, float* loss4, void* workspace,
+                            struct arl_fold_item* items3, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * The policy network's dense contractions on the matrix cores (fp32 MFMA)
  * ------------------------------------------------------------------------- */
