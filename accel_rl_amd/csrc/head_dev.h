@@ -1,5 +1,5 @@
-// Wave-level helpers of the output-layer kernels (learner.hip: head_kernel; serve_step.hip evaluates the same heads inside
-// the env step's launch with the same operations in the same order).
+// Wave-level helpers of the output-layer kernels (head_kernel_dev.h: head_kernel; serve_step.hip evaluates the same heads
+// inside the env step's launch with the same operations in the same order).
 #pragma once
 #include "arl_common.h"
 

@@ -1,7 +1,5 @@
-// What the training-time output-layer launches share besides head_dev.h's wave helpers (learner.hip: head_kernel;
-// ppg.hip: ppg_head_kernel): the limits, the separate head weight-gradient kernel with its row splits, and the two
-// host-side checks in front of a launch.  Both files lay their workspace out the same way
-// (arl_pg_head_workspace_bytes).
+// What head_kernel_dev.h's output-layer kernel and launcher stand on besides head_dev.h's wave helpers: the limits, the
+// separate head weight-gradient kernel with its row splits, and the two host-side checks in front of a launch.
 #pragma once
 #include "arl_common.h"
 

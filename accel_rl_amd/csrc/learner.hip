@@ -13,13 +13,12 @@
 //                               a2c.py:43-46; ppo.py:42-51; distributions/categorical.py:35-88)
 //   arl_pg_head_wgrad          dW_head = dout^T h, db_head = colsum(dout)
 //   arl_pg_head_infer          heads + softmax for action serving (atari_cnn_policy.py:67,109)
+// (the heads' kernel and launcher are head_kernel_dev.h's, shared with ppg.hip: this file holds their two losses)
 //
 // All fp32 (the reference's floatX); compiled with -ffp-contract=off.
 
 #include "arl_common.h"
-#include "head_dev.h"
-#include "head_wgrad_dev.h"
-#include "dgrad_wt_dev.h"
+#include "head_kernel_dev.h"
 
 namespace {
 
@@ -133,227 +132,30 @@ __global__ __launch_bounds__(1024) void fold_partials_kernel(const float* __rest
     }
 }
 
-// ---------------------------------------------------------------- heads
+// ---------------------------------------------------------------- heads (head_kernel_dev.h: head_kernel<Loss, HVT>)
 
-struct HeadLossArgs {
-    const float* h;          // [B][hid] post-relu hidden activations
-    const float* w_head;     // [K][hid], rows 0..A-1 = pi, row A = value
-    const float* b_head;     // [K]
-    const uint8_t* actions;  // [n_rows]
-    const float* adv;        // [n_rows]
-    const float* ret;        // [n_rows]
-    const float* old_prob;   // [n_rows][A]
-    const int8_t* valids;    // [n_rows] or null
-    const int32_t* idx;      // [B] rows of this minibatch, or null (identity)
-    const float* lr_mult;    // device scalar (PPO clip anneals with it, ppo.py:46)
-    const float* inv_count;  // device scalar 1/sum(valids) or null -> 1/B
-    float* dout;             // [B][K] gradient wrt (logits, value)
-    float* dh;               // [B][hid] gradient wrt h (before the relu mask)
-    float* loss_partials;    // [gridDim][4] = pi, v, ent, their sum
-    float* wpart;            // [gridDim][wstride] this workgroup's share of dW_head[K][hid] = sum_b dout[b] x h[b], or null
-    float* bpart;            // [gridDim][Kp]     ... of db_head = sum_b dout[b]                (with wpart)
-    int batch, hid, n_act, kind, tie_rule;
-    float clip_param, v_coeff, ent_coeff;
-    int mask_dh;             // dh *= (h > 0): h is a rectifier's output and the caller wants the gradient before it
-    int head_blocks;         // workgroups of the head itself (the launch may carry more: see head_kernel)
-    int64_t wstride;         // floats between workgroups' wpart: K * hid rounded up to 4 (arl_fold_many folds float4s)
+struct InferLoss {           // action serving: probabilities and values are the output
+    static constexpr bool TRAIN = false, WT = false;
+    static constexpr const char* NAME = "head_kernel<infer>";
+    __device__ explicit InferLoss(const HeadArgs&) {}
 };
 
-// one wave per row (looping); lanes split the hidden dimension.  Every per-action
-// array is indexed with compile-time indices only (fully unrolled loops with
-// `k < n_act` guards) so that it lives in VGPRs, not scratch.
-// HVT = hid / 64 when the hidden width is a multiple of 64 (no per-lane guards: a guarded element costs an
-// exec-mask save / branch / restore, and the generic kernel is mostly those), 0 = any width.
-// wt (TRAIN): the workgroups behind the head's own grid (blockIdx.x >= a.head_blocks) write the data gradients' k-contiguous
-// weight copies (dgrad_wt_dev.h) -- the backward pass that follows reads them, and this launch is where a minibatch's
-// parameters are final and nothing else needs the CUs (one launch less per minibatch).
-template <bool TRAIN, int HVT = 0>
-__global__ __launch_bounds__(256) void head_kernel(HeadLossArgs a, float* __restrict__ prob_out,
-                                                   float* __restrict__ value_out, const arlw::DgradWtArgs wt) {
-    if (TRAIN && (int)blockIdx.x >= a.head_blocks) {
-        arlw::dgrad_wt_block(wt, (int)blockIdx.x - a.head_blocks, (int)threadIdx.x);
-        return;
+struct PgLoss {              // A2C (kind 0) / PPO (kind 1): a runtime branch, one set of instantiations for both
+    static constexpr bool TRAIN = true, WT = true;
+    static constexpr const char* NAME = "head_kernel<train>";
+    float clip;
+    __device__ explicit PgLoss(const HeadArgs& a) : clip(a.clip_param * a.lr_mult[0]) {}
+    __device__ void load(const HeadArgs& a, int64_t row, int A, int, HeadRow& m) const {
+        m.act = a.actions[row];
+        m.adv = a.adv[row]; m.ret = a.ret[row];
+        m.valid = a.valids ? (a.valids[row] != 0 ? 1.f : 0.f) : 1.f;
+        if (a.kind == 1) m.old = a.old_prob[row * A + m.act];
     }
-    constexpr int HV = HVT ? HVT : HID_MAX / 64;
-    extern __shared__ __attribute__((aligned(16))) float s_w[];     // [K][hid] (+ [4][K][hid] head-gradient slices)
-    __shared__ float s_loss[4][4];
-    __shared__ float s_db[4][64];
-    const int A = a.n_act, K = A + 1, hid = a.hid, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // A row's scalars hang off a three-deep chain of dependent loads (idx -> action -> old probability): they
-    // are fetched one row ahead -- the first row's before the weights are even staged -- so the chain's
-    // latency runs under the dot products instead of after them.
-    struct RowMeta { int64_t row; int act; float adv, ret, valid, old_pa; };
-    auto load_meta = [&](int b) {
-        RowMeta m = {b, 0, 0.f, 0.f, 1.f, 0.f};
-        if (TRAIN && b < a.batch) {
-            m.row = a.idx ? (int64_t)a.idx[b] : b;
-            m.act = a.actions[m.row];
-            m.adv = a.adv[m.row]; m.ret = a.ret[m.row];
-            m.valid = a.valids ? (a.valids[m.row] != 0 ? 1.f : 0.f) : 1.f;
-            if (a.kind == 1) m.old_pa = a.old_prob[m.row * A + m.act];
-        }
-        return m;
-    };
-    const int waves_total = ((TRAIN ? a.head_blocks : (int)gridDim.x) * blockDim.x) >> 6;
-    RowMeta meta = load_meta(blockIdx.x * (blockDim.x >> 6) + wave);
-    if (((K * hid) & 3) || (reinterpret_cast<uintptr_t>(a.w_head) & 15)) {
-        for (int i = threadIdx.x; i < K * hid; i += blockDim.x) s_w[i] = a.w_head[i];
-    } else {    // stage W: independent b128 loads, four in flight per thread
-        const int n4 = (K * hid) >> 2;
-        const float4* src = reinterpret_cast<const float4*>(a.w_head);
-        float4* dst = reinterpret_cast<float4*>(s_w);
-        for (int i0 = threadIdx.x; i0 < n4; i0 += 4 * 256) {
-            float4 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (i0 + u * 256 < n4) v[u] = src[i0 + u * 256];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (i0 + u * 256 < n4) dst[i0 + u * 256] = v[u];
-        }
+    __device__ HeadTerms row(const HeadArgs& a, const HeadRow& r, int A, int lane, float pk, float w) const {
+        return pg_row(a, r, a.kind == 1, clip, A, lane, pk, w);
     }
-    __syncthreads();
-    const float TINY = 1e-8f;                                        // categorical.py:6
-    const float inv_n = TRAIN ? (a.inv_count ? a.inv_count[0] : 1.f / (float)a.batch) : 0.f;
-    const float clip = TRAIN ? a.clip_param * a.lr_mult[0] : 0.f;
-    float l_pi = 0.f, l_v = 0.f, l_ent = 0.f;
-    // The head's own weight / bias gradient rides along (no second pass over dout and h): every wave adds its rows'
-    // outer products dout[b] x h[b] into its LDS slice, the workgroup sums the four slices in wave order and leaves
-    // ONE partial per workgroup for arl_fold_many (fixed order => deterministic).
-    const bool fused_wgrad = TRAIN && a.wpart != nullptr;            // uniform
-    float* s_dw = s_w + K * hid + wave * K * hid;
-    float db_lane = 0.f;
-    if (fused_wgrad) {
-        for (int k = 0; k < K; ++k)
-#pragma unroll
-            for (int j = 0; j < HV; ++j)
-                if (HVT || lane + 64 * j < hid) s_dw[k * hid + lane + 64 * j] = 0.f;
-    }
-    const int waves = waves_total;
-    for (int b = blockIdx.x * (blockDim.x >> 6) + wave; b < a.batch; b += waves) {
-        const RowMeta cur = meta;
-        meta = load_meta(b + waves);                                    // next row's chain starts now
-        const float* hrow = a.h + (int64_t)b * hid;
-        float hv[HV];
-#pragma unroll
-        for (int j = 0; j < HV; ++j) hv[j] = (HVT || lane + 64 * j < hid) ? hrow[lane + 64 * j] : 0.f;
-        // Lane k owns action k (lane A the value): the transcendental work is done once per action, not
-        // once per lane; sums over actions stay sequential in k (readlane), i.e. in a fixed order.  The loops
-        // over k are real loops (K is uniform): unrolled to the 19-action maximum they were mostly branches.
-        float v = 0.f, mx = -3.0e38f, mine = 0.f;
-        for (int k = 0; k < K; ++k) {
-            float sdot = 0.f;
-#pragma unroll
-            for (int j = 0; j < HV; ++j)
-                if (HVT || lane + 64 * j < hid) sdot += hv[j] * s_w[k * hid + lane + 64 * j];
-            const float o = wave_sum_f(sdot) + a.b_head[k];
-            if (k < A) mx = fmaxf(mx, o); else v = o;
-            mine = (lane == k) ? o : mine;
-        }
-        const bool is_act = lane < A;
-        const float ex = is_act ? expf(mine - mx) : 0.f;
-        float z = 0.f;
-        for (int k = 0; k < A; ++k) z += readlane_f(ex, k);
-        const float pk = ex / z;
-        if (!TRAIN) {
-            if (is_act) prob_out[(int64_t)b * A + lane] = pk;
-            if (lane == 0) value_out[b] = v;
-            continue;
-        }
-        const float w = cur.valid * inv_n;                              // valids_mean
-        const int act = cur.act;
-        const float adv = cur.adv, ret = cur.ret;
-        const float pa = __shfl(pk, act, 64);
-        // ---- d loss / d p_k : entropy term for every action (categorical.py:76-78)
-        const float lg = is_act ? logf(pk + TINY) : 0.f;
-        const float ent_k = pk * lg;
-        float gk = is_act ? a.ent_coeff * w * (lg + pk / (pk + TINY)) : 0.f;     // d(-c_e * ent)/dp_k
-        float ent = 0.f;
-        for (int k = 0; k < A; ++k) ent -= readlane_f(ent_k, k);
-        float pi_term, g_act;
-        if (a.kind == 1) {                                               // PPO, ppo.py:42-51
-            const float old_pa = cur.old_pa;
-            const float ratio = (pa + TINY) / (old_pa + TINY);           // categorical.py:66-70
-            const float lo = 1.f - clip, hi = 1.f + clip;
-            const float rc = fminf(fmaxf(ratio, lo), hi);
-            const float s1 = ratio * adv, s2 = rc * adv;
-            pi_term = fminf(s1, s2);
-            const bool in_range = (ratio >= lo) && (ratio <= hi);
-            float g_ratio;
-            if (a.tie_rule == ARL_PPO_TIE_THEANO) {
-                // the reference's graph as Theano >= 0.8 differentiates it: Minimum.L_op, e = eq(min, x), gives e g to
-                // its FIRST argument (s1 here: T.minimum(surr_1, surr_2)) and (1 - e) g to the second -- a tie goes to
-                // the first alone --, Clip.L_op passes g for lo <= r <= hi
-                g_ratio = (pi_term == s1) ? adv : (in_range ? adv : 0.f);
-            } else if (a.tie_rule == ARL_PPO_TIE_BOTH) {
-                // Theano <= 0.7: eq(min, x) g to EVERY argument equal to the minimum -- inside the range s1 and s2 are the
-                // same number and the sample counts twice
-                g_ratio = ((pi_term == s1) ? adv : 0.f) + ((pi_term == s2 && in_range) ? adv : 0.f);
-            } else {
-                g_ratio = in_range ? adv : (s1 < s2 ? adv : 0.f);
-            }
-            g_act = -w * g_ratio / (old_pa + TINY);
-        } else {                                                         // A2C, a2c.py:43-46
-            pi_term = logf(pa + TINY) * adv;
-            g_act = -w * adv / (pa + TINY);
-        }
-        const float dv = 2.f * a.v_coeff * w * (v - ret);                // aac_base.py:60-61
-        gk += (lane == act) ? g_act : 0.f;
-        const float gp = gk * pk;
-        float dot = 0.f;
-        for (int k = 0; k < A; ++k) dot += readlane_f(gp, k);
-        const float dlk = is_act ? pk * (gk - dot) : (lane == A ? dv : 0.f);      // softmax backward | value
-        if (lane < K) a.dout[(int64_t)b * K + lane] = dlk;
-        if (lane == 0) {
-            l_pi += -w * pi_term;
-            l_v += a.v_coeff * w * (v - ret) * (v - ret);
-            l_ent += -a.ent_coeff * w * ent;
-        }
-        // dh[b][c] = sum_k dl_k W[k][c], k in order
-        float sdh[HV];
-#pragma unroll
-        for (int j = 0; j < HV; ++j) sdh[j] = 0.f;
-        for (int k = 0; k < K; ++k) {
-            const float dl_k = readlane_f(dlk, k);
-#pragma unroll
-            for (int j = 0; j < HV; ++j)
-                if (HVT || lane + 64 * j < hid) sdh[j] += dl_k * s_w[k * hid + lane + 64 * j];
-            if (fused_wgrad) {
-#pragma unroll
-                for (int j = 0; j < HV; ++j)
-                    if (HVT || lane + 64 * j < hid) s_dw[k * hid + lane + 64 * j] += dl_k * hv[j];
-            }
-        }
-        if (lane < K) db_lane += dlk;
-        float* dhrow = a.dh + (int64_t)b * hid;
-#pragma unroll
-        for (int j = 0; j < HV; ++j) {
-            const int c = lane + 64 * j;
-            if (HVT || c < hid) dhrow[c] = (a.mask_dh && !(hv[j] > 0.f)) ? 0.f : sdh[j];
-        }
-    }
-    if (TRAIN) {
-        if (lane == 0) { s_loss[wave][0] = l_pi; s_loss[wave][1] = l_v; s_loss[wave][2] = l_ent; s_loss[wave][3] = (l_pi + l_v) + l_ent; }
-        __syncthreads();
-        if (threadIdx.x < 4) {
-            float sl = 0.f;
-            for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) sl += s_loss[wv][threadIdx.x];
-            a.loss_partials[blockIdx.x * 4 + threadIdx.x] = sl;
-        }
-        if (fused_wgrad) {                                               // (the barrier above covers the slices too)
-            s_db[wave][lane] = db_lane;
-            const float* s0 = s_w + K * hid;
-            float* out = a.wpart + (int64_t)blockIdx.x * a.wstride;
-            for (int i = threadIdx.x; i < K * hid; i += blockDim.x)
-                out[i] = ((s0[i] + s0[K * hid + i]) + s0[2 * K * hid + i]) + s0[3 * K * hid + i];
-            __syncthreads();
-            const int Kp = (K + 3) & ~3;
-            if (threadIdx.x < Kp)
-                a.bpart[(int64_t)blockIdx.x * Kp + threadIdx.x] =
-                    threadIdx.x < K ? ((s_db[0][threadIdx.x] + s_db[1][threadIdx.x]) + s_db[2][threadIdx.x]) + s_db[3][threadIdx.x] : 0.f;
-        }
-    }
-}
+    static __device__ int dh_rows(int A) { return A + 1; }
+};
 
 }  // namespace
 
@@ -431,24 +233,12 @@ extern "C" int arl_pg_head_infer(const float* h, const float* w_head, const floa
     ARL_REQUIRE(h && w_head && b_head && prob && value, ARL_E_ARG, "null pointer");
     int rc = check_head(batch, hid, n_actions);
     if (rc) return rc;
-    HeadLossArgs a = {};
+    HeadArgs a = {};
     a.h = h; a.w_head = w_head; a.b_head = b_head; a.batch = (int)batch; a.hid = hid; a.n_act = n_actions;
-    const int grid = (int)((batch + 3) / 4 < 1024 ? (batch + 3) / 4 : 1024);
-    const size_t lds = (size_t)(n_actions + 1) * hid * 4;
-#define ARL_HEAD_INFER(HVT_)                                                                                         \
-    do {                                                                                                             \
-        rc = head_allow_lds(head_kernel<false, HVT_>, lds);                                                          \
-        if (rc) return rc;                                                                                           \
-        hipLaunchKernelGGL((head_kernel<false, HVT_>), dim3(grid), dim3(256), lds, (hipStream_t)stream, a, prob,    \
-                           value, arlw::DgradWtArgs{});                                                              \
-    } while (0)
-    if (hid == 512) ARL_HEAD_INFER(8);
-    else if (hid == 256) ARL_HEAD_INFER(4);
-    else if (hid == 1024) ARL_HEAD_INFER(16);
-    else if (hid == 64) ARL_HEAD_INFER(1);
-    else ARL_HEAD_INFER(0);
-#undef ARL_HEAD_INFER
-    return arl::check_launch("head_kernel<infer>");
+    a.prob = prob; a.value = value;
+    a.head_blocks = (int)((batch + 3) / 4 < 1024 ? (batch + 3) / 4 : 1024);
+    return head_launch<InferLoss>(a, a.head_blocks, (size_t)(n_actions + 1) * hid * 4, arlw::DgradWtArgs{},
+                                  (hipStream_t)stream);
 }
 
 extern "C" int arl_pg_head_loss_parts(const float* h, const float* w_head, const float* b_head,
@@ -467,65 +257,14 @@ extern "C" int arl_pg_head_loss_parts(const float* h, const float* w_head, const
                 "tie_rule must be ARL_PPO_TIE_THEANO, ARL_PPO_TIE_MATH or ARL_PPO_TIE_BOTH");
     int rc = check_head(batch, hid, n_actions);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    HeadLossArgs a = {};
+    HeadArgs a = {};
     a.h = h; a.w_head = w_head; a.b_head = b_head; a.actions = actions; a.adv = advantages;
     a.ret = returns; a.old_prob = old_prob; a.valids = valids_or_null; a.idx = idx_or_null;
     a.lr_mult = lr_mult; a.inv_count = inv_count_or_null; a.dout = dout; a.dh = dh;
-    a.loss_partials = (float*)workspace;
     a.batch = (int)batch; a.hid = hid; a.n_act = n_actions; a.kind = kind; a.tie_rule = tie_rule;
     a.clip_param = clip_param; a.v_coeff = v_loss_coeff; a.ent_coeff = ent_loss_coeff; a.mask_dh = relu_mask_dh;
-    const int grid = (int)((batch + 3) / 4 < 256 ? (batch + 3) / 4 : 256);
-    const int K = n_actions + 1;
-    const int Kp = (K + 3) & ~3;
-    float* ws = (float*)workspace;
-    float* part = ws + 256 * 4;
-    const bool fused = K * hid <= FUSED_WGRAD_MAX;
-    // one split's weight partials [K][hid], padded to a multiple of 4 floats (the fold reads float4s; the padding is
-    // folded but not stored: items3[0].valid)
-    const int64_t kh = (int64_t)K * hid, kh4 = (kh + 3) & ~(int64_t)3;
-    float* part_b = part + (fused ? (int64_t)grid : (int64_t)WG_SPLITS) * kh4;
-    if (fused) { a.wpart = part; a.bpart = part_b; }
-    a.wstride = kh4;
-    const size_t head_lds = (size_t)(fused ? 5 : 1) * K * hid * 4;
-    arlw::DgradWtArgs wt = {};
-    int wt_blocks = 0;
-    if (wt_items_or_null && n_wt > 0) {
-        rc = arlw::dgrad_wt_plan(wt_items_or_null, n_wt, &wt, &wt_blocks);
-        if (rc) return rc;
-    }
-    a.head_blocks = grid;
-#define ARL_HEAD_TRAIN(HVT_)                                                                                         \
-    do {                                                                                                             \
-        rc = head_allow_lds(head_kernel<true, HVT_>, head_lds);                                                      \
-        if (rc) return rc;                                                                                           \
-        hipLaunchKernelGGL((head_kernel<true, HVT_>), dim3(grid + wt_blocks), dim3(256), head_lds, s, a,             \
-                           (float*)nullptr, (float*)nullptr, wt);                                                    \
-    } while (0)
-    if (hid == 512) ARL_HEAD_TRAIN(8);
-    else if (hid == 256) ARL_HEAD_TRAIN(4);
-    else if (hid == 1024) ARL_HEAD_TRAIN(16);
-    else if (hid == 64) ARL_HEAD_TRAIN(1);
-    else ARL_HEAD_TRAIN(0);
-#undef ARL_HEAD_TRAIN
-    rc = arl::check_launch("head_kernel<train>");
-    if (rc) return rc;
-    // head weight / bias gradient: row-split partials [WG_SPLITS][K][hid] and [WG_SPLITS][Kp]; their folds and the
-    // fold of the per-workgroup loss partials [grid][4] are left to arl_fold_many (one launch per backward pass)
-    if (!fused) {
-        hipLaunchKernelGGL(head_wgrad_kernel, dim3((hid + 63) / 64, WG_SPLITS), dim3(256), 0, s, dout, h,
-                           (int)batch, (int)hid, K, Kp, kh4, part, part_b);
-        rc = arl::check_launch("head_wgrad_kernel");
-        if (rc) return rc;
-    }
-    const int n_parts = fused ? grid : WG_SPLITS;
-    items3[0].part = part; items3[0].out = dw_head; items3[0].total = kh4; items3[0].splits = n_parts;
-    items3[1].part = part_b; items3[1].out = db_head; items3[1].total = Kp; items3[1].splits = n_parts;
-    items3[2].part = ws; items3[2].out = loss4; items3[2].total = 4; items3[2].splits = grid;
-    items3[0].valid = kh4 != kh ? kh : 0;              // dw_head holds K * hid floats
-    items3[2].valid = 0;
-    items3[1].valid = K;                                // db_head holds K floats, the partials are padded to Kp
-    return 0;
+    return head_loss_launch<PgLoss>(a, dw_head, db_head, loss4, workspace, items3, wt_items_or_null, n_wt,
+                                    (hipStream_t)stream);
 }
 
 extern "C" int arl_pg_head_loss(const float* h, const float* w_head, const float* b_head,

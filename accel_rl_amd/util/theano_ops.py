@@ -10,7 +10,7 @@ imports theano.gpuarray, i.e. runs on Theano >= 0.9, and since 0.8 the rules are
 
 (`both=True` is Theano <= 0.7's minimum: gx = eq(out, x) g, gy = eq(out, y) g -- a tie feeds both arguments.)
 
-The learner never calls these (the same rules live inside `head_kernel`, csrc/learner.hip, selected by
+The learner never calls these (the same rules live inside `pg_row`, csrc/head_kernel_dev.h, selected by
 ARL_PPO_TIE_*); `BasePPO.pi_loss` is written with them so that the formula the numerics tests differentiate is the
 reference's graph and not torch.minimum's (which splits a tie's gradient evenly)."""
 import torch

@@ -424,7 +424,8 @@ int arl_pg_head_loss_parts(const float* h, const float* w_head, const float* b_h
                            void* stream);
 
 /* Phasic policy gradient (PPG, single-network variant): arl_pg_head_loss_parts' sibling for PPG's two phases
- * (csrc/ppg.hip).  The forward is the sibling's: o_k = sum_j h[b][j] W[k][j] + b_head[k] (lanes split j, lane l sums
+ * (csrc/ppg.hip; both entries run ONE kernel source and launcher, csrc/head_kernel_dev.h, and differ in the loss they
+ * hand it).  The forward is the sibling's: o_k = sum_j h[b][j] W[k][j] + b_head[k] (lanes split j, lane l sums
  * j = l, l + 64, ... ascending, butterfly sum over the wave), p = softmax(o[0..A)) (max over k ascending, z = sum_k
  * exp(o_k - max) k ascending, p_k = exp(o_k - max) / z), V = o[A], TINY = 1e-8.  Rows of actions / advantages /
  * returns / old_prob are selected by idx_or_null (NULL = identity); inv_n = inv_count_or_null ? inv_count[0] :

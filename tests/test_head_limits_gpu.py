@@ -75,6 +75,7 @@ HEAD_CASES = [
     (1, 1024, 12288), (2, 60, 4097), (18, 1, 17), (17, 4, 16),
     (18, 1024, 1),                       # split kernel on one row, 77 824 B of head-kernel LDS
     (18, 1024, 12288),                   # both kernels' LDS past 64 KiB before the row chunking
+    (6, 64, 5), (6, 256, 5),             # the two specialised widths (hid / 64 = 1, 4) no case above reaches
 ]
 
 

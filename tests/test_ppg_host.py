@@ -1,6 +1,6 @@
 """PPG without a GPU: the float64 restatement of its two output stages (tests/ppg_ref.py) against autograd, the
-algorithm's refusals, the new entry point's declaration and binding, and ppg.hip's compile for gfx950 with the compiler's
-resource report."""
+algorithm's refusals, the new entry point's declaration and binding, and the compile for gfx950 of the two files that instantiate
+the head kernel (learner.hip, ppg.hip) with the compiler's resource report."""
 import os
 import re
 import shutil
@@ -177,21 +177,27 @@ def test_entry_is_declared_and_bound_with_matching_arguments():
     assert lib.arl_ppg_head_loss_parts(*null) == -1 and b"phase" in lib.arl_last_error()
 
 
-def test_ppg_hip_compiles_for_gfx950_without_scratch():
-    """The compiler's own report (-Rpass-analysis=kernel-resource-usage), printed; every ppg_head_kernel variant keeps its
-    per-action values in registers (scratch 0) and within the 128 VGPRs that leave four waves per SIMD."""
+def test_head_kernels_compile_for_gfx950_without_scratch():
+    """The compiler's own report (-Rpass-analysis=kernel-resource-usage), printed, for both files that instantiate
+    head_kernel_dev.h's kernel: every head_kernel variant keeps its per-action values in registers (scratch 0) and within
+    the 128 VGPRs that leave four waves per SIMD, and so does each file's head_wgrad_kernel."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                          "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "accel_rl_amd", "csrc"),
-                          "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
-                          os.path.join(ROOT, "accel_rl_amd", "csrc", "ppg.hip"), "-o", os.devnull],
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, check=True).stdout.decode()
     field = lambda name, block: int(re.search(name + r": (\d+)", block).group(1))             # noqa: E731
-    blocks = [b for b in out.split("Function Name: ")[1:] if "ppg_head_kernel" in b.split()[0]]
-    assert len(blocks) == 10                                 # 2 phases x (4 specialised widths + the generic one)
-    for b in blocks:
-        vgprs, scratch = field("VGPRs", b), field(r"ScratchSize \[bytes/lane\]", b)
-        print("%-60s VGPRs %3d SGPRs %3d scratch %d LDS %d occupancy %d" % (
-            b.split()[0], vgprs, field("TotalSGPRs", b), scratch, field(r"LDS Size \[bytes/block\]", b),
-            field(r"Occupancy \[waves/SIMD\]", b)))
-        assert scratch == 0 and vgprs <= 128
+    for source, losses in (("learner.hip", ["InferLoss", "PgLoss"]), ("ppg.hip", ["PpgPolicyLoss", "PpgAuxLoss"])):
+        out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
+                              "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "accel_rl_amd", "csrc"),
+                              "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
+                              os.path.join(ROOT, "accel_rl_amd", "csrc", source), "-o", os.devnull],
+                             stdout=subprocess.PIPE, stderr=subprocess.STDOUT, check=True).stdout.decode()
+        blocks = [b for b in out.split("Function Name: ")[1:] if "head_" in b.split()[0]]
+        # mangled names: head_kernel<Loss, HVT> carries "11head_kernelI" and the loss's name; one variant per width
+        count = lambda piece: sum(piece in b.split()[0] for b in blocks)                        # noqa: E731
+        assert count("head_wgrad_kernel") == 1 and count("11head_kernelI") == 10 and len(blocks) == 11, source
+        for loss in losses:
+            assert count("%d%sE" % (len(loss), loss)) == 5, loss   # 4 specialised widths + the generic one
+        for b in blocks:
+            vgprs, scratch = field("VGPRs", b), field(r"ScratchSize \[bytes/lane\]", b)
+            print("%-80s VGPRs %3d SGPRs %3d scratch %d LDS %d occupancy %d" % (
+                b.split()[0], vgprs, field("TotalSGPRs", b), scratch, field(r"LDS Size \[bytes/block\]", b),
+                field(r"Occupancy \[waves/SIMD\]", b)))
+            assert scratch == 0 and vgprs <= 128
