@@ -233,6 +233,10 @@ _SIGNATURES = {
     "arl_ppg_head_loss_parts": (_i32, [_vp] * 10 + [_i64, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _i32] +
                                 [_vp] * 8),
     "arl_vtrace_scan": (_i32, [_vp] * 7 + [_f64] * 5 + [_i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "arl_seq_store": (_i32, [C.POINTER(_vp), _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_vp), _vp, _vp]),
+    "arl_seq_prepare": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_vp), _i32, _i32, _vp, _vp, _vp, C.POINTER(_vp),
+                               _vp, _vp]),
+    "arl_r2d2_loss": (_i32, [_vp] * 6 + [_i32] * 7 + [_f64] * 3 + [_vp] * 5),
     "arl_ln_bwd_workspace_bytes": (_i64, []),
     "arl_ln_relu_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp]),
     "arl_ln_relu_bwd": (_i32, [_vp] * 5 + [_i64, _i32, _i32, _vp, _vp, _vp, _vp, C.POINTER(ArlFoldItem), _vp]),
@@ -1415,6 +1419,87 @@ def vtrace_scan(prob, old_prob, actions, values, last_values, rewards, dones, di
                                   ptr(dones), float(discount), float(vtrace_lambda), float(rho_bar), float(c_bar),
                                   float(pg_rho_bar), n_env, horizon, n_actions, ptr(returns), ptr(advantages), ptr(stats),
                                   stream_ptr(stream)), "arl_vtrace_scan")
+
+
+# ---------------------------------------------------------------------------
+# R2D2: stored-state sequences on the replay memory and the sequence loss (csrc/r2d2.hip)
+# ---------------------------------------------------------------------------
+
+def _state_ptrs(tensors, name):
+    for t in tensors:
+        _want(t, torch.float32, name)
+    return (C.c_void_p * max(len(tensors), 1))(*[ptr(t) for t in tensors])
+
+
+def seq_store(state_in, resets, n_env, horizon, size, seq_stride, idx, state_store, reset_ring, stream=None):
+    """One launch (arl_seq_store): the states recorded before every step of the batch whose ring index is a multiple of
+    seq_stride -> state_store[s] f32[n_env, size / seq_stride, H]; every step's reset flag -> reset_ring u8[n_env, size].
+    state_in: 0 .. 2 f32 [n_env * horizon, H] tensors (env-major); resets u8 / bool [n_env * horizon]; idx: the ring
+    index of the batch's step 0."""
+    if len(state_in) != len(state_store):
+        raise ValueError("seq_store: %d states in, %d stores" % (len(state_in), len(state_store)))
+    if resets.dtype == torch.bool:
+        resets = resets.view(torch.uint8)
+    _want(resets, torch.uint8, "resets")
+    _want(reset_ring, torch.uint8, "reset_ring")
+    hidden = state_in[0].shape[-1] if state_in else 0
+    slots = size // max(seq_stride, 1)
+    for a, b in zip(state_in, state_store):
+        if a.numel() != n_env * horizon * hidden or b.numel() != n_env * slots * hidden:
+            raise ValueError("seq_store: state shapes %s -> %s" % (tuple(a.shape), tuple(b.shape)))
+    if resets.numel() != n_env * horizon or reset_ring.numel() != n_env * size:
+        raise ValueError("seq_store: resets holds %d, the ring %d flags" % (resets.numel(), reset_ring.numel()))
+    _check(load().arl_seq_store(_state_ptrs(state_in, "state_in"), len(state_in), hidden, ptr(resets), n_env, horizon,
+                                size, seq_stride, idx, _state_ptrs(state_store, "state_store"), ptr(reset_ring),
+                                stream_ptr(stream)), "arl_seq_store")
+
+
+def seq_prepare(env, slot, seq_len, size, seq_stride, state_store, reset_ring, env_rows, step_rows, state_out, resets_out,
+                stream=None):
+    """One launch (arl_seq_prepare): (env, slot) i32[B] -> env_rows, step_rows i32[B * seq_len] (arl_replay_extract's
+    lists), state_out[s] f32[B, H] <- state_store[s][env, slot], resets_out u8[B * seq_len] <- the ring's flags.  The
+    caller guarantees env < n_env and slot < size / seq_stride."""
+    for t, n in ((env, "env"), (slot, "slot"), (env_rows, "env_rows"), (step_rows, "step_rows")):
+        _want(t, torch.int32, n)
+    _want(reset_ring, torch.uint8, "reset_ring")
+    _want(resets_out, torch.uint8, "resets_out")
+    batch = env.numel()
+    if len(state_out) != len(state_store):
+        raise ValueError("seq_prepare: %d stores, %d states out" % (len(state_store), len(state_out)))
+    if slot.numel() != batch or not env_rows.numel() == step_rows.numel() == resets_out.numel() == batch * seq_len:
+        raise ValueError("seq_prepare: %d sequences of %d rows, lists of %d / %d / %d" % (
+            batch, seq_len, env_rows.numel(), step_rows.numel(), resets_out.numel()))
+    hidden = state_store[0].shape[-1] if state_store else 0
+    for a, b in zip(state_store, state_out):
+        if b.numel() != batch * hidden or a.numel() % max(hidden * (size // max(seq_stride, 1)), 1):
+            raise ValueError("seq_prepare: state shapes %s -> %s" % (tuple(a.shape), tuple(b.shape)))
+    _check(load().arl_seq_prepare(ptr(env), ptr(slot), batch, seq_len, size, seq_stride,
+                                  _state_ptrs(state_store, "state_store"), len(state_store), hidden, ptr(reset_ring),
+                                  ptr(env_rows), ptr(step_rows), _state_ptrs(state_out, "state_out"), ptr(resets_out),
+                                  stream_ptr(stream)), "arl_seq_prepare")
+
+
+def r2d2_loss(q, q_tgt, actions, returns, terminals, is_weights, batch, burn_in, train_len, n, n_actions, gamma_n,
+              rescale_eps, eta, dq, td_abs, loss_rows, priorities, dueling=False, stream=None):
+    """R2D2's loss, gradient and sequence priorities (arl_r2d2_loss): q, q_tgt, dq f32 [batch * U, q_stride] with
+    U = burn_in + train_len + n, rows [sequence][time]; rescale_eps None or <= 0: no value rescaling."""
+    for t, name in ((q, "q"), (q_tgt, "q_tgt"), (returns, "returns"), (dq, "dq"), (td_abs, "td_abs"),
+                    (loss_rows, "loss_rows"), (priorities, "priorities")):
+        _want(t, torch.float32, name)
+    _want(actions, torch.uint8, "actions")
+    if terminals.dtype not in (torch.uint8, torch.bool):
+        raise TypeError("terminals must be uint8/bool")
+    rows = batch * (burn_in + train_len + n)
+    assert actions.numel() == returns.numel() == terminals.numel() == rows, "per-row input sizes"
+    assert q.numel() == q_tgt.numel() == dq.numel() and q.numel() % rows == 0, "q / q_tgt / dq size"
+    assert td_abs.numel() == batch * train_len and loss_rows.numel() == priorities.numel() == batch, "output sizes"
+    if is_weights is not None:
+        _want(is_weights, torch.float32, "is_weights")
+        assert is_weights.numel() == batch, "is_weights size"
+    _check(load().arl_r2d2_loss(ptr(q), ptr(q_tgt), ptr(actions), ptr(returns), ptr(terminals), ptr(is_weights), batch,
+                                burn_in, train_len, n, n_actions, q.numel() // rows, int(dueling), float(gamma_n),
+                                0.0 if rescale_eps is None else float(rescale_eps), float(eta), ptr(dq), ptr(td_abs),
+                                ptr(loss_rows), ptr(priorities), stream_ptr(stream)), "arl_r2d2_loss")
 
 
 # ---------------------------------------------------------------------------

@@ -77,7 +77,8 @@ class DQN(RLAlgorithm):
         if not mid_batch_reset:
             raise NotImplementedError
         if int(policy.recurrent):
-            raise NotImplementedError
+            raise NotImplementedError("%s trains feed-forward Q policies on single transitions; a recurrent Q policy trains "
+                                      "with R2D2 (algos/dqn/r2d2.py) on replayed sequences" % type(self).__name__)
         self.policy = policy
         input_list, loss = self.build_loss(env_spec, policy)
         self.optimizer.initialize(inputs=input_list, loss=loss, target=policy)

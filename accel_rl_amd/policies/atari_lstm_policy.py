@@ -153,6 +153,89 @@ class RecurrentCnnPolicy(AtariCnnPolicy):
         return action, infos
 
     # ---- training: BPTT over each environment's segment ----------------------------
+    def _forward_scan(self, xf, nb, t_len, w, init, resets=None, idx=None, tag="", keep=True):
+        """The recurrent layer over rows [trajectory][time] (nb x t_len) of conv features xf, with the (W, b) views `w`,
+        from the states `init` (one [nb, H] tensor per state key).  With `resets` the previous state of step t > 0 is the
+        masked copy one arl_seq_handover launch leaves (see loss_and_grads).  keep=False (a pass nothing is differentiated
+        through): the per-step values of the backward pass are not stored.  `tag` keeps the scratch of a second scan
+        apart.  Returns what _backward_scan and _recurrent_grads read."""
+        hh, gm, n_state, k = self._H, self._gate_mult, len(self._state_keys), self._k_x
+        rows = nb * t_len
+        buf = lambda name, cols: self._buffer((name + tag, rows), (rows, cols))           # noqa: E731
+        gx = buf("gx_all", gm * hh)
+        saved = buf("saved_all", self._saved_mult * hh) if (self._saved_mult and keep) else None
+        st_all = [buf("state%d_all" % i, hh) for i in range(n_state)]
+        hprev_all = buf("hprev_all", hh)
+        g_xh = self._geom(rows, self._rec_fan, gm * hh)
+        _lib.conv2d_fwd(xf, w[k], w[k + 2], gx, g_xh, False, self._conv_ws)
+        sl = lambda a, t: a.view(nb, t_len, -1)[:, t]                                 # noqa: E731  time slice, strided rows
+        prev_at = lambda t: init if t == 0 else [sl(s, t - 1) for s in st_all]        # noqa: E731
+        hp = self._buffer(("hp" + tag, nb), (nb, hh))
+        gh = self._buffer(("gh" + tag, nb), (nb, gm * hh))
+        g_hh = self._geom(nb, hh, gm * hh)
+        mk, flags_at = self._masked_prev_key, None
+        if resets is not None:
+            # the previous state of step t > 0 is the masked copy the hand-over launch leaves: hprev_all's slice
+            # for h, a per-row buffer for the state the cell reads elementwise besides (the LSTM's c)
+            masked = buf("prev%d_masked" % mk, hh) if mk is not None else None
+            flags_at = lambda t: (resets, idx, t, t_len)                              # noqa: E731
+            prev_at = lambda t: init if t == 0 else [                                 # noqa: E731
+                sl(hprev_all, t) if i == 0 else sl(masked, t) for i in range(n_state)]
+        for t in range(t_len):                                                        # forward scan
+            prev = prev_at(t)
+            if resets is None or t == 0:
+                hp.copy_(prev[0])
+                sl(hprev_all, t).copy_(hp)
+            else:
+                _lib.seq_handover(sl(st_all[0], t - 1), None if mk is None else sl(st_all[mk], t - 1),
+                                  flags_at(t - 1), hp, prev[0], None if mk is None else prev[mk])
+            _lib.conv2d_fwd(hp, w[k + 1], None, gh, g_hh, False, self._conv_ws)
+            self._cell_fwd(sl(gx, t), gh, prev, [sl(s, t) for s in st_all], None if saved is None else sl(saved, t))
+        return dict(nb=nb, t_len=t_len, w=w, st_all=st_all, hprev_all=hprev_all, saved=saved, prev_at=prev_at,
+                    flags_at=flags_at, sl=sl, g_xh=g_xh, g_hh=g_hh, tag=tag)
+
+    def _backward_scan(self, scan, dh_all, t_lo, t_hi):
+        """BPTT through steps t_hi - 1 .. t_lo of a _forward_scan, given dh_all = d loss / d h of every row: the gate
+        gradients of those steps into scan["dgx"] / scan["dgh"] (rows of other steps are not written).  No gradient
+        enters from steps >= t_hi and none leaves towards steps < t_lo."""
+        nb, t_len, sl, saved, st_all = scan["nb"], scan["t_len"], scan["sl"], scan["saved"], scan["st_all"]
+        hh, gm, w, k, rows = self._H, self._gate_mult, scan["w"], self._k_x, scan["nb"] * scan["t_len"]
+        buf = lambda name, cols: self._buffer((name + scan["tag"], rows), (rows, cols))   # noqa: E731
+        dgx = buf("dgx_all", gm * hh)
+        dgh = buf("dgh_all", gm * hh) if self._separate_dgh else dgx
+        carry = self._buffer(("carry", nb), (nb, hh))
+        dh_rec = self._buffer(("dh_rec", nb), (nb, hh))
+        dg_t = self._buffer(("dg_t", nb), (nb, gm * hh))
+        flags_at = scan["flags_at"]
+        for t in range(t_hi - 1, t_lo - 1, -1):
+            last = t == t_hi - 1
+            self._cell_bwd(sl(dh_all, t), None if last else dh_rec, carry, last,
+                           None if saved is None else sl(saved, t), scan["prev_at"](t), [sl(s, t) for s in st_all],
+                           sl(dgx, t), sl(dgh, t), *(() if flags_at is None else (flags_at(t),)))
+            if t > t_lo:
+                dg_t.copy_(sl(dgh, t))
+                _lib.conv2d_bwd_data(dg_t, w[k + 1], None, dh_rec, scan["g_hh"])
+        scan["dgx"], scan["dgh"] = dgx, dgh
+
+    def _recurrent_grads(self, scan, x, acts, xf):
+        """Parameter gradients of the recurrent layer from the gate gradients of _backward_scan, then the conv stack's."""
+        hh, gm, w, g, k = self._H, self._gate_mult, scan["w"], self.grads, self._k_x
+        rows, dgx, dgh, g_xh = scan["nb"] * scan["t_len"], scan["dgx"], scan["dgh"], scan["g_xh"]
+        buf = lambda name, cols: self._buffer((name, rows), (rows, cols))            # noqa: E731
+        _lib.conv2d_bwd_weight(dgh, scan["hprev_all"], self._g[k + 1], self._geom(rows, hh, gm * hh), self._conv_ws)
+        _lib.conv2d_bwd_weight(dgx, xf, self._g[k], g_xh, self._conv_ws)
+        dxf = buf("dxf", self._rec_fan)
+        _lib.conv2d_bwd_data(dgx, w[k], None, dxf, g_xh)
+        # db = column sums of dgx = the weight gradient of a 4-channel all-ones input (column 0)
+        ones = buf("ones4", 4)
+        if not getattr(ones, "_filled", False):
+            ones.fill_(1.)
+            ones._filled = True
+        db4 = self._buffer(("db4", gm * hh), (gm * hh, 4))
+        _lib.conv2d_bwd_weight(dgx, ones, db4, self._geom(rows, 4, gm * hh), self._conv_ws)
+        g[k + 2].copy_(db4[:, 0])
+        self._backward_convs(x, acts, dxf.view(acts[-1].shape))
+
     def traj_minibatch(self, mb):
         """mb with `traj` (i32[n_seg] segment numbers) and `horizon` -> mb plus what one arl_traj_minibatch launch
         derives from them: `traj_idx` (the segments' rows in time order), `traj_state` (the stored state before each
@@ -179,7 +262,7 @@ class RecurrentCnnPolicy(AtariCnnPolicy):
         if mb.get("idx") is not None:
             raise NotImplementedError("recurrent training takes whole trajectories: no row minibatches")
         with torch.no_grad():
-            t_len, hh, gm, n_state = int(mb["horizon"]), self._H, self._gate_mult, len(self._state_keys)
+            t_len, hh = int(mb["horizon"]), self._H
             idx = traj_state = None
             if mb.get("traj") is not None:
                 if "traj_idx" not in mb:
@@ -191,74 +274,23 @@ class RecurrentCnnPolicy(AtariCnnPolicy):
             rows = x.shape[0]
             nb = rows // t_len
             assert nb * t_len == rows
-            w, g, k, kh = self._w, self.grads, self._k_x, self._k_head
+            g, kh = self.grads, self._k_head
             acts, xf = self._conv_features(x)
-            buf = lambda name, cols: self._buffer((name, rows), (rows, cols))            # noqa: E731
-            gx, dgx = buf("gx_all", gm * hh), buf("dgx_all", gm * hh)
-            dgh = buf("dgh_all", gm * hh) if self._separate_dgh else dgx
-            saved = buf("saved_all", self._saved_mult * hh) if self._saved_mult else None
-            st_all = [buf("state%d_all" % i, hh) for i in range(n_state)]
-            hprev_all = buf("hprev_all", hh)
-            g_xh = self._geom(rows, self._rec_fan, gm * hh)
-            _lib.conv2d_fwd(xf, w[k], w[k + 2], gx, g_xh, False, self._conv_ws)
-            sl = lambda a, t: a.view(nb, t_len, -1)[:, t]                                 # noqa: E731  time slice, strided rows
-            init = [sl(mb[key], 0) for key in self._state_keys] if traj_state is None else traj_state
-            prev_at = lambda t: init if t == 0 else [sl(s, t - 1) for s in st_all]        # noqa: E731
-            hp = self._buffer(("hp", nb), (nb, hh))
-            gh = self._buffer(("gh", nb), (nb, gm * hh))
-            g_hh = self._geom(nb, hh, gm * hh)
-            resets, mk = mb.get("resets"), self._masked_prev_key
-            if resets is not None:
-                # the previous state of step t > 0 is the masked copy the hand-over launch leaves: hprev_all's slice
-                # for h, a per-row buffer for the state the cell reads elementwise besides (the LSTM's c)
-                masked = buf("prev%d_masked" % mk, hh) if mk is not None else None
-                flags_at = lambda t: (resets, idx, t, t_len)                              # noqa: E731
-                prev_at = lambda t: init if t == 0 else [                                 # noqa: E731
-                    sl(hprev_all, t) if i == 0 else sl(masked, t) for i in range(n_state)]
-            for t in range(t_len):                                                        # forward scan
-                prev = prev_at(t)
-                if resets is None or t == 0:
-                    hp.copy_(prev[0])
-                    sl(hprev_all, t).copy_(hp)
-                else:
-                    _lib.seq_handover(sl(st_all[0], t - 1), None if mk is None else sl(st_all[mk], t - 1),
-                                      flags_at(t - 1), hp, prev[0], None if mk is None else prev[mk])
-                _lib.conv2d_fwd(hp, w[k + 1], None, gh, g_hh, False, self._conv_ws)
-                self._cell_fwd(sl(gx, t), gh, prev, [sl(s, t) for s in st_all], None if saved is None else sl(saved, t))
+            init = traj_state
+            if init is None:
+                init = [mb[key].view(nb, t_len, -1)[:, 0] for key in self._state_keys]
+            scan = self._forward_scan(xf, nb, t_len, self._w, init, mb.get("resets"), idx)
+            st_all = scan["st_all"]
             # ---- heads + losses on every step
             dout = self._buffer(("dout", rows), (rows, self.n_act + 1))
-            dh_all = buf("dh_all", hh)
+            dh_all = self._buffer(("dh_all", rows), (rows, hh))
             loss4 = self._buffer(("loss", rows), (4,))
             _lib.pg_head_loss(st_all[0], self.params[kh], self.params[kh + 1], mb["actions"], mb["advantages"],
                               mb["returns"], mb.get("old_prob"), mb.get("valids"), idx, lr_mult, inv_count,
                               self.n_act, kind, clip_param, v_loss_coeff, ent_loss_coeff, dout, dh_all, g[kh],
                               g[kh + 1], loss4, self._loss_ws, tie_rule=tie_rule)
-            # ---- backward scan
-            carry = self._buffer(("carry", nb), (nb, hh))
-            dh_rec = self._buffer(("dh_rec", nb), (nb, hh))
-            dg_t = self._buffer(("dg_t", nb), (nb, gm * hh))
-            for t in range(t_len - 1, -1, -1):
-                last = t == t_len - 1
-                self._cell_bwd(sl(dh_all, t), None if last else dh_rec, carry, last,
-                               None if saved is None else sl(saved, t), prev_at(t), [sl(s, t) for s in st_all],
-                               sl(dgx, t), sl(dgh, t), *(() if resets is None else (flags_at(t),)))
-                if t > 0:
-                    dg_t.copy_(sl(dgh, t))
-                    _lib.conv2d_bwd_data(dg_t, w[k + 1], None, dh_rec, g_hh)
-            # ---- parameter gradients of the recurrent layer, then the conv stack
-            _lib.conv2d_bwd_weight(dgh, hprev_all, self._g[k + 1], self._geom(rows, hh, gm * hh), self._conv_ws)
-            _lib.conv2d_bwd_weight(dgx, xf, self._g[k], g_xh, self._conv_ws)
-            dxf = buf("dxf", self._rec_fan)
-            _lib.conv2d_bwd_data(dgx, w[k], None, dxf, g_xh)
-            # db = column sums of dgx = the weight gradient of a 4-channel all-ones input (column 0)
-            ones = buf("ones4", 4)
-            if not getattr(ones, "_filled", False):
-                ones.fill_(1.)
-                ones._filled = True
-            db4 = self._buffer(("db4", gm * hh), (gm * hh, 4))
-            _lib.conv2d_bwd_weight(dgx, ones, db4, self._geom(rows, 4, gm * hh), self._conv_ws)
-            g[k + 2].copy_(db4[:, 0])
-            self._backward_convs(x, acts, dxf.view(acts[-1].shape))
+            self._backward_scan(scan, dh_all, 0, t_len)
+            self._recurrent_grads(scan, x, acts, xf)
             return loss4
 
 

@@ -24,7 +24,73 @@ from accel_rl_amd import _lib
 from accel_rl_amd.policies.atari_cnn_policy import AtariCnnPolicy, ObsRows, _norm_c
 
 
-class QPolicyBase(AtariCnnPolicy):
+class EpsGreedyTargetMixin(object):
+    """What every epsilon-greedy Q policy keeps besides its network, whatever the network is (feed-forward: QPolicyBase;
+    recurrent: AtariR2d2Policy): the target network as a second flat bucket, epsilon, and the override tables that carry
+    a whole rollout's host draws to the device.  The host class provides flat_params, _shapes, _offsets, n_act and
+    device (AtariCnnPolicy.initialize)."""
+
+    _epsilon = 1
+
+    def _init_target_and_tables(self):
+        self.flat_target = self.flat_params.clone()             # target network (:57-61)
+        sizes = [int(np.prod(s)) for s in self._shapes]
+        self._w_target = [self.flat_target[o:o + n] for o, n in zip(self._offsets, sizes)]
+        self._overrides = dict()          # n_envs -> (pinned host, device) i32[horizon][n_envs], the last one drawn
+        self._override_tables = dict()    # (n_envs, horizon) -> the same pair, kept for good (_select_overrides)
+        self._step = 0
+
+    def _step_overrides(self, b):
+        if b in self._overrides and self._step < self._overrides[b][1].shape[0]:
+            return self._overrides[b][1][self._step]
+        return None
+
+    # ---- epsilon-greedy draws (host RNG, reference order) ---------------------
+    def host_draws(self, horizon, n_envs, n_groups=2):
+        """All of one rollout's action randomness: for every (step, group) the reference's
+        get_actions draws rand(B) and then sample_n(#(rand < epsilon)).  Returns the uniforms the
+        sampler feeds its categorical kernel (0.5: with a one-hot row that selects the hot action)."""
+        ov = np.full((horizon, n_envs), -1, np.int32)
+        per = n_envs // n_groups
+        for s in range(horizon):
+            for j in range(n_groups):
+                u = np.random.rand(per)
+                idx = np.where(u < self._epsilon)[0]
+                ov[s, j * per + idx] = np.random.randint(low=0, high=self.n_act, size=len(idx), dtype=np.uint8)
+        # one table per env count (training / evaluation), allocated once: a captured rollout graph
+        # keeps reading the same device buffer
+        host, dev = self._select_overrides(horizon, n_envs, lambda: (
+            torch.zeros(ov.shape, dtype=torch.int32).pin_memory(),
+            torch.zeros(ov.shape, dtype=torch.int32, device=self.device)))
+        host.copy_(torch.from_numpy(ov))
+        dev.copy_(host, non_blocking=True)
+        return np.full(horizon * n_envs, 0.5)
+
+    def _select_overrides(self, horizon, n_envs, make):
+        """Make (once) and select the (pinned host, device) tables of one (env count, horizon).  A table is never
+        replaced: a captured rollout graph holds its device address, and training and evaluation may serve the same
+        number of envs over different horizons -- a table reallocated at every switch between them would leave the
+        graph reading whichever block the allocator happened to hand out for the one before."""
+        key = (n_envs, horizon)
+        if key not in self._override_tables:
+            self._override_tables[key] = make()
+        self._overrides[n_envs] = self._override_tables[key]
+        return self._overrides[n_envs]
+
+    def set_step(self, s):
+        self._step = s
+
+    def get_epsilon(self):
+        return self._epsilon
+
+    def set_epsilon(self, value):
+        self._epsilon = value
+
+    def update_target(self):
+        self.flat_target.copy_(self.flat_params)
+
+
+class QPolicyBase(EpsGreedyTargetMixin, AtariCnnPolicy):
     """Subclasses give `_head_width` (columns of the output layer as stored), `_serve(out, override, onehot,
     greedy)` (the action kernel; or, where the network is not `_logits`, `_serve_obs`) and the four `_head_*` layout
     hooks."""
@@ -89,12 +155,7 @@ class QPolicyBase(AtariCnnPolicy):
 
     def initialize(self, env_spec, device=None, **kwargs):
         super().initialize(env_spec, device=device, **kwargs)
-        self.flat_target = self.flat_params.clone()             # target network (:57-61)
-        sizes = [int(np.prod(s)) for s in self._shapes]
-        self._w_target = [self.flat_target[o:o + n] for o, n in zip(self._offsets, sizes)]
-        self._overrides = dict()          # n_envs -> (pinned host, device) i32[horizon][n_envs], the last one drawn
-        self._override_tables = dict()    # (n_envs, horizon) -> the same pair, kept for good (_select_overrides)
-        self._step = 0
+        self._init_target_and_tables()
         if self._dueling:                 # 1 on the two blocks of the output matrix that exist, 0 elsewhere
             hs = self.hidden_sizes[0]
             adv_rows, val_rows = self._duel_blocks()
@@ -195,11 +256,6 @@ class QPolicyBase(AtariCnnPolicy):
         """The network on `observations`, then the action kernel: what the three serving calls below share."""
         self._serve(self._logits(self._scaled(observations))[0], override, onehot, greedy)
 
-    def _step_overrides(self, b):
-        if b in self._overrides and self._step < self._overrides[b][1].shape[0]:
-            return self._overrides[b][1][self._step]
-        return None
-
     def prob_value(self, observations):
         """The sampler's serving call: a one-hot 'prob' row for the epsilon-greedy action of this
         step (so that the categorical sampling kernel picks it) and a zero 'value'."""
@@ -233,41 +289,6 @@ class QPolicyBase(AtariCnnPolicy):
             self._serve_obs(observations, None, onehot, greedy)
             return greedy
 
-    # ---- epsilon-greedy draws (host RNG, reference order) ---------------------
-    def host_draws(self, horizon, n_envs, n_groups=2):
-        """All of one rollout's action randomness: for every (step, group) the reference's
-        get_actions draws rand(B) and then sample_n(#(rand < epsilon)).  Returns the uniforms the
-        sampler feeds its categorical kernel (0.5: with a one-hot row that selects the hot action)."""
-        ov = np.full((horizon, n_envs), -1, np.int32)
-        per = n_envs // n_groups
-        for s in range(horizon):
-            for j in range(n_groups):
-                u = np.random.rand(per)
-                idx = np.where(u < self._epsilon)[0]
-                ov[s, j * per + idx] = np.random.randint(low=0, high=self.n_act, size=len(idx), dtype=np.uint8)
-        # one table per env count (training / evaluation), allocated once: a captured rollout graph
-        # keeps reading the same device buffer
-        host, dev = self._select_overrides(horizon, n_envs, lambda: (
-            torch.zeros(ov.shape, dtype=torch.int32).pin_memory(),
-            torch.zeros(ov.shape, dtype=torch.int32, device=self.device)))
-        host.copy_(torch.from_numpy(ov))
-        dev.copy_(host, non_blocking=True)
-        return np.full(horizon * n_envs, 0.5)
-
-    def _select_overrides(self, horizon, n_envs, make):
-        """Make (once) and select the (pinned host, device) tables of one (env count, horizon).  A table is never
-        replaced: a captured rollout graph holds its device address, and training and evaluation may serve the same
-        number of envs over different horizons -- a table reallocated at every switch between them would leave the
-        graph reading whichever block the allocator happened to hand out for the one before."""
-        key = (n_envs, horizon)
-        if key not in self._override_tables:
-            self._override_tables[key] = make()
-        self._overrides[n_envs] = self._override_tables[key]
-        return self._overrides[n_envs]
-
-    def set_step(self, s):
-        self._step = s
-
     def get_actions(self, observations, deterministic=False):
         """Host-interface twin of the reference's get_actions (one group of one step)."""
         acts = self.greedy_actions(observations).cpu().numpy()
@@ -282,15 +303,6 @@ class QPolicyBase(AtariCnnPolicy):
         else:
             action = self.action_space.sample()
         return action, dict()
-
-    def get_epsilon(self):
-        return self._epsilon
-
-    def set_epsilon(self, value):
-        self._epsilon = value
-
-    def update_target(self):
-        self.flat_target.copy_(self.flat_params)
 
     # ---- training: the output layer's backward, then the trunk's ---------------------
     def _head_backward(self, dout, x, acts, hids):

@@ -1281,6 +1281,91 @@ int arl_vtrace_scan(const float* prob, const float* old_prob, const uint8_t* act
                     float* returns, float* advantages, float* stats_or_null, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * R2D2 (Kapturowski et al. 2019; the reference has none): replayed sequences from a stored recurrent state.
+ * csrc/r2d2.hip.  A sequence is U = burn_in + train_len + n consecutive steps of one environment's ring
+ * (arl_replay: `size` steps per environment); sequences start at the ring indices that are multiples of the sequence
+ * stride S (slot k starts at step k * S; size % S == 0), and rows are laid out [sequence][time].
+ * ------------------------------------------------------------------------- */
+
+/* Append side, ONE launch, no arithmetic (states are copied bit for bit).  From one sampler batch (env-major: row
+ * e * horizon + t; step t of the batch lands on ring index (idx + t) mod size, as arl_replay_append's idx):
+ *   state_store[s][e][((idx + t) mod size) / S][:] = state_in[s][e * horizon + t][:]   for every t with
+ *                                                    ((idx + t) mod size) % S == 0: the state BEFORE that step
+ *   reset_ring[e][(idx + t) mod size]              = resets[e * horizon + t]           for every t
+ *   state_in / state_store: HOST arrays of n_state (0 .. 2) device pointers, f32[n_env * horizon][hidden] and
+ *   f32[n_env][size / S][hidden], 16-byte aligned (else ARL_E_ALIGN; both may be NULL with n_state == 0);
+ *   resets u8[n_env * horizon]; reset_ring u8[n_env][size].
+ * Null pointers: ARL_E_ARG.  ARL_E_RANGE, nothing launched and no output written: n_env, horizon, size or seq_stride
+ * < 1, horizon % seq_stride != 0, size % seq_stride != 0, horizon > size, idx outside 0 .. size - 1, n_state outside
+ * 0 .. 2, hidden % 4 != 0, hidden > 1024.  One workgroup per environment: a latency-bound launch.                   */
+int arl_seq_store(const float* const* state_in, int32_t n_state, int32_t hidden, const uint8_t* resets,
+                  int32_t n_env, int32_t horizon, int32_t size, int32_t seq_stride, int32_t idx,
+                  float* const* state_store, uint8_t* reset_ring, void* stream);
+
+/* Sample side, ONE launch, no arithmetic.  env i32[batch], slot i32[batch] (the sum tree's, or the host's, on the
+ * device); for sequence j and t = 0 .. seq_len - 1:
+ *   env_rows[j * seq_len + t]   = env[j]
+ *   step_rows[j * seq_len + t]  = (slot[j] * S + t) mod size            the lists arl_replay_extract takes
+ *   resets_out[j * seq_len + t] = reset_ring[env[j]][that step]
+ *   state_out[s][j][:]          = state_store[s][env[j]][slot[j]][:]    the state BEFORE the sequence's first step
+ *   state_store / state_out: HOST arrays of n_state (0 .. 2) device pointers, f32[n_env][size / S][hidden] and
+ *   f32[batch][hidden], 16-byte aligned (else ARL_E_ALIGN).  (env, slot) pairs may repeat.
+ * The CALLER guarantees 0 <= env[j] < n_env and 0 <= slot[j] < size / S: the numbers live on the device, the host
+ * cannot check them and the kernel clamps nothing (and asserts nothing).
+ * Null pointers: ARL_E_ARG.  ARL_E_RANGE, nothing launched and no output written: batch, seq_len, size or seq_stride
+ * < 1, size % seq_stride != 0, batch * seq_len > 2^31 - 1, n_state outside 0 .. 2, hidden % 4 != 0, hidden > 1024.
+ * One workgroup per sequence: a latency-bound launch.                                                                */
+int arl_seq_prepare(const int32_t* env, const int32_t* slot, int32_t batch, int32_t seq_len, int32_t size,
+                    int32_t seq_stride, const float* const* state_store, int32_t n_state, int32_t hidden,
+                    const uint8_t* reset_ring, int32_t* env_rows, int32_t* step_rows, float* const* state_out,
+                    uint8_t* resets_out, void* stream);
+
+/* R2D2's loss, its gradient and the sequence priorities in ONE launch.  U = burn_in + train_len + n; row (b, t) is row
+ * b * U + t.
+ *   q, q_tgt     f32[batch * U][q_stride]   the online and the target network on the same rows; dueling != 0: rows as
+ *                                           in arl_dqn_act (q_a = val + (adv_a - mean adv))
+ *   actions      u8[batch * U]              a byte >= n_actions is read as n_actions - 1 (arl_dqn_loss indexes with
+ *                                           the byte as it is; here no access leaves the row)
+ *   returns      f32[batch * U]             the replay memory's n-step discounted return
+ *   terminals    u8[batch * U]              terminal inside the n-step window, as arl_replay_extract reports it
+ *   is_weights_or_null f32[batch]
+ * Everything is float64 from the float32 inputs, in exactly this expression order and without contraction, rounded to
+ * float32 once per output.  A merged entry is (double) val + ((double) adv_a - mean), mean = (0.0 + adv_0 + adv_1 ...)
+ * / (double) n_actions.  For every sequence b and train step t = burn_in .. burn_in + train_len - 1:
+ *   a*   = first maximum over a of q[b, t + n, a]                     (merged if dueling)
+ *   x    = q_tgt[b, t + n, a*]                                        (merged if dueling)
+ *   hinv = x                                                          if rescale_eps <= 0, else, with e = rescale_eps,
+ *        = sign(x) * (dl * (dl + 2.0)),  dl = (2.0 * |x|) / ((s + 1.0) + 2.0 * e),
+ *                                        s  = sqrt(1.0 + (4.0 * e) * ((|x| + 1.0) + e))
+ *          (the closed form ((s - 1) / (2 e))^2 - 1 of h's inverse, written without its cancellation near x = 0:
+ *          u = (s - 1) / (2 e) has u - 1 = dl, because s^2 = (1 + 2 e)^2 + 4 e |x|, and u^2 - 1 = dl (dl + 2))
+ *   z    = returns[b, t] + (terminals[b, t] ? 0.0 : gamma_n * hinv)
+ *   y    = z                                                          if rescale_eps <= 0, else
+ *        = sign(z) * (sqrt(|z| + 1.0) - 1.0) + e * z                  (sign(0) = 0)
+ *   d    = y - q[b, t, action]                                        (merged if dueling)
+ * and with w_b = (is_weights[b] or 1.0) / (double) (batch * train_len), the sums and the maximum walked in time order
+ * from 0.0:
+ *   td_abs f32[batch][train_len] = |d|
+ *   loss_rows f32[batch]         = w_b * sum_t 0.5 * (d * d)
+ *   priorities f32[batch]        = eta * max_t |d| + (1.0 - eta) * ((sum_t |d|) / (double) train_len)
+ *   dq f32[batch * U][q_stride]  = the gradient of sum_b loss_rows[b] w.r.t. q: g = -(w_b * d) in the taken action's
+ *                                  column of a train row; dueling: through the merge, g - g / A in the taken
+ *                                  advantage, -(g / A) in the others, g in the value column.  Exact +0 in every
+ *                                  burn-in row, every one of the n trailing rows, every padding column and (without
+ *                                  dueling) every other action.  The target carries no gradient.
+ * loss_rows and priorities need not be adjacent, but may be.  One 64-lane wave per sequence: lanes take train steps
+ * l, l + 64, ...; one lane walks the sums; no atomics, two launches give the same bits.  Indexing is 64-bit.
+ * Refused before any HIP call, nothing written: a NULL pointer other than is_weights_or_null, gamma_n, rescale_eps
+ * or eta not finite (ARL_E_ARG); batch < 1, train_len outside 1 .. 1024, burn_in outside 0 .. 1024, n outside
+ * 1 .. ARL_REPLAY_MAX_HORIZON, n_actions outside 1 .. 255, q_stride % 4 != 0, q_stride < n_actions + (dueling != 0),
+ * batch * U > 2^31 - 1 (ARL_E_RANGE); dq not 16-byte or another float pointer not 4-byte aligned (ARL_E_ALIGN).       */
+int arl_r2d2_loss(const float* q, const float* q_tgt, const uint8_t* actions, const float* returns,
+                  const uint8_t* terminals, const float* is_weights_or_null, int32_t batch, int32_t burn_in,
+                  int32_t train_len, int32_t n, int32_t n_actions, int32_t q_stride, int32_t dueling, double gamma_n,
+                  double rescale_eps, double eta, float* dq, float* td_abs, float* loss_rows, float* priorities,
+                  void* stream);
+
+/* ------------------------------------------------------------------------- *
  * LayerNorm + rectifier between the contraction launches (PQN's Q-network)
  * ------------------------------------------------------------------------- */
 
