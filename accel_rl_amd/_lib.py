@@ -94,12 +94,24 @@ DGRAD_WT_MAX = 4
 
 class ArlServeHead(C.Structure):
     _fields_ = [("hidden", ArlFoldItem), ("hidden_bias", _vp), ("hidden_relu", _i32), ("hid", _i32),
-                ("w_head", _vp), ("b_head", _vp)]
+                ("w_head", _vp), ("b_head", _vp), ("hidden_out", _vp)]
 
 
 class ArlServeConv1(C.Structure):
     _fields_ = [("geom", C.POINTER(ArlConvGeom)), ("w", _vp), ("bias", _vp), ("y", _vp), ("scale", _f32),
                 ("relu", _i32)]
+
+
+class ArlGatherItem(C.Structure):
+    _fields_ = [("src", _vp), ("dst", _vp), ("row_bytes", _i64), ("src_rows", _i64)]
+
+
+GATHER_MAX_ITEMS = 8
+ROW_MAP_IDENTITY, ROW_MAP_STEP_MAJOR = 0, 1       # ARL_ROW_MAP_*
+
+
+class ArlRowMap(C.Structure):
+    _fields_ = [("kind", _i32), ("horizon", _i32), ("n_env", _i32), ("reserved", _i32)]
 
 
 class ArlNoisyLayer(C.Structure):
@@ -156,6 +168,7 @@ _SIGNATURES = {
     "arl_preprocess_frames": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
     "arl_copy_bytes": (_i32, [_vp, _vp, _i64, _vp]),
     "arl_ring_append": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp]),
+    "arl_gather_rows_many": (_i32, [C.POINTER(ArlGatherItem), _i32, _vp, _i64, C.POINTER(ArlRowMap), _vp]),
     "arl_gather_scale_obs": (_i32, [_vp, _vp, _i64, _i64, _f32, _vp, _vp]),
     "arl_gather_scale_obs_nhwc": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp]),
     "arl_traj_minibatch": (_i32, [_vp, _i32, _i32, _i64, C.POINTER(_vp), _i32, _i32, _vp, _vp, C.POINTER(_vp), _vp, _vp]),
@@ -176,6 +189,7 @@ _SIGNATURES = {
                                            _vp, C.POINTER(ArlFoldItem), _vp]),
     "arl_fold_many": (_i32, [C.POINTER(ArlFoldItem), _i32, _vp]),
     "arl_conv2d_fwd_parts": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _i32, _vp, C.POINTER(ArlFoldItem), _vp]),
+    "arl_conv2d_fwd_plan": (_i32, [C.POINTER(ArlConvGeom), C.POINTER(_i32), C.POINTER(_i32)]),
     "arl_serve_conv1_supported": (_i32, [C.POINTER(ArlGame), C.POINTER(ArlConvGeom)]),
     "arl_rollout_begin_conv1": (_i32, [C.POINTER(ArlGame), C.POINTER(ArlEnvState), C.POINTER(ArlRollout),
                                        C.POINTER(ArlServeConv1), _vp]),
@@ -401,6 +415,28 @@ def ring_append(src, ring, counter, stream=None):
                          (src.numel(), tuple(ring.shape)))
     _check(load().arl_ring_append(ptr(src), src.numel(), ptr(ring), ring.shape[0], ptr(counter), stream_ptr(stream)),
            "arl_ring_append")
+
+
+def gather_rows_many(pairs, idx, step_major=None, stream=None):
+    """dst[j] = src[map(idx[j])] for every (src, dst) of `pairs` (at most GATHER_MAX_ITEMS) in one launch: rows of
+    contiguous tensors -- src [src_rows, ...], dst [n_rows, ...] of the same row size and dtype -- picked by one int32
+    index vector (None: rows 0 .. n_rows - 1).  step_major = (horizon, n_env): the sources are laid out [horizon][n_env]
+    and the indices name rows env-major (env * horizon + t); None: the indices are source rows."""
+    if idx is not None:
+        _want(idx, torch.int32, "idx")
+    n_rows = pairs[0][1].shape[0] if idx is None else idx.numel()
+    items = (ArlGatherItem * max(len(pairs), 1))()
+    for it, (src, dst) in zip(items, pairs):
+        if src.dtype != dst.dtype or dst.shape[0] != n_rows or src[0].numel() != dst[0].numel():
+            raise ValueError("gather_rows_many: src %s %s and dst %s %s do not describe the same rows (%d wanted)" %
+                             (tuple(src.shape), src.dtype, tuple(dst.shape), dst.dtype, n_rows))
+        it.src, it.dst = ptr(src), ptr(dst)
+        it.row_bytes, it.src_rows = src[0].numel() * src.element_size(), src.shape[0]
+    row_map = None
+    if step_major is not None:
+        row_map = ArlRowMap(ROW_MAP_STEP_MAJOR, int(step_major[0]), int(step_major[1]), 0)
+    _check(load().arl_gather_rows_many(items, len(pairs), ptr(idx), n_rows, None if row_map is None else C.byref(row_map),
+                                       stream_ptr(stream)), "arl_gather_rows_many")
 
 
 def stream_ptr(stream=None):
@@ -763,6 +799,13 @@ def conv2d_fwd_parts(x, w, bias, y, geom, relu, workspace, stream=None):
                                        y.data_ptr(), C.byref(geom), int(bool(relu)), ptr(workspace), C.byref(item),
                                        stream_ptr(stream)), "arl_conv2d_fwd_parts")
     return item
+
+
+def conv2d_fwd_plan(geom):
+    """(splits, k_per_split) of conv2d_fwd on this geometry (arl_conv2d_fwd_plan; nothing is launched)."""
+    splits, per = _i32(), _i32()
+    _check(load().arl_conv2d_fwd_plan(C.byref(geom), C.byref(splits), C.byref(per)), "arl_conv2d_fwd_plan")
+    return splits.value, per.value
 
 
 def conv2d_u8_supported(in_h, in_w, out_c, kh, kw, stride, pad_h, pad_w):

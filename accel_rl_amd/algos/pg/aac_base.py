@@ -94,8 +94,11 @@ class AdvActorCriticBase(RLAlgorithm):
         self._n_env = sample_size // horizon
         self._std_ws = _lib.standardize_workspace(dev)
         self._lr_mult_host = torch.ones(1, dtype=torch.float32).pin_memory()
-        self._graph = None
-        self._graph_out = None
+        # One captured update per flavour of its first minibatch: True = it takes the rollout's activations over
+        # (_reuse_granted), False = the full forward.  `_graph` / `_graph_out` name the flavour captured first.
+        self._graphs = dict()
+        self._reuse_now = False
+        self._mb_no = 0
         self._graph_samples = None
         self._warm_calls = 0
         self._done_event = None
@@ -104,8 +107,37 @@ class AdvActorCriticBase(RLAlgorithm):
         self._info_ring = None
         self._info_replays = 0
 
+    @property
+    def _graph(self):
+        """The captured update (the flavour captured first); assigning None drops every flavour."""
+        return next(iter(self._graphs.values()))[0] if getattr(self, "_graphs", None) else None
+
+    @_graph.setter
+    def _graph(self, value):
+        if value is not None:
+            raise AttributeError("the update's graphs are captured by _enqueue_optimize; only None (drop them) is assigned")
+        self._graphs = dict()
+
+    @property
+    def _graph_out(self):
+        return next(iter(self._graphs.values()))[1] if getattr(self, "_graphs", None) else None
+
+    @_graph_out.setter
+    def _graph_out(self, value):
+        if value is not None:
+            raise AttributeError("_graph_out belongs to the captured update; only None is assigned")
+        self._graphs = dict()
+
     def set_n_itr(self, n_itr):
         self.n_itr = n_itr
+
+    def _reuse_granted(self, samples_data):
+        """May this call's first minibatch take its trunk activations from the rollout's per-step buffers?  The policy
+        answers (AtariCnnPolicy.stored_acts_for: the sampler's own buffer of its latest batch, no parameter write since
+        its forwards, the same route, the switch) for A2C's and PPO's loss; any doubt is the full forward."""
+        ask = getattr(self.policy, "stored_acts_for", None)
+        return bool(ask is not None and self.loss_kind in (0, 1) and not self._state_info_keys and
+                    ask(samples_data["observations"]) is not None)
 
     def optimize_policy(self, itr, samples_data):
         """reference: aac_base.py:102-106.  Host-side draws (minibatch permutations, lr
@@ -132,23 +164,38 @@ class AdvActorCriticBase(RLAlgorithm):
         sync = tag == "synchronous" and getattr(self.optimizer, "graph_ready", lambda: False)()
         graphable = self.use_graph and hasattr(self.optimizer, "device_updates") and (tag == "single" or sync)
         if not graphable:
-            return self._device_optimize(itr, samples_data)
-        if self._graph is None:
+            return self._run_update(itr, samples_data, self._reuse_granted(samples_data))
+        reuse = self._reuse_granted(samples_data)
+        if not self._graphs:
             self._warm_calls += 1
             if self._warm_calls <= 2:
-                out = self._device_optimize(itr, samples_data)
+                out = self._run_update(itr, samples_data, reuse)
                 self._ensure_info_ring(out[1])              # (allocated here: not from the capture's private pool)
                 return out
+        if reuse not in self._graphs:
+            if self._graphs and not (tag == "single"):
+                # (N > 1: the ranks captured one flavour together; a call of the other one runs eagerly)
+                return self._run_update(itr, samples_data, reuse)
             torch.cuda.synchronize(self.policy.device)
-            graph, failure = torch.cuda.CUDAGraph(), None
+            failure = None
             # a capture that fails part-way leaves the optimiser's host-side call counters advanced by a partial call
             # (no kernel ran): the eager re-run below must start from the state the capture started from
             opt_host = {k: getattr(self.optimizer, k) for k in
                         ("_n_updates", "_hole", "_call_hole", "_hole_count", "_pending_avg") if hasattr(self.optimizer, k)}
             try:
-                with capture_graph(graph):
-                    self._graph_out = self._device_optimize(itr, samples_data)
-                    self._append_infos(self._graph_out[1])
+                # with the first capture of a reusing update its full-forward twin is captured too (a capture runs no
+                # kernel: the host-side counters are put back in between) -- a caller that later updates twice on one
+                # batch, or writes the parameters in between, then replays that one instead of capturing mid-run
+                flavours = [reuse] + ([False] if reuse and tag == "single" and not self._graphs else [])
+                for k, flavour in enumerate(flavours):
+                    if k:
+                        for name, v in opt_host.items():
+                            setattr(self.optimizer, name, v)
+                    graph = torch.cuda.CUDAGraph()
+                    with capture_graph(graph):
+                        out = self._run_update(itr, samples_data, flavour)
+                        self._append_infos(out[1])
+                    self._graphs[flavour] = (graph, out)
             except Exception as e:          # single GPU: a bug, raise.  N > 1: every rank must take the same road
                 if not sync:
                     raise
@@ -162,13 +209,15 @@ class AdvActorCriticBase(RLAlgorithm):
                 for k, v in opt_host.items():
                     setattr(self.optimizer, k, v)
                 torch.cuda.synchronize(self.policy.device)
-                return self._device_optimize(itr, samples_data)
-            self._graph, self._graph_samples = graph, samples_data
+                self._graphs = dict()
+                return self._run_update(itr, samples_data, reuse)
+            self._graph_samples = samples_data
         assert samples_data is self._graph_samples, "the sampler must hand over the same buffer"
-        self._graph.replay()
+        graph, (opt_data, infos) = self._graphs[reuse]
+        graph.replay()
+        self._params_written()              # (the replayed updates: the capture's own count was the capture's)
         # the graph owns its outputs and every replay overwrites them: callers keep the diagnostics across iterations
         # (AccelRL.store_diagnostics) -- the graph itself left this replay's copy in a ring slot
-        opt_data, infos = self._graph_out
         # (the modulus is the ALLOCATED ring's length -- what ring_append's device counter wraps at -- not the current
         #  _ring_slots(): a log interval lowered after the ring was sized must not move the host's idea of the slot)
         slot = self._info_replays % next(iter(self._info_ring.values())).shape[0]
@@ -201,6 +250,19 @@ class AdvActorCriticBase(RLAlgorithm):
         """(inside the capture) every diagnostics tensor of the call -> the next slot of its ring."""
         for k, v in infos.items():
             _lib.ring_append(v.reshape(-1), self._info_ring[k], self._info_counts[k])
+
+    def _params_written(self):
+        note = getattr(self.policy, "note_params_changed", None)
+        if note is not None:
+            note()
+
+    def _run_update(self, itr, samples_data, reuse):
+        """_device_optimize whose FIRST minibatch may take the rollout's activations over (reuse: _reuse_granted)."""
+        self._reuse_now, self._mb_no = bool(reuse), 0
+        try:
+            return self._device_optimize(itr, samples_data)
+        finally:
+            self._reuse_now = False
 
     def _device_optimize(self, itr, samples_data):
         _lib.copy_bytes(self._lr_mult, self._lr_mult_host)
@@ -265,6 +327,13 @@ class AdvActorCriticBase(RLAlgorithm):
             inv_count = (1. / v.sum(dtype=torch.float32)).reshape(1)
         if self._state_info_keys:
             mb = dict(mb, horizon=self._horizon)
+        first, self._mb_no = self._mb_no == 0, self._mb_no + 1
+        if first and self._reuse_now:
+            # the rollout's forwards of these rows ran under the parameters as they stand (asked again here: an eager
+            # call's own updates, or anything else since the grant, withdraw it)
+            store = self.policy.stored_acts_for(mb["observations"])
+            if store is not None:
+                mb = dict(mb, stored_acts=store)
         loss4 = self.policy.loss_and_grads(mb, self.loss_kind, getattr(self, "clip_param", 0.),
                                            self.v_loss_coeff, self.ent_loss_coeff, self._lr_mult,
                                            inv_count, tie_rule=self.loss_tie_rule)

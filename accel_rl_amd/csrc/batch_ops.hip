@@ -216,6 +216,95 @@ extern "C" int arl_copy_bytes(void* dst, const void* src, int64_t nbytes, void* 
     return arl::check_launch("copy_kernel");
 }
 
+// Rows of several arrays by one index vector (arl_gather_rows_many).  A task = (destination row, chunk of one item's
+// row): GR_PER 16-byte vectors per thread, 256 apart (every load instruction of a wave reads 1 KB in one piece), all of a
+// task's loads issued before its first store.  Tasks are dealt to the workgroups round-robin; the item of a chunk is found
+// through a prefix table in the kernel arguments (uniform per workgroup: scalar code).
+namespace {
+constexpr int GR_THREADS = 256, GR_PER = 4, GR_CHUNK = GR_THREADS * GR_PER;
+
+struct GatherArgs {
+    const uint4* src[ARL_GATHER_MAX_ITEMS];
+    uint4* dst[ARL_GATHER_MAX_ITEMS];
+    int64_t row_vec[ARL_GATHER_MAX_ITEMS];      // 16-byte vectors per row
+    int64_t src_rows[ARL_GATHER_MAX_ITEMS];
+    int chunk_start[ARL_GATHER_MAX_ITEMS + 1];  // chunks of a row: item i owns [chunk_start[i], chunk_start[i + 1])
+    const int32_t* idx;
+    int64_t n_rows;
+    int n_items, step_major, horizon, n_env;
+};
+
+__global__ __launch_bounds__(GR_THREADS) void gather_rows_kernel(const GatherArgs a) {
+    typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+    const int chunks = a.chunk_start[a.n_items];
+    const int64_t tasks = a.n_rows * chunks;
+    for (int64_t task = blockIdx.x; task < tasks; task += gridDim.x) {
+        const int64_t j = task / chunks;
+        const int c = (int)(task - j * chunks);
+        int it = 0;
+        while (it + 1 < a.n_items && c >= a.chunk_start[it + 1]) ++it;      // uniform
+        int64_t r = a.idx ? (int64_t)a.idx[j] : j;
+        if (a.step_major) {
+            // (a negative index must stay outside after the map: C division would fold it back into range)
+            r = r >= 0 ? (r % a.horizon) * (int64_t)a.n_env + r / a.horizon : -1;
+        }
+        if (r < 0 || r >= a.src_rows[it]) r = 0;                            // never a wild read
+        const int64_t vecs = a.row_vec[it];
+        const int64_t v0 = (int64_t)(c - a.chunk_start[it]) * GR_CHUNK + threadIdx.x;
+        const u32x4_t* s = reinterpret_cast<const u32x4_t*>(a.src[it] + r * vecs);
+        uint4* d = a.dst[it] + j * vecs;
+        u32x4_t v[GR_PER];
+#pragma unroll
+        for (int k = 0; k < GR_PER; ++k)
+            if (v0 + GR_THREADS * k < vecs) v[k] = __builtin_nontemporal_load(s + v0 + GR_THREADS * k);     // read once
+#pragma unroll
+        for (int k = 0; k < GR_PER; ++k)
+            if (v0 + GR_THREADS * k < vecs) d[v0 + GR_THREADS * k] = make_uint4(v[k].x, v[k].y, v[k].z, v[k].w);
+    }
+}
+}  // namespace
+
+extern "C" int arl_gather_rows_many(const arl_gather_item* items, int32_t n_items, const int32_t* idx_or_null,
+                                    int64_t n_rows, const arl_row_map* row_map_or_null, void* stream) {
+    ARL_REQUIRE(items, ARL_E_ARG, "null pointer");
+    ARL_REQUIRE(n_items >= 1 && n_items <= ARL_GATHER_MAX_ITEMS, ARL_E_RANGE, "1 <= n_items <= ARL_GATHER_MAX_ITEMS");
+    ARL_REQUIRE(n_rows >= 1 && n_rows <= INT32_MAX, ARL_E_RANGE, "1 <= n_rows <= 2^31 - 1");
+    ARL_REQUIRE(arl::aligned4(idx_or_null), ARL_E_ALIGN, "idx must be 4-byte aligned");
+    GatherArgs a = {};
+    if (row_map_or_null && row_map_or_null->kind != ARL_ROW_MAP_IDENTITY) {
+        const arl_row_map& m = *row_map_or_null;
+        ARL_REQUIRE(m.kind == ARL_ROW_MAP_STEP_MAJOR, ARL_E_RANGE, "row_map kind: ARL_ROW_MAP_IDENTITY or _STEP_MAJOR");
+        ARL_REQUIRE(m.horizon >= 1 && m.n_env >= 1 && (int64_t)m.horizon * m.n_env <= INT32_MAX, ARL_E_RANGE,
+                    "step-major map: horizon >= 1, n_env >= 1, horizon * n_env <= 2^31 - 1");
+        a.step_major = 1; a.horizon = m.horizon; a.n_env = m.n_env;
+    }
+    int64_t total_vec = 0;
+    for (int i = 0; i < n_items; ++i) {
+        const arl_gather_item& it = items[i];
+        ARL_REQUIRE(it.src && it.dst && it.src_rows >= 1, ARL_E_ARG, "item: null pointer / src_rows < 1");
+        ARL_REQUIRE(it.row_bytes > 0 && (it.row_bytes & 15) == 0 && it.row_bytes <= ((int64_t)1 << 30), ARL_E_RANGE,
+                    "row_bytes must be a positive multiple of 16, <= 2^30");
+        ARL_REQUIRE(it.src_rows <= INT32_MAX, ARL_E_RANGE, "src_rows <= 2^31 - 1");
+        ARL_REQUIRE(arl::aligned16(it.src) && arl::aligned16(it.dst), ARL_E_ALIGN, "src and dst must be 16-byte aligned");
+        if (!idx_or_null) {         // the indices are the host's: 0 .. n_rows - 1 through the map
+            const int64_t span = a.step_major ? (int64_t)a.horizon * a.n_env : n_rows;
+            ARL_REQUIRE(n_rows <= span && span <= it.src_rows, ARL_E_RANGE, "identity rows outside the source");
+        }
+        a.src[i] = (const uint4*)it.src; a.dst[i] = (uint4*)it.dst;
+        a.row_vec[i] = it.row_bytes >> 4; a.src_rows[i] = it.src_rows;
+        const int64_t chunks = (a.row_vec[i] + GR_CHUNK - 1) / GR_CHUNK;
+        ARL_REQUIRE(a.chunk_start[i] + chunks <= (1 << 24), ARL_E_RANGE, "rows too long");
+        a.chunk_start[i + 1] = a.chunk_start[i] + (int)chunks;
+        total_vec += a.row_vec[i];
+    }
+    a.idx = idx_or_null; a.n_rows = n_rows; a.n_items = n_items;
+    const int64_t tasks = n_rows * a.chunk_start[n_items];
+    unsigned grid = arl::stream_grid(n_rows * total_vec, GR_THREADS);      // sized from the bytes: 16 per thread and pass
+    if ((int64_t)grid > tasks) grid = (unsigned)tasks;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(grid), dim3(GR_THREADS), 0, (hipStream_t)stream, a);
+    return arl::check_launch("gather_rows_kernel");
+}
+
 extern "C" int arl_gather_scale_obs(const uint8_t* obs, const int32_t* idx_or_null, int64_t batch,
                                     int64_t row_bytes, float scale, float* out, void* stream) {
     ARL_REQUIRE(obs && out, ARL_E_ARG, "null pointer");

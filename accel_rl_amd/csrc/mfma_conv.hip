@@ -168,6 +168,20 @@ extern "C" int arl_corun_job_run(const arl_corun_job* job, void* stream) {
 }
 
 namespace {
+// The forward's reduction split for M rows x N columns over K (under the calling scope's route); returns `small`.
+bool fwd_plan(int M, int N, int K, int* splits, int* per) {
+    *splits = 1; *per = round_up(K, BKT);
+    const bool small = N >= 128 && (int64_t)M * N <= (int64_t)1 << 20;     // dense layers: split K
+    // (the bf16-split kernels have no 16-wide tiles: 64x64 there)
+    const bool small32 = small && !g_split;         // 32x64 tiles: half the splits (and partial bytes) for the same grid
+    if (small) plan_split(((M + (small32 ? 31 : 63)) / (small32 ? 32 : 64)) * ((N + 63) / 64), K, splits, per, 3 * TARGET_WGS);
+    // ... and wider ones whose 128x128 tiles still leave CUs idle (spec-0 dense at the A2C batch: 5120 x 256 =
+    // 80 tiles walking 88 k-tiles each, 231 us)
+    const int tiles128 = ((M + 127) / 128) * ((N + 127) / 128);
+    if (!small && N >= 128 && tiles128 * 4 <= TARGET_WGS * 3) plan_split(tiles128, K, splits, per, TARGET_WGS);
+    return small;
+}
+
 // parts: leave a split reduction unfolded and describe it (arl_conv2d_fwd_parts); null = fold here
 int fwd_impl(const float* x, const float* w, const float* bias_or_null, float* y, const arl_conv_geom* geom, int32_t relu,
              void* workspace, void* stream, arl_fold_item* parts = nullptr) {
@@ -185,15 +199,10 @@ int fwd_impl(const float* x, const float* w, const float* bias_or_null, float* y
     a.g.src_bytes = (unsigned)(g.batch * g.H * g.W * g.C * 4);
     a.b.w = w; a.b.ld = a.K; a.b.w_bytes = (unsigned)((int64_t)a.N * a.K * 4);
     a.o.dense = 1; a.trace = g_trace; a.xcd = 1;
-    int splits = 1, per = round_up(a.K, BKT);
-    const bool small = a.N >= 128 && (int64_t)a.M * a.N <= (int64_t)1 << 20;     // dense layers: split K
-    // (the bf16-split kernels have no 16-wide tiles: 64x64 there)
-    const bool small32 = small && !g_split;         // 32x64 tiles: half the splits (and partial bytes) for the same grid
-    if (small) plan_split(((a.M + (small32 ? 31 : 63)) / (small32 ? 32 : 64)) * ((a.N + 63) / 64), a.K, &splits, &per, 3 * TARGET_WGS);
-    // ... and wider ones whose 128x128 tiles still leave CUs idle (spec-0 dense at the A2C batch: 5120 x 256 =
-    // 80 tiles walking 88 k-tiles each, 231 us)
+    int splits, per;
+    const bool small = fwd_plan(a.M, a.N, a.K, &splits, &per);
+    const bool small32 = small && !g_split;
     const int tiles128 = ((a.M + 127) / 128) * ((a.N + 127) / 128);
-    if (!small && a.N >= 128 && tiles128 * 4 <= TARGET_WGS * 3) plan_split(tiles128, a.K, &splits, &per, TARGET_WGS);
     // ... and unsplit ones whose 128x128 tiles fill the last round of CUs badly (160 tiles on 256 CUs: 62 %): 64x64 tiles,
     // four times the workgroups, when their fill beats it by more than their lower per-tile efficiency (0.85) -- spec-1
     // dense at 5 120 rows 378.7 -> 309.4 us, 10 240 x 3 456 -> 256: 194.2 -> 160.7, 20 000 x 256 -> 128: 21.1 -> 17.3; 256
@@ -280,6 +289,21 @@ extern "C" int arl_conv2d_fwd_parts(const float* x, const float* w, const float*
     ARL_REQUIRE(item, ARL_E_ARG, "null pointer");
     ARL_ROUTE_SCOPE(geom, nullptr);
     return fwd_impl(x, w, bias_or_null, y, geom, relu, workspace, stream, item);
+}
+
+extern "C" int arl_conv2d_fwd_plan(const arl_conv_geom* geom, int32_t* splits, int32_t* k_per_split) {
+    ARL_REQUIRE(splits && k_per_split, ARL_E_ARG, "null pointer");
+    ARL_REQUIRE(split_of(geom) >= 0, ARL_E_ARG, "conv route: ARL_CONV_ROUTE_SPLIT9, _FP32, _SPLIT6 or _BF16");
+    Geom g;
+    int rc = check_geom(geom, &g);
+    if (rc) return rc;
+    const int saved = g_split;                      // (no CallScope: a query leaves the thread's launch log alone)
+    g_split = split_of(geom);
+    int s, per;
+    fwd_plan((int)(g.batch * g.Ho * g.Wo), g.K, g.kh * g.kw * g.C, &s, &per);
+    g_split = saved;
+    *splits = s; *k_per_split = per;
+    return 0;
 }
 
 extern "C" int arl_conv2d_fwd(const float* x, const float* w, const float* bias_or_null, float* y,

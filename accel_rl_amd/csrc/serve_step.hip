@@ -45,6 +45,7 @@ struct ServeHead {
     const float4* bias;         // [hid / 4] or null
     const float* w_head;        // [A + 1][hid]
     const float* b_head;        // [A + 1]
+    float4* hidden_out;         // [n_env][hid / 4] or null: the folded, biased, rectified hidden rows, kept for the learner
     int64_t total4;             // n_env * hid / 4
     int splits, zgn, hid, relu;
 };
@@ -57,7 +58,8 @@ struct ServeHead {
 //            is known before the heads are evaluated and the lane of the action drawn later simply commits ITS outcome
 //   waves 1+ meanwhile: the hidden layer's split partial sums, fold_splits_kernel's first level
 //   sync A   -> frame loads issued (they fly under everything below), weights split into LDS, arrival ticket;
-//            fold's second level + bias + rectifier
+//            fold's second level + bias + rectifier (with hd.hidden_out the finished row also goes to memory: the
+//            learner's first minibatch takes it over instead of computing it again, arl_gather_rows_many)
 //   sync B   -> head rows (one per wave, butterfly sums); pixels boxed and stored (rollout buffer + LDS)
 //   sync C   -> wave 0: softmax, the draw, commit;  waves 1+: conv 1 of the new observation from LDS
 template <bool CONV1>
@@ -193,6 +195,7 @@ __global__ __launch_bounds__(SV_NT) void serve_step_kernel(
             s = (hd.part + e * hid4)[c4];                 // finished activations
         }
         reinterpret_cast<float4*>(s_h)[c4] = s;
+        if (hd.hidden_out) hd.hidden_out[e * hid4 + c4] = s;
     }
     __syncthreads();                                      // ---- B: the hidden activations are out (and sF is free)
 
@@ -283,11 +286,11 @@ extern "C" int arl_env_step_served(const arl_game* game, const arl_env_state* st
     ARL_REQUIRE(hid > 0 && (hid & 3) == 0 && hid <= SV_HID_MAX, ARL_E_RANGE, "hid must be a multiple of 4, <= 1024");
     ARL_REQUIRE(h.total == st->n_env * (int64_t)hid && h.splits >= 0, ARL_E_ARG,
                 "head->hidden must describe n_env rows of hid floats");
-    ARL_REQUIRE(arl::aligned16(h.part) && (!head->hidden_bias || arl::aligned16(head->hidden_bias)), ARL_E_ALIGN,
-                "16-byte alignment");
+    ARL_REQUIRE(arl::aligned16(h.part) && (!head->hidden_bias || arl::aligned16(head->hidden_bias)) &&
+                    (!head->hidden_out || arl::aligned16(head->hidden_out)), ARL_E_ALIGN, "16-byte alignment");
     ServeHead hd = {};
     hd.part = (const float4*)h.part; hd.bias = (const float4*)head->hidden_bias;
-    hd.w_head = head->w_head; hd.b_head = head->b_head;
+    hd.w_head = head->w_head; hd.b_head = head->b_head; hd.hidden_out = (float4*)head->hidden_out;
     hd.total4 = h.total >> 2; hd.splits = h.splits; hd.hid = hid; hd.relu = head->hidden_relu;
     hd.zgn = h.splits >= arlc::fold_wide_from() ? 64 : 16;              // fold_slot (mfma_conv.hip)
     const size_t fold_lds = h.splits > 0 ? (size_t)hd.zgn * hid * 4 : 0;

@@ -122,6 +122,11 @@ class BaseOptimizer(object):
             _lib.opt_step(self._opt_state, self._update_method.kernel_id, self._learning_rate,
                           avg_factor, self._grad_norm_clip, b1, b2, eps)
         self._n_updates += 1
+        # the parameters have moved (under a capture: will move at every replay, which the replaying caller says again):
+        # whoever holds results computed under the old ones -- the rollout's stored activations -- must see it
+        note = getattr(self._target, "note_params_changed", None)
+        if note is not None:
+            note()
 
     corun_update = True             # (tests switch it off to compare with the plain one-launch update)
 

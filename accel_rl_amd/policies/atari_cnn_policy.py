@@ -37,6 +37,7 @@ import torch
 from accel_rl_amd import _lib
 from accel_rl_amd.distributions import Categorical
 from accel_rl_amd.spaces import Discrete
+from accel_rl_amd.util.misc import struct
 from accel_rl_amd.util.seed import layer_rng
 
 KIND_A2C, KIND_PPO = 0, 1
@@ -180,6 +181,7 @@ class AtariCnnPolicy(object):
         self._relu_ws = _lib.relu_bwd_workspace(self.device)
         self._folds, self._fold_workspaces = _lib.FoldList(), {}
         self._loss_ws = _lib.pg_head_workspace(self.device)
+        self._param_writes, self._stored_acts = 0, None
         self._set_from_reference_arrays(ref)
         if self.initial_param_values is not None:
             self.set_param_values(self.initial_param_values)
@@ -392,26 +394,115 @@ class AtariCnnPolicy(object):
         return (type(self).prob_value is AtariCnnPolicy.prob_value and self._n_hid >= 1 and
                 self._hid_geom[-1][0] <= 1024 and self.n_act <= _lib.MAX_ACTIONS)
 
-    def serve_conv1(self, game, b):
+    # ---- the rollout's activations, kept for the learner's first minibatch
+    # Between a rollout's forwards and the first minibatch of the update that follows it no parameter changes: that
+    # minibatch's forward recomputes rows the rollout has just computed with the same kernels.  A sampler on the served
+    # path therefore gives serve_conv1 / serve_forward one set of activation buffers PER STEP (`store`) instead of the one
+    # reused set, stamps it with the parameters' write count and offers it (offer_stored_acts); loss_and_grads then gathers
+    # its minibatch's rows from the store (one launch) instead of running the layers -- exactly those layers whose rows
+    # are the same bits at both batch sizes (_reuse_depth), the rest is computed on top as ever.
+    def note_params_changed(self):
+        """Every writer of flat_params that torch does not see (the optimisers' HIP updates: eager, captured, replayed)
+        says so here; torch's own in-place writes count themselves (flat_params._version).  Plain host integers."""
+        self._param_writes += 1
+
+    def param_stamp(self):
+        return (self._param_writes, self.flat_params._version)
+
+    def serve_store(self, horizon, b):
+        """Activation buffers of `horizon` served steps of b envs, step-major: acts[i] f32 [horizon, b, Ho, Wo, K] per
+        conv layer, hids[j] f32 [horizon, b, units] per hidden layer; None for a policy whose learner does not run this
+        class's trunk (recurrent, noisy, Q-network and residual policies keep the one reused set)."""
+        cls = type(self)
+        if not (cls._trunk is AtariCnnPolicy._trunk and cls._convs is AtariCnnPolicy._convs and
+                cls.loss_and_grads is AtariCnnPolicy.loss_and_grads and cls.serve_forward is AtariCnnPolicy.serve_forward
+                and self._n_conv + self._n_hid <= _lib.GATHER_MAX_ITEMS):
+            return None
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)     # noqa: E731
+        return struct(horizon=int(horizon), n_env=int(b),
+                      acts=[f32(horizon, b, ho, wo, nf) for nf, ci, sz, st, pad, ho, wo in self._conv_geom],
+                      hids=[f32(horizon, b, hs) for hs, fan_in in self._hid_geom],
+                      stamp=None, route=None, batch_id=-1, observations=None, owner=None)
+
+    def offer_stored_acts(self, store):
+        """The sampler's word that `store` holds the forwards of the batch it has just enqueued (None: no offer)."""
+        self._stored_acts = store
+
+    def stored_acts_for(self, observations):
+        """The store whose rows are the forward of `observations` under the parameters as they stand, or None: the
+        switch (ARL_REUSE_ACTS=0: always the full forward; A/B), the sampler's own buffer of its latest batch, no write
+        to the parameters since its forwards, the same contraction route."""
+        st = self._stored_acts
+        if st is None or os.environ.get("ARL_REUSE_ACTS", "1") == "0":
+            return None
+        if not (st.observations is observations and st.owner is not None and st.batch_id == st.owner._batch_no and
+                st.stamp == self.param_stamp() and st.route == _lib.default_route and
+                observations.shape[0] == st.horizon * st.n_env):
+            return None
+        return st
+
+    def _reuse_depth(self, store, b):
+        """How many trunk layers (conv layers first, then the hidden ones) of a b-row forward are, row for row, the bits
+        the rollout's store.n_env-row forwards left in the store.  Conv 1 is the image-stationary kernel at every size (a
+        store exists only where the step launch computes it); every later layer counts while its reduction is split the
+        same way at both sizes (_lib.conv2d_fwd_plan) -- the dense layer of spec 1 is split 24 ways at 256 rows and 12
+        ways at 512, so the PPO minibatch takes the conv layers and computes the dense layer itself.  Decided once per
+        pair of sizes and route; no tensor is compared."""
+        key = ("reuse_depth", store.n_env, b, _lib.default_route)
+        depth = self._geoms.get(key)
+        if depth is None:
+            conv_a, dense_a = self._layer_geoms(store.n_env)
+            conv_b, dense_b = self._layer_geoms(b)
+            depth = 1
+            for ga, gb in zip(conv_a[1:] + dense_a, conv_b[1:] + dense_b):
+                if _lib.conv2d_fwd_plan(ga) != _lib.conv2d_fwd_plan(gb):
+                    break
+                depth += 1
+            self._geoms[key] = depth
+        return depth
+
+    def _trunk_from_store(self, x, store, idx):
+        """_trunk for rows the rollout has already computed: the first _reuse_depth layers are gathered from the store
+        into the buffers _trunk would have filled (one launch), the layers above are computed from them."""
+        b = x.shape[0]
+        conv_g, dense_g = self._layer_geoms(b)
+        w, n_conv = self._w, self._n_conv
+        acts = [self._buffer(("act", i, b), (b, ho, wo, nf)) for i, (nf, ci, sz, st, pad, ho, wo) in enumerate(self._conv_geom)]
+        hids = [self._buffer(("hid", j, b), (b, hs)) for j, (hs, fan_in) in enumerate(self._hid_geom)]
+        depth = self._reuse_depth(store, b)
+        stored = [t.flatten(0, 1) for t in store.acts + store.hids]
+        _lib.gather_rows_many(list(zip(stored, acts + hids))[:depth], idx, step_major=(store.horizon, store.n_env))
+        for i in range(max(depth, 1), n_conv):
+            _lib.conv2d_fwd(acts[i - 1], w[2 * i], w[2 * i + 1], acts[i], conv_g[i], True, self._conv_ws)
+        for j in range(max(depth - n_conv, 0), self._n_hid):
+            k = 2 * (n_conv + j)
+            _lib.conv2d_fwd(hids[j - 1] if j > 0 else acts[-1], w[k], w[k + 1], hids[j], dense_g[j], True, self._conv_ws)
+        return acts, hids
+
+    def serve_conv1(self, game, b, store=None):
         """(_lib.ArlServeConv1, y1) for a launch that computes conv 1 of b observations itself (arl_env_step_served,
-        arl_rollout_begin_conv1), or (None, None) when this first layer / route is not one it takes."""
+        arl_rollout_begin_conv1), or (None, None) when this first layer / route is not one it takes.  store: y1 is its
+        step 0."""
         conv_g, _ = self._layer_geoms(b)
         if not (self._u8 and _lib.serve_conv1_supported(game, conv_g[0])):
             return None, None
         nf, ci, sz, st, pad, ho, wo = self._conv_geom[0]
-        y1 = self._buffer(("act", 0, b), (b, ho, wo, nf))
+        y1 = self._buffer(("act", 0, b), (b, ho, wo, nf)) if store is None else store.acts[0][0]
         conv1 = _lib.ArlServeConv1()
         conv1.geom = C.pointer(conv_g[0])
         conv1.w, conv1.bias, conv1.y = self._w[0].data_ptr(), self._w[1].data_ptr(), y1.data_ptr()
         conv1.scale, conv1.relu = self._scale, 1
         return conv1, y1
 
-    def serve_forward(self, game, observations, rows, y1=None, want_next=True):
+    def serve_forward(self, game, observations, rows, y1=None, want_next=True, store=None, step=0):
         """prob_value's trunk for arl_env_step_served: everything up to the last hidden layer, whose split partial sums
         stay unfolded (the step launch folds them, applies bias + rectifier, evaluates the heads and samples).
         y1: conv 1's output for these rows if the previous step's launch has already computed it (None: computed here).
         Returns (head, conv1, y1_next): _lib.ArlServeHead; _lib.ArlServeConv1 or None (want_next False, or a first layer
         the step launch does not take); the tensor that launch will leave the next rows' conv 1 output in (or None).
+        store, step: every layer's output goes to the store's buffers of this step (serve_store) instead of the one
+        reused set -- the next rows' conv 1 to step + 1's --, and the step launch leaves the last hidden layer there too;
+        the launches and their work are the same.
         Same kernels, same arithmetic as prob_value (atari_cnn_policy.py:63-67 of the reference)."""
         with torch.no_grad():
             b = rows.shape[0]
@@ -420,7 +511,7 @@ class AtariCnnPolicy(object):
             nf, ci, sz, st, pad, ho, wo = self._conv_geom[0]
             if y1 is None:
                 x = self._scaled(observations, rows)
-                y1 = self._buffer(("act", 0, b), (b, ho, wo, nf))
+                y1 = self._buffer(("act", 0, b), (b, ho, wo, nf)) if store is None else store.acts[0][step]
                 if isinstance(x, ObsRows):
                     _lib.conv2d_u8_fwd(x.obs, x.idx, self._scale, w[0], w[1], y1, conv_g[0], True)
                 else:
@@ -428,12 +519,12 @@ class AtariCnnPolicy(object):
             a = y1
             for i in range(1, self._n_conv):
                 nf_i, _, _, _, _, ho_i, wo_i = self._conv_geom[i]
-                z = self._buffer(("act", i, b), (b, ho_i, wo_i, nf_i))
+                z = self._buffer(("act", i, b), (b, ho_i, wo_i, nf_i)) if store is None else store.acts[i][step]
                 _lib.conv2d_fwd(a, w[2 * i], w[2 * i + 1], z, conv_g[i], True, self._conv_ws)
                 a = z
             k = 2 * self._n_conv
             for j, (hs, fan_in) in enumerate(self._hid_geom):
-                hcur = self._buffer(("hid", j, b), (b, hs))
+                hcur = self._buffer(("hid", j, b), (b, hs)) if store is None else store.hids[j][step]
                 if j + 1 < self._n_hid:
                     _lib.conv2d_fwd(a, w[k], w[k + 1], hcur, dense_g[j], True, self._conv_ws)
                 else:
@@ -444,12 +535,18 @@ class AtariCnnPolicy(object):
             head.hidden = item
             head.hidden_bias, head.hidden_relu, head.hid = w[k - 1].data_ptr(), 1, self._hid_geom[-1][0]
             head.w_head, head.b_head = w[self._k_head].data_ptr(), w[self._k_head + 1].data_ptr()
+            if store is not None and item.splits > 0:   # (not split: hcur, the store's row block, is already final)
+                head.hidden_out = hcur.data_ptr()
             conv1 = None
             if want_next and self._u8 and _lib.serve_conv1_supported(game, conv_g[0]):
-                conv1 = _lib.ArlServeConv1()            # (into the buffer this step's conv 2 has just read: stream order)
+                # (into the buffer this step's conv 2 has just read: stream order; with a store into the next step's own)
+                y1 = y1 if store is None else store.acts[0][step + 1]
+                conv1 = _lib.ArlServeConv1()
                 conv1.geom = C.pointer(conv_g[0])
                 conv1.w, conv1.bias, conv1.y = w[0].data_ptr(), w[1].data_ptr(), y1.data_ptr()
                 conv1.scale, conv1.relu = self._scale, 1
+            if store is not None:
+                store.route = _lib.default_route
             return head, conv1, (y1 if conv1 is not None else None)
 
     # ------------------------------------------------------------- training
@@ -477,7 +574,10 @@ class AtariCnnPolicy(object):
                                                       lr_mult, inv_count, tie_rule, beta_clone)
             x = self._scaled(mb["observations"], idx)
             b = x.shape[0]
-            acts, hids = self._trunk(x)
+            # (the caller's grant -- stored_acts_for -- that these rows' forward under the parameters as they stand is
+            #  in the rollout's store: gathered instead of computed; A2C's and PPO's one-pass minibatches only)
+            store = mb.get("stored_acts") if kind in (KIND_A2C, KIND_PPO) else None
+            acts, hids = self._trunk(x) if store is None else self._trunk_from_store(x, store, idx)
             g, k_head = self.grads, self._k_head
             hid = self._hid_geom[-1][0]
             dout = self._buffer(("dout", b), (b, self.n_act + 1))
@@ -546,7 +646,7 @@ class AtariCnnPolicy(object):
                        "order; max_rows_per_pass = None keeps one pass)" % (rows, limit))
         acc = self._buffer(("grad_acc",), tuple(self.flat_grads.shape))
         loss_acc = self._buffer(("loss_acc",), (4,))
-        one = dict((k, v) for k, v in mb.items() if k not in ("split_hook", "dense_w_hook"))
+        one = dict((k, v) for k, v in mb.items() if k not in ("split_hook", "dense_w_hook", "stored_acts"))
         saved, self.max_rows_per_pass = self.max_rows_per_pass, None
         try:
             for k, lo in enumerate(range(0, rows, limit)):
@@ -763,6 +863,7 @@ class AtariCnnPolicy(object):
             assert tuple(a.shape) == tuple(s), (a.shape, s)
             host[o:o + a.size] = np.ascontiguousarray(a).reshape(-1)
         self.flat_params.copy_(torch.from_numpy(host))
+        self.note_params_changed()
 
     def set_param_values(self, flat, trainable=True):
         flat = np.asarray(flat, np.float32)

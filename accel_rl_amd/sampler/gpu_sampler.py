@@ -299,9 +299,22 @@ class GpuVecSampler(BaseMbSampler):
         # copied (worker.py:108-113), so the copy stays.
         self._serve_fused = bool(self._single_write and type(self)._serve_in_step and self._game.n_stack <= 4 and
                                  hasattr(policy, "serve_forward") and policy.serve_supported())
+        self._act_store = None
         if self._serve_fused:
             with_conv1 = policy.serve_conv1(self._game, n)[0] is not None
             self._serve_fused = n <= type(self)._serve_in_step_max_envs[int(with_conv1)]
+            # The learner's first minibatch runs under the parameters these forwards ran under: with one set of
+            # activation buffers per step (allocated once; fixed addresses, so the captured batches stay valid) it takes
+            # their rows over instead of computing them again (AtariCnnPolicy.stored_acts_for).  Only where conv 1 rides
+            # in the step launch -- the one first layer whose kernel is the same at every batch size; ARL_REUSE_ACTS=0
+            # keeps the one reused set (A/B switch).
+            if (self._serve_fused and with_conv1 and hasattr(policy, "serve_store") and
+                    os.environ.get("ARL_REUSE_ACTS", "1") != "0"):
+                self._act_store = policy.serve_store(t, n)
+                if self._act_store is not None:
+                    self._act_store.owner = self
+                    logger.log("GpuVecSampler -- per-step activation buffers for the learner: {:,.1f} {}".format(
+                        *nbytes_unit(sum(a.numel() * 4 for a in self._act_store.acts + self._act_store.hids))))
         self._extra_is_step_obs = bool(self.need_extra_obs and self.mid_batch_reset and type(self)._alias_extra_obs)
         if self._extra_is_step_obs:
             self.samples_buf.extra_observations = self.envs_buf.extra_observations = self.step_obs
@@ -343,6 +356,12 @@ class GpuVecSampler(BaseMbSampler):
             else:
                 self._enqueue_batch(cur)
             cur.event.record()
+        if self._act_store is not None:
+            # (the forwards run in stream order behind whatever has been enqueued: the stamp is the parameters' write
+            #  count as of this enqueue, and every later write -- an update, set_param_values -- moves it)
+            st = self._act_store
+            st.stamp, st.batch_id, st.observations = self.policy.param_stamp(), self._batch_no, self.samples_buf.observations
+            self.policy.offer_stored_acts(st)
         older = self._last_pending if (self._last_pending is not None and self._last_pending._sampler is not None) else None
         cur.pending = self._last_pending = _LazyTrajInfos(self, cur, older)
         return self.samples_buf, cur.pending
@@ -378,7 +397,9 @@ class GpuVecSampler(BaseMbSampler):
         # observations[:, 0] = step_obs (worker.py:30-32), done_count = 0 -- and, when the steps are served in one launch
         # each, conv 1 of those rows from the same pass over them (y1: conv 1 of the step's observations, once a launch
         # has left it)
-        conv1, y1 = self.policy.serve_conv1(self._game, n) if self._serve_fused else (None, None)
+        store = self._act_store
+        served = dict() if store is None else dict(store=store)
+        conv1, y1 = self.policy.serve_conv1(self._game, n, **served) if self._serve_fused else (None, None)
         if conv1 is not None:
             _lib.rollout_begin_conv1(self._game, self._state, ro, conv1)
         else:
@@ -387,8 +408,10 @@ class GpuVecSampler(BaseMbSampler):
             if hasattr(self.policy, "set_step"):
                 self.policy.set_step(s)
             if self._serve_fused:
+                if store is not None:
+                    served["step"] = s
                 head, conv1, y1 = self.policy.serve_forward(self._game, buf.observations, self._step_rows[s], y1,
-                                                            want_next=s + 1 < t)
+                                                            want_next=s + 1 < t, **served)
                 _lib.env_step_served(self._game, self._state, ro, head, conv1, self._uniforms[s], s,
                                      self._kernel_max_path_length(), self.discount, env.max_start_noops)
                 continue

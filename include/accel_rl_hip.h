@@ -283,6 +283,39 @@ int arl_copy_bytes(void* dst, const void* src, int64_t nbytes, void* stream);
  * can name without a launch of its own (it counts the replays).  ring f32[n_slots][n], counter i32[1] on the device. */
 int arl_ring_append(const float* src, int32_t n, float* ring, int32_t n_slots, int32_t* counter, void* stream);
 
+/* Rows of up to ARL_GATHER_MAX_ITEMS arrays gathered by ONE shared index vector in ONE launch: for every item,
+ * dst row j (j = 0 .. n_rows - 1) = src row map(idx[j]) (idx NULL: map(j)).  This is how the learner's first minibatch
+ * takes over the activations the rollout's forwards have just computed under the same parameters, instead of computing
+ * them again (the reference re-evaluates the whole network on `s[idxs]`, accel_rl/optimizers/util.py:86-89).
+ *   row_map  how the sources are laid out (NULL = ARL_ROW_MAP_IDENTITY).  IDENTITY: map(r) = r.  STEP_MAJOR: the sources
+ *            were written step-major [horizon][n_env] while the rows are named env-major, r = env * horizon + t (the
+ *            batch arrays' convention above): map(r) = (r % horizon) * n_env + r / horizon.
+ *   Loads and stores are 16 bytes wide: row_bytes a positive multiple of 16, <= 2^30 (else ARL_E_RANGE), src and dst 16-byte and idx
+ *   4-byte aligned (else ARL_E_ALIGN).  Also refused, nothing launched: items NULL, a NULL src or dst, src_rows < 1
+ *   (ARL_E_ARG); n_items outside 1 .. ARL_GATHER_MAX_ITEMS, n_rows outside 1 .. 2^31 - 1, src_rows > 2^31 - 1, a kind other
+ *   than the two, STEP_MAJOR with horizon < 1, n_env < 1 or horizon * n_env > 2^31 - 1, and -- the one case in which the
+ *   host knows the indices -- idx NULL with a row outside a source: n_rows > src_rows, or STEP_MAJOR with n_rows >
+ *   horizon * n_env or horizon * n_env > src_rows (ARL_E_RANGE).  idx itself lives on the device: the kernel cannot
+ *   refuse a bad entry, so a mapped source row outside [0, src_rows) reads row 0 (as arl_conv2d_u8_fwd does with
+ *   obs_rows), never memory outside the source.  dst must not overlap any src.                                       */
+typedef struct arl_gather_item {
+    const void* src;        /* [src_rows][row_bytes] */
+    void*       dst;        /* [n_rows][row_bytes]   */
+    int64_t     row_bytes;
+    int64_t     src_rows;
+} arl_gather_item;
+#define ARL_GATHER_MAX_ITEMS 8
+#define ARL_ROW_MAP_IDENTITY   0
+#define ARL_ROW_MAP_STEP_MAJOR 1
+typedef struct arl_row_map {
+    int32_t kind;           /* ARL_ROW_MAP_* */
+    int32_t horizon;        /* STEP_MAJOR: T */
+    int32_t n_env;          /* STEP_MAJOR: N */
+    int32_t reserved;
+} arl_row_map;
+int arl_gather_rows_many(const arl_gather_item* items, int32_t n_items, const int32_t* idx_or_null, int64_t n_rows,
+                         const arl_row_map* row_map_or_null, void* stream);
+
 /* out[b] = float(obs[idx[b]]) * scale  (u8 -> f32 gather; the reference gathers
  * on device with `s[idxs]`, accel_rl/optimizers/util.py:86-89, and scales by
  * 1/255 in ScalarFixedScaleLayer, accel_rl/policies/layers.py:22-41).
@@ -567,6 +600,14 @@ int arl_fold_many(const arl_fold_item* items, int32_t n, void* stream);
  * the consumer has run.  Replaces the same Lasagne DenseLayer forward as arl_conv2d_fwd (pg_cnn.py:57-68).          */
 int arl_conv2d_fwd_parts(const float* x, const float* w, const float* bias_or_null, float* y,
                          const arl_conv_geom* geom, int32_t relu, void* workspace, arl_fold_item* item, void* stream);
+/* How arl_conv2d_fwd / _parts walk this geometry's reduction (host-side, nothing launched): *splits = the number of
+ * partial sums per output (1: not split) and *k_per_split = the reduction indices of one.  Two geometries of one layer
+ * that differ only in `batch` give every row the same bits when both numbers agree and the route is one of the
+ * bf16-split ones (ARL_CONV_ROUTE_SPLIT9 / _SPLIT6): their kernels issue the same piece products in the same k order
+ * whatever the tile shape the launch's size picks, and the fold's order depends on the split count alone.  A caller
+ * that wants to reuse rows computed at another batch size (the rollout's activations in the learner) asks here.
+ * NULL pointers, a bad geometry or route: as arl_conv2d_fwd.                                                        */
+int arl_conv2d_fwd_plan(const arl_conv_geom* geom, int32_t* splits, int32_t* k_per_split);
 
 /* ------------------------------------------------------------------------- *
  * One agent step of action serving in ONE launch
@@ -582,6 +623,9 @@ typedef struct arl_serve_head {
     int32_t hid;                /* multiple of 4, <= 1024                                                               */
     const float* w_head;        /* f32[n_actions + 1][hid], rows 0..A-1 pi, row A value (arl_pg_head_infer's layout)    */
     const float* b_head;        /* f32[n_actions + 1]                                                                   */
+    float* hidden_out;          /* f32[n_env][hid], 16-byte aligned, or NULL: where the launch leaves the last hidden
+                                 * layer as its heads read it (folded, bias and rectifier applied) -- with split partials
+                                 * that row exists nowhere else.  NULL: nothing is stored, the launch is what it was.   */
 } arl_serve_head;
 
 /* The first convolution of the NEXT observation, evaluated from LDS right after the env step has built it
