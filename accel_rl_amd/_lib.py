@@ -18,6 +18,7 @@ PROMO_NEP50, PROMO_LEGACY, PROMO_ASSOC = 0, 1, 2
 PPO_TIE_THEANO, PPO_TIE_MATH, PPO_TIE_BOTH = 0, 1, 2      # ARL_PPO_TIE_*: whose gradient min() / clip() hand on (accel_rl_hip.h)
 PPG_POLICY, PPG_AUX = 0, 1                                # ARL_PPG_*: arl_ppg_head_loss_parts' phase
 OPT_ADAM, OPT_RMSPROP = 0, 1
+VMPO_MAX_ROWS = 65536                                     # ARL_VMPO_MAX_ROWS: rows of one arl_vmpo_weights launch
 MAX_ACTIONS = 18
 REPLAY_MAX_HORIZON = 16
 RAW_H, RAW_W, OBS_H, OBS_W = 210, 160, 104, 80
@@ -246,6 +247,9 @@ _SIGNATURES = {
     "arl_qlambda_scan": (_i32, [_vp] * 4 + [_f64, _f64, _i64, _i32, _i32, _i32, _vp, _vp]),
     "arl_ppg_head_loss_parts": (_i32, [_vp] * 10 + [_i64, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _i32] +
                                 [_vp] * 8),
+    "arl_vmpo_weights": (_i32, [_vp, _vp, _i64, _vp, _f64, _vp, _vp, _vp]),
+    "arl_vmpo_head_loss_parts": (_i32, [_vp] * 10 + [_i64, _i32, _i32, _f32, _i32] + [_vp] * 8),
+    "arl_vmpo_dual_step": (_i32, [_vp] * 7 + [_f32, _i32, _f32, _f32, _f32, _f32, _vp]),
     "arl_vtrace_scan": (_i32, [_vp] * 7 + [_f64] * 5 + [_i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "arl_seq_store": (_i32, [C.POINTER(_vp), _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(_vp), _vp, _vp]),
     "arl_seq_prepare": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_vp), _i32, _i32, _vp, _vp, _vp, C.POINTER(_vp),
@@ -1035,6 +1039,21 @@ class FoldList(object):
             "arl_ppg_head_loss_parts")
         self._n += 3                # (a refused call leaves no items behind)
 
+    def vmpo_head_loss(self, h, w_head, b_head, actions, psi, returns, old_prob, idx, duals, inv_count, n_actions,
+                       v_loss_coeff, dout, dh, dw_head, db_head, loss4, workspace, stream=None, relu_mask_dh=False):
+        """V-MPO's output stage (csrc/vmpo.hip: arl_vmpo_head_loss_parts) with its three small folds left to run(), as
+        ppg_head_loss leaves them.  psi: vmpo_weights' output; duals: device (eta, alpha).  loss4 = (pi_loss, v_loss,
+        mean KL, their plain sum)."""
+        batch, hid = h.shape
+        assert self._n + 3 <= FOLD_MAX_ITEMS, "too many pending folds"
+        first = C.byref(self._items[self._n])
+        _check(load().arl_vmpo_head_loss_parts(
+            ptr(h), ptr(w_head), ptr(b_head), ptr(actions), ptr(psi), ptr(returns), ptr(old_prob), ptr(idx), ptr(duals),
+            ptr(inv_count), batch, hid, n_actions, float(v_loss_coeff), int(bool(relu_mask_dh)), ptr(dout), ptr(dh),
+            ptr(dw_head), ptr(db_head), ptr(loss4), ptr(workspace), first, stream_ptr(stream)),
+            "arl_vmpo_head_loss_parts")
+        self._n += 3                # (a refused call leaves no items behind)
+
     def ln_relu_bwd(self, dy, y, z, stats, gamma, dy_masked, dz, dgamma, dbeta, workspace, stream=None):
         """ln_relu_bwd with its two column-sum folds (dgamma, dbeta) left to run()."""
         rows, width = _ln_rows(z, gamma, (dy, y, dz), stats)
@@ -1462,6 +1481,38 @@ def vtrace_scan(prob, old_prob, actions, values, last_values, rewards, dones, di
                                   ptr(dones), float(discount), float(vtrace_lambda), float(rho_bar), float(c_bar),
                                   float(pg_rho_bar), n_env, horizon, n_actions, ptr(returns), ptr(advantages), ptr(stats),
                                   stream_ptr(stream)), "arl_vtrace_scan")
+
+
+# ---------------------------------------------------------------------------
+# V-MPO: top-half weights and the duals' step (csrc/vmpo.hip; the head's loss is FoldList.vmpo_head_loss)
+# ---------------------------------------------------------------------------
+
+def vmpo_weights(advantages, idx, duals, eps_eta, psi, temp4, stream=None):
+    """psi[rows of the minibatch] = softmax(A / eta) over the top half of its advantages, 0 on its other rows (rows
+    outside it are left alone); temp4 = (temp_loss, d temp_loss / d eta, log mean exp(A / eta), n_top).  idx None: the
+    minibatch is rows 0 .. psi.numel() - 1.  duals: device f32[2] = (eta, alpha)."""
+    for t, n in ((advantages, "advantages"), (duals, "duals"), (psi, "psi"), (temp4, "temp4")):
+        _want(t, torch.float32, n)
+    if idx is not None:
+        _want(idx, torch.int32, "idx")
+    assert psi.numel() == advantages.numel() and duals.numel() >= 2 and temp4.numel() >= 4, "psi / duals / temp4 size"
+    n = advantages.numel() if idx is None else idx.numel()
+    assert n <= advantages.numel(), "more positions than rows"
+    _check(load().arl_vmpo_weights(ptr(advantages), ptr(idx), n, ptr(duals), float(eps_eta), ptr(psi), ptr(temp4),
+                                   stream_ptr(stream)), "arl_vmpo_weights")
+
+
+def vmpo_dual_step(duals, slot0, slot1, step_count, lr_mult, temp4, loss4, eps_alpha, method, learning_rate,
+                   beta1_or_rho, beta2, epsilon, stream=None):
+    """One optimiser step on (eta, alpha) from (temp4[1], eps_alpha - loss4[2]), then max(x, 1e-8); step_count += 1."""
+    for t, n in ((duals, "duals"), (slot0, "slot0"), (step_count, "step_count"), (lr_mult, "lr_mult"), (temp4, "temp4"),
+                 (loss4, "loss4")):
+        _want(t, torch.float32, n)
+    assert duals.numel() >= 2 and slot0.numel() >= 2 and (slot1 is None or slot1.numel() >= 2), "duals / slot sizes"
+    assert temp4.numel() >= 4 and loss4.numel() >= 4, "temp4 / loss4 size"
+    _check(load().arl_vmpo_dual_step(ptr(duals), ptr(slot0), ptr(slot1), ptr(step_count), ptr(lr_mult), ptr(temp4),
+                                     ptr(loss4), float(eps_alpha), int(method), float(learning_rate), float(beta1_or_rho),
+                                     float(beta2), float(epsilon), stream_ptr(stream)), "arl_vmpo_dual_step")
 
 
 # ---------------------------------------------------------------------------

@@ -1,2 +1,3 @@
 from accel_rl_amd.algos.pg.impala import IMPALA  # noqa: F401
 from accel_rl_amd.algos.pg.ppg import PPG  # noqa: F401
+from accel_rl_amd.algos.pg.vmpo import VMPO  # noqa: F401

@@ -47,6 +47,15 @@ __device__ __forceinline__ void update_one(float& p, float g, float& s0, float& 
     }
 }
 
+// Adam's step size at Lasagne's t (update_methods_stats.py:67); rmsprop has none (its step is lr's own)
+template <int METHOD>
+__device__ __forceinline__ float opt_step_size(float lr, float b1, float b2, float t) {
+    float a_t = 0.f;
+    if (METHOD == ARL_OPT_ADAM)
+        a_t = lr * sqrtf(1.f - powf(b2, t)) / (1.f - powf(b1, t));       // :67
+    return a_t;
+}
+
 // One no-clip update of the float4 ranges [a0, a0 + an) and [b0, b0 + bn) of the flat bucket (the whole bucket: a =
 // everything, b empty; "everything but a hole": a below it, b above it; "the hole": a = the hole).  Workgroup `block`
 // of `nblocks` leaves its sum of squared gradients at norm_parts[k][block0 + block]; the launch with `finish` set
@@ -69,9 +78,7 @@ __device__ __forceinline__ void opt_update_block(const OptSeg& c, int block, int
     const arl_opt_state& o = c.o;
     const float t = c.step_pp[c.k & 1] + 1.0f;                      // update_methods_stats.py:66
     const float lr = c.lr_base * o.lr_mult[0];
-    float a_t = 0.f;
-    if (METHOD == ARL_OPT_ADAM)
-        a_t = lr * sqrtf(1.f - powf(c.b2, t)) / (1.f - powf(c.b1, t));   // :67
+    const float a_t = opt_step_size<METHOD>(lr, c.b1, c.b2, t);
     float4* p4 = reinterpret_cast<float4*>(o.params);
     const float4* g4 = reinterpret_cast<const float4*>(o.grads);
     float4* m4 = reinterpret_cast<float4*>(o.slot0);

@@ -1,6 +1,6 @@
 // The actor-critic output stage, once: policy / value heads + softmax (+ a loss and its gradients) in one pass, and the
-// host side of its launch.  learner.hip (serving, A2C / PPO) and ppg.hip (PPG's two phases) instantiate it with their
-// `Loss` types; nothing but the loss differs between them.  All fp32; compiled with -ffp-contract=off, the order of
+// host side of its launch.  learner.hip (serving, A2C / PPO), ppg.hip (PPG's two phases) and vmpo.hip (V-MPO) instantiate
+// it with their `Loss` types; nothing but the loss differs between them.  All fp32; compiled with -ffp-contract=off, the order of
 // operations is the one include/accel_rl_hip.h states.
 //
 // A Loss provides
@@ -44,6 +44,7 @@ struct HeadArgs {
     int mask_dh;             // dh *= (h > 0): h is a rectifier's output and the caller wants the gradient before it
     int head_blocks;         // workgroups of the head itself (a Loss::WT launch carries more: see head_kernel)
     int64_t wstride;         // floats between workgroups' wpart: K * hid rounded up to 4 (arl_fold_many folds float4s)
+    const float* duals;      // device (eta, alpha): V-MPO reads its KL multiplier here, it moves inside a captured graph
 };
 
 struct HeadRow { int act; float adv, ret, valid, old; };     // old: the taken action's stored probability (PPG-aux: lane k's)

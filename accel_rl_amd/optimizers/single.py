@@ -187,6 +187,58 @@ class VtraceOptimizer(PpoOptimizer):
         return losses, self._recent_grad_norms(self._n_minibatches)
 
 
+class VmpoOptimizer(PpoOptimizer):
+    """PpoOptimizer that also owns V-MPO's duals (eta, alpha): after the network's step of every minibatch, one
+    arl_vmpo_dual_step moves both on the gradients the minibatch left behind -- temp4[1] (arl_vmpo_weights, which the
+    algorithm points at `temp4`) and eps_alpha - loss4[2] (the head's mean KL) -- and projects them onto x >= 1e-8.
+    `duals`, their optimiser slots, their step count and `temp4` are allocated at initialize(), so a captured graph keeps
+    its addresses.  dual_args = dict(learning_rate, update_method, update_method_args), each defaulting to the
+    network's; the learning-rate multiplier is the network's.  minibatch_size None = the whole batch."""
+
+    def __init__(self, learning_rate, update_method, update_method_args, epochs, minibatch_size, dual_args=None,
+                 dual_init=(1.0, 5.0), eps_alpha=0.005, **kwargs):
+        super().__init__(learning_rate, update_method, update_method_args, epochs, minibatch_size, **kwargs)
+        dual = dict(dual_args or dict())
+        unknown = sorted(set(dual) - {"learning_rate", "update_method", "update_method_args"})
+        if unknown:
+            raise ValueError("dual_args: unknown keys %s (learning_rate, update_method, update_method_args)" % unknown)
+        self._dual_lr = dual.get("learning_rate", learning_rate)
+        self._dual_method = dual.get("update_method", update_method)
+        if "update_method" in dual:                 # (another rule does not inherit the network's arguments)
+            dual.setdefault("update_method_args", dict())
+        a = self._dual_method.resolve(**(dual.get("update_method_args", update_method_args) or dict()))
+        self._dual_kernel_args = (a["beta1"], a["beta2"], a["epsilon"]) if self._dual_method.name == "adam" else \
+            (a["rho"], 0.0, a["epsilon"])
+        self.dual_init = (float(dual_init[0]), float(dual_init[1]))
+        self.eps_alpha = float(eps_alpha)
+
+    def initialize(self, inputs, losses, constraints, target, givens=None, lr_mult=1):
+        super().initialize(inputs, losses, constraints, target, givens=givens, lr_mult=lr_mult)
+        dev = target.device
+        self.duals = torch.tensor(self.dual_init, dtype=torch.float32, device=dev)
+        self.temp4 = torch.zeros(4, dtype=torch.float32, device=dev)
+        self._dual_slot0 = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._dual_slot1 = torch.zeros(2, dtype=torch.float32, device=dev) if self._dual_method.name == "adam" else None
+        self._dual_step_count = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._loss4 = None
+
+    def prepare_host(self, data_length):
+        if self._minibatch_size is None:
+            self._minibatch_size = int(data_length)
+        super().prepare_host(data_length)
+
+    def _backward(self, losses, minibatch):
+        self._loss4 = losses(minibatch)             # (pi_loss, v_loss, mean KL, their sum): the dual step reads [2]
+        return self._loss4[3]
+
+    def _apply_update(self, avg_factor=1.0):
+        super()._apply_update(avg_factor)
+        b1, b2, eps = self._dual_kernel_args
+        _lib.vmpo_dual_step(self.duals, self._dual_slot0, self._dual_slot1, self._dual_step_count, self._lr_mult,
+                            self.temp4, self._loss4, self.eps_alpha, self._dual_method.kernel_id, self._dual_lr, b1, b2,
+                            eps)
+
+
 class TrajPpoOptimizer(PpoOptimizer):
     """PPO for recurrent policies: epochs x minibatches of WHOLE trajectory segments (optimizers/util.py:21-32,
     iterate_traj_idxs; the reference's own PpoOptimizer slices rows and cuts trajectories apart).  `minibatch_size`

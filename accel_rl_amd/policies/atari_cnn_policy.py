@@ -41,6 +41,7 @@ from accel_rl_amd.util.misc import struct
 from accel_rl_amd.util.seed import layer_rng
 
 KIND_A2C, KIND_PPO = 0, 1
+KIND_VMPO = 4                   # (2 / 3: PPG's two phases)
 
 
 def _glorot_uniform(shape):
@@ -551,7 +552,7 @@ class AtariCnnPolicy(object):
 
     # ------------------------------------------------------------- training
     def loss_and_grads(self, mb, kind, clip_param, v_loss_coeff, ent_loss_coeff, lr_mult,
-                       inv_count=None, tie_rule=_lib.PPO_TIE_THEANO, beta_clone=1.0):
+                       inv_count=None, tie_rule=_lib.PPO_TIE_THEANO, beta_clone=1.0, duals=None):
         """One minibatch: forward, losses (a2c.py:43-46 / ppo.py:42-51 + aac_base.py:60-66)
         and the full backward pass into `flat_grads` (overwritten, not accumulated).
         mb: observations u8[n,...], idx i32[B] or None, actions, advantages, returns,
@@ -562,16 +563,24 @@ class AtariCnnPolicy(object):
         kind 2 / 3: PPG's policy / auxiliary phase (arl_ppg_head_loss_parts, csrc/ppg.hip; no valids).  2 is PPO's loss
         with the value gradient stopped at the last hidden layer (it still trains the head's value row); 3 is
         v_loss + beta_clone * KL(old_prob || pi) on observations, returns, old_prob alone, and returns loss4 =
-        (clone, v_loss, 0, their sum)."""
+        (clone, v_loss, 0, their sum).
+        kind 4: V-MPO (arl_vmpo_head_loss_parts, csrc/vmpo.hip; no valids): -sum(psi log pi(a)) + v_loss +
+        duals[1] * mean KL(old_prob || pi) with mb["psi"] (vmpo_weights' output, normalised over the whole minibatch) and
+        `duals` the device (eta, alpha); returns loss4 = (pi_loss, v_loss, mean KL, their plain sum)."""
         if kind in (2, 3) and mb.get("valids") is not None:
             raise NotImplementedError("the PPG kinds take no valids (mid_batch_reset=False is not built for PPG)")
+        if kind == KIND_VMPO:
+            if mb.get("valids") is not None:
+                raise NotImplementedError("the V-MPO kind takes no valids (mid_batch_reset=False is not built for V-MPO)")
+            if duals is None or mb.get("psi") is None:
+                raise TypeError("the V-MPO kind needs mb['psi'] (vmpo_weights) and duals=(eta, alpha) on the device")
         with torch.no_grad():
             idx = mb.get("idx")
             rows = mb["observations"].shape[0] if idx is None else idx.shape[0]
             limit = self.rows_per_pass()
             if limit and rows >= 3 * limit:
                 return self._loss_and_grads_in_passes(mb, rows, limit, kind, clip_param, v_loss_coeff, ent_loss_coeff,
-                                                      lr_mult, inv_count, tie_rule, beta_clone)
+                                                      lr_mult, inv_count, tie_rule, beta_clone, duals)
             x = self._scaled(mb["observations"], idx)
             b = x.shape[0]
             # (the caller's grant -- stored_acts_for -- that these rows' forward under the parameters as they stand is
@@ -589,6 +598,14 @@ class AtariCnnPolicy(object):
                                           self.n_act, kind - 2, clip_param, v_loss_coeff, ent_loss_coeff, beta_clone,
                                           dout, dh, g[k_head], g[k_head + 1], loss4, self._loss_ws,
                                           relu_mask_dh=True, tie_rule=tie_rule)
+                self._backward_trunk(x, acts, hids, dh, masked=True, split_hook=mb.get("split_hook"),
+                                     dense_w_hook=mb.get("dense_w_hook"))
+                return loss4
+            if kind == KIND_VMPO:
+                self._folds.vmpo_head_loss(hids[-1], self.params[k_head], self.params[k_head + 1], mb["actions"],
+                                           mb["psi"], mb["returns"], mb["old_prob"], idx, duals, inv_count, self.n_act,
+                                           v_loss_coeff, dout, dh, g[k_head], g[k_head + 1], loss4, self._loss_ws,
+                                           relu_mask_dh=True)
                 self._backward_trunk(x, acts, hids, dh, masked=True, split_hook=mb.get("split_hook"),
                                      dense_w_hook=mb.get("dense_w_hook"))
                 return loss4
@@ -627,7 +644,7 @@ class AtariCnnPolicy(object):
         return max(256, (self.CACHE_BYTES // per_row + 128) // 256 * 256)
 
     def _loss_and_grads_in_passes(self, mb, rows, limit, kind, clip_param, v_loss_coeff, ent_loss_coeff, lr_mult,
-                                  inv_count, tie_rule=_lib.PPO_TIE_THEANO, beta_clone=1.0):
+                                  inv_count, tie_rule=_lib.PPO_TIE_THEANO, beta_clone=1.0, duals=None):
         """loss_and_grads of a minibatch larger than rows_per_pass(): passes over consecutive slices of its index list,
         every pass normalised by the WHOLE minibatch's count; gradients and the four loss sums accumulate in pass
         order (deterministic).  The co-run / split hooks of the one-pass learner do not apply (nothing is final before
@@ -652,7 +669,7 @@ class AtariCnnPolicy(object):
             for k, lo in enumerate(range(0, rows, limit)):
                 one["idx"] = idx[lo:min(lo + limit, rows)]
                 loss4 = self.loss_and_grads(one, kind, clip_param, v_loss_coeff, ent_loss_coeff, lr_mult, inv_count,
-                                            tie_rule, beta_clone)
+                                            tie_rule, beta_clone, duals)
                 if k == 0:
                     acc.copy_(self.flat_grads)
                     loss_acc.copy_(loss4)

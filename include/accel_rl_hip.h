@@ -503,6 +503,75 @@ int arl_ppg_head_loss_parts(const float* h, const float* w_head, const float* b_
                             float* dw_head, float* db_head, float* loss4, void* workspace,
                             struct arl_fold_item* items3, void* stream);
 
+/* V-MPO (single-GPU, feed-forward, synchronous variant; csrc/vmpo.hip): the policy is regressed onto the better half of
+ * a minibatch with weights softmax(A / eta), a trust region KL(old || pi) <= eps_alpha is held by a learned multiplier
+ * alpha, and the temperature eta is learned from its own dual loss.  duals is a device f32[2] = (eta, alpha); both
+ * kernels that need a dual read it on the device (the values move inside a captured graph).  TINY = 1e-8.
+ *
+ * arl_vmpo_weights: the top half of n advantages and its weights.  Position b = 0 .. n - 1 stands for row
+ *   r(b) = idx_or_null ? idx[b] : b of `advantages` and of `psi` (idx must not repeat a row); A_b = advantages[r(b)].
+ *       n_top    = (n + 1) / 2                                                          (integer division)
+ *       key(a)   = bits(a) ^ (sign bit of a ? 0xFFFFFFFF : 0x80000000)                  (uint32; orders fp32 values, +0 above -0)
+ *       selected = the n_top positions first in (key descending, b ascending)           (ties go to the lower position)
+ *   The selection is exact: an integer radix select (four passes of 8 bits, most significant first, on an LDS histogram
+ *   of integer atomics) finds the n_top-th largest key T and the number of keys equal to T that are selected; a prefix
+ *   count over the positions in ascending order hands those places to the first ties.  What follows is float64 on the
+ *   promoted fp32 inputs, eta = (double) duals[0], m = the largest advantage (always selected):
+ *       e_b = exp((A_b - m) / eta) for selected b,   S = sum_b e_b,   psi_b = e_b / S,   SA = sum_b psi_b * A_b
+ *       L   = m / eta + log(S / n_top)
+ *       psi[r(b)]  = (float) psi_b for selected b, 0.f for every other position of the minibatch
+ *       temp4      = ((float) (eta * eps_eta + eta * L), (float) ((eps_eta + L) - SA / eta), (float) L, (float) n_top)
+ *   i.e. the temperature's dual loss, its derivative with respect to eta, the log mean exp(A / eta) of the selection
+ *   and the selection's size; every output is rounded to fp32 once.  Sums over b: thread t of the one workgroup of
+ *   1 024 adds its positions t, t + 1 024, ... in ascending order, a wave adds by halving shuffles (offsets 32 .. 1),
+ *   the workgroup adds its 16 waves in wave order.  No float atomics: two launches on the same inputs give the same bits.
+ *   Elements of psi that are no row of the minibatch are not written.  advantages must be finite and eta > 0 (not
+ *   checked: the kernel reads them on the device).
+ *   Limits: 1 <= n <= ARL_VMPO_MAX_ROWS (else ARL_E_RANGE); ARL_E_ARG: a NULL advantages, duals, psi or temp4, an
+ *   eps_eta that is not finite.  A refused call launches nothing and writes nothing.
+ *
+ * arl_vmpo_head_loss_parts: arl_ppg_head_loss_parts' sibling (the same kernel source and launcher,
+ *   csrc/head_kernel_dev.h; forward, row order of the sums, fold items, workspace and relu_mask_dh exactly as stated
+ *   there).  Rows of actions / psi / returns / old_prob are selected by idx_or_null; psi is arl_vmpo_weights' output
+ *   (already normalised over the minibatch: it takes no 1 / n); old_prob f32[n_rows][A] is read whole.  With
+ *   w = inv_n, alpha = duals[1], a = actions[row], old = old_prob[row], c = alpha * w:
+ *       pi_b   = -psi_b * log(p_a + TINY)
+ *       kl_b   = sum_k old_k * (log(old_k + TINY) - log(p_k + TINY))                   (k ascending)
+ *       q_k    = old_k * p_k / (p_k + TINY),  S = sum_k q_k                            (k ascending)
+ *       g_a    = -psi_b / (p_a + TINY),  g_k = 0 elsewhere
+ *       dout[b][j] = p_j * (g_j - g_a * p_a) + c * (p_j * S - q_j), j < A      dout[b][A] = 2 * v_loss_coeff * w * (V_b - R_b)
+ *       dh[b][c] = sum_{k <= A} dout[b][k] W[k][c]                                     (k ascending: the value gradient
+ *                                                                                       reaches the trunk)
+ *   loss4 = (sum_b pi_b, sum_b (v_loss_coeff * w * (V_b - R_b)) * (V_b - R_b), sum_b w * kl_b, ([0] + [1]) + [2]): the
+ *   KL is the plain mean, NOT scaled by alpha -- the dual step reads it -- so loss4[3] is not the Lagrangian the
+ *   gradients belong to (that is [0] + [1] + alpha * [2]).  There is no entropy term, no ratio and no valids.
+ *   This entry does not write the arl_dgrad_wt weight copies.
+ *   Limits (else ARL_E_RANGE): 1 <= n_actions <= 18, 1 <= hid <= 1024, 1 <= batch <= 2^31 - 1.  ARL_E_ARG: a NULL pointer
+ *   other than idx_or_null / inv_count_or_null, a v_loss_coeff that is not finite.  A refused call launches nothing.
+ *
+ * arl_vmpo_dual_step: one optimiser step on both duals in one launch of one workgroup, then the projection.
+ *       g = (temp4[1], eps_alpha - loss4[2])                         (d temp_loss / d eta, d alpha (eps_alpha - KL) / d alpha)
+ *       t = step_count[0] + 1,  lr = learning_rate * lr_mult[0],  adam: a_t = lr sqrt(1 - beta2^t) / (1 - beta1^t)
+ *       element i: the update of arl_opt_step with avg_factor 1 and no clipping, expression for expression
+ *                  (slot0 = adam's m | rmsprop's accumulator, slot1 = adam's v; f32[2] each)
+ *       duals[i] = max(duals[i], 1e-8);  step_count[0] = t
+ *   Limits: method ARL_OPT_ADAM / ARL_OPT_RMSPROP, adam needs slot1, a finite eps_alpha, non-NULL pointers (ARL_E_ARG);
+ *   beta1, beta2 in [0, 1) (rmsprop: rho in [0, 1]), epsilon >= 0, learning_rate >= 0 (ARL_E_RANGE).               */
+#define ARL_VMPO_MAX_ROWS 65536
+int arl_vmpo_weights(const float* advantages, const int32_t* idx_or_null, int64_t n, const float* duals,
+                     double eps_eta, float* psi, float* temp4, void* stream);
+int arl_vmpo_head_loss_parts(const float* h, const float* w_head, const float* b_head,
+                             const uint8_t* actions, const float* psi, const float* returns,
+                             const float* old_prob, const int32_t* idx_or_null, const float* duals,
+                             const float* inv_count_or_null, int64_t batch, int32_t hid, int32_t n_actions,
+                             float v_loss_coeff, int32_t relu_mask_dh, float* dout, float* dh,
+                             float* dw_head, float* db_head, float* loss4, void* workspace,
+                             struct arl_fold_item* items3, void* stream);
+int arl_vmpo_dual_step(float* duals, float* slot0, float* slot1_or_null, float* step_count,
+                       const float* lr_mult, const float* temp4, const float* loss4, float eps_alpha,
+                       int32_t method, float learning_rate, float beta1_or_rho, float beta2, float epsilon,
+                       void* stream);
+
 /* ------------------------------------------------------------------------- *
  * The policy network's dense contractions on the matrix cores (fp32 MFMA)
  * ------------------------------------------------------------------------- */
