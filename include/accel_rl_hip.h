@@ -1494,6 +1494,10 @@ int arl_r2d2_loss(const float* q, const float* q_tgt, const uint8_t* actions, co
  * A row sum: per lane s = q_0, then s = s + q_v (v ascending), q_v = ((x + y) + z) + w of float4 v (0 past the row's
  * end); then the butterfly s = s + s[lane ^ off], off = LPR / 2, LPR / 4, .. 1, after which every lane of the row holds
  * the same bits.  Every element passes through at most D = 4 V + log2(LPR) additions.
+ * A block of 256 threads holds RPB = 256 / LPR row slots, slot k in its threads k * LPR .. k * LPR + LPR - 1 (a wave holds
+ * 64 / LPR consecutive slots); a slot past the last row computes on zeros and stores nothing.  The forward takes
+ * min(2048, ceil(rows / RPB)) blocks, slot k of block b walking the rows b * RPB + k + i * grid * RPB; no result of it
+ * depends on that grid.
  * Forward: writes y (a second buffer: z is KEPT, y == z is refused -- the backward pass recomputes xhat from z and
  * stats, so nothing but stats, 8 bytes per row, is stored for it beyond the activations) and stats f32[rows][2] =
  * (mean, rstd).
@@ -1503,9 +1507,10 @@ int arl_r2d2_loss(const float* q, const float* q_tgt, const uint8_t* actions, co
  *   dgamma_j = sum_rows g_j * xhat_j,  dbeta_j = sum_rows g_j
  * dy_masked = 1: dy already carries the mask (masked-out entries +0, as the data-gradient launches leave them): it is
  * taken as it comes and y is not read; the mask being idempotent, the outputs equal the dy_masked = 0 call's bit for bit.
- * The column sums: a block of 256 threads holds RPB = 256 / LPR row slots; slot k of block b adds the terms of rows
- * b * RPB + k + i * grid * RPB, i ascending, grid = min(256, ceil(rows / RPB)); the block adds its RPB slots in slot
- * order into one partial row, part f32[grid][width] for dgamma followed by the same for dbeta in `workspace`
+ * The column sums: slot k of block b adds the terms of rows b * RPB + k + i * grid * RPB (one fp32 product g_j * xhat_j
+ * per dgamma term), i ascending, to an accumulator that starts at +0, grid = min(256, ceil(rows / RPB)); the block adds
+ * its RPB slots in slot order (slot 0's accumulator, then + slot 1's, ..; a slot without a row holds +0) into one
+ * partial row, part f32[grid][width] for dgamma followed by the same for dbeta in `workspace`
  * (>= arl_ln_bwd_workspace_bytes()); arl_fold_many adds the partial rows in its fixed order -- at once (items2_or_null
  * NULL: a second launch here) or later (items2_or_null: two arl_fold_item are filled in, the workspace stays live until
  * the caller's arl_fold_many).  No atomics; bit-identical run to run.  Indexing is 64-bit.
