@@ -9,6 +9,7 @@ are float64 NumPy restatements of include/accel_rl_hip.h's statements, written f
   within_one_ulp         got == want or its float32 neighbour
   brute_sampleable       which sequence slots can be sampled, from a simulation of the ring in global time
   SeqModel               arl_seq_store / arl_seq_prepare in NumPy
+  LIMIT_SHAPES, limits_loss_case, seq_written_slots, seq_t0       the cases of tests/test_r2d2_vmpo_sacd_limits_*.py
 """
 import numpy as np
 
@@ -212,3 +213,45 @@ class SeqModel(object):
         resets = self.ring[env_rows, step_rows]
         states = [st[np.asarray(env), np.asarray(slot)] for st in self.stores]
         return env_rows, step_rows, states, resets
+
+
+# ---- the limits tests (tests/test_r2d2_vmpo_sacd_limits_gpu.py / _host.py) -------------------------------------------------
+
+# (batch, burn_in, train_len, n, A, stride, dueling): all three limits at once with the value column in the last float of
+# the row | A = 255 dueling at the tight stride | A = 255 plain | one train step behind the longest burn-in | a block
+# index above 65535
+LIMIT_SHAPES = [(2, 1024, 1024, 16, 3, 4, 1), (2, 0, 1023, 1, 255, 256, 1), (3, 5, 129, 2, 255, 256, 0),
+                (1, 1024, 1, 16, 2, 4, 0), (70000, 0, 1, 1, 1, 4, 0)]
+BIG_RETURN = np.float32(1e6)
+
+
+def limits_loss_case(seed, batch, burn_in, train_len, n, n_actions, stride, dueling, gamma_n):
+    """loss_case with two more plants.  The last train row's action byte is 255 (past the row for every A).  Sequence 0's
+    last train step -- terminal already -- gets the return 1e6, so that the largest |d| of the sequence sits at train step
+    train_len - 1 (y = h(1e6) ~ 2e3 with eps = 1e-3, 1e6 without; the next largest |d| of sequence 0 is the tie row's,
+    n_actions + 7 at most; tests/test_r2d2_vmpo_sacd_limits_host.py asserts the margin): a walk
+    of the staged errors that stops short, or a maximum that misses the last entry, shows in loss_rows and priorities.
+    Left out where that row is the z == 0 plant (batch == 1 and train_len == 1: the only |d| is the last one anyway)."""
+    c = loss_case(seed, batch, burn_in, train_len, n, n_actions, stride, dueling, gamma_n)
+    U = burn_in + train_len + n
+    c["actions"][batch * U - n - 1] = 255
+    last = burn_in + train_len - 1
+    if last != (batch - 1) * U + burn_in:
+        c["returns"][last] = BIG_RETURN
+    return c
+
+
+def seq_t0(S, idx):
+    """the first step of a batch whose ring index is a multiple of S (include/accel_rl_hip.h: ((idx + t) mod size) % S == 0;
+    size % S == 0)."""
+    t = 0
+    while (idx + t) % S:
+        t += 1
+    return t
+
+
+def seq_written_slots(size, S, horizon, idx):
+    """the set of state slots SeqModel.store writes for one environment (read off a NaN-filled store)."""
+    m = SeqModel(1, size, S, 4, 1)
+    m.store([np.ones((horizon, 4), np.float32)], np.zeros(horizon, np.uint8), horizon, idx)
+    return set(np.flatnonzero(~np.isnan(m.stores[0][0, :, 0])).tolist())

@@ -1,6 +1,7 @@
 """Shared by tests/test_sacd_host.py and tests/test_sacd_gpu.py: the input cases and the float64 NumPy restatements of
 arl_sacd_act, arl_sacd_loss and arl_sacd_alpha_grad (include/accel_rl_hip.h), per row and in the stated order, with the
-derived error bounds.
+derived error bounds.  At the end: the shapes of tests/test_r2d2_vmpo_sacd_limits_*.py and arl_sacd_alpha_grad's summation
+order restated in fp32 (alpha_grad_sum32).
 
 Bounds (EPS = 2^-24, the unit roundoff; the derivation is repeated in DESIGN.md, section 23).
 
@@ -177,3 +178,55 @@ def ref_alpha_grad(ent_rows, log_alpha, target_entropy):
     b = ent.size
     return (alpha * (ent.sum() / b - target_entropy),
             (b / 256. + 16) * EPS * alpha * (np.abs(ent).sum() / b + abs(target_entropy)))
+
+
+# ---- the limits tests (tests/test_r2d2_vmpo_sacd_limits_gpu.py / _host.py) -------------------------------------------------
+
+# (n_actions, stride, batch, shift): the action limit at the tight stride; 253 actions (three dead floats in the last
+# float4) with one row in a second workgroup -- row 256, which the shift makes an ACT_OUTSIDE row; three and five
+# workgroups with a one-row tail
+LIMIT_SHAPES = [(255, 256, 3, 0), (253, 256, 257, 2), (6, 8, 513, 0), (18, 32, 1025, 3)]
+ALPHA_GRAD_BATCHES = [1, 255, 256, 257, 65537]
+ALPHA_GRAD_TARGET = F32(0.6)
+
+
+def limit_case(shape, weighted):
+    n_act, stride, batch, shift = shape
+    return case(7000 + 10 * LIMIT_SHAPES.index(tuple(shape)) + int(weighted), n_act, stride, batch, weighted, shift=shift)
+
+
+def alpha_grad_rows(batch):
+    """entropies in [0.1, 1.6): sums of them round at nearly every addition."""
+    return (np.random.RandomState(400 + batch).rand(batch) * 1.5 + 0.1).astype(F32)
+
+
+def alpha_grad_sum32(ent_rows, drop_last_fold=False):
+    """The header's summation order in fp32: thread t adds rows t, t + 256, ... to 0 in ascending order, then
+    s[t] += s[t + h] for h = 128, 64, ... 1 -> s[0].  (Rows past the end are +0: x + 0 is x, and no partial sum is -0.)"""
+    ent = np.asarray(ent_rows, F32)
+    trips = -(-ent.size // 256)
+    grid = np.zeros(trips * 256, F32)
+    grid[:ent.size] = ent
+    s = np.zeros(256, F32)
+    for row in grid.reshape(trips, 256):
+        s = s + row
+    h = 128
+    while h > (1 if drop_last_fold else 0):
+        s[:h] = s[:h] + s[h:2 * h]
+        h //= 2
+    assert s.dtype == F32
+    return s[0]
+
+
+def alpha_grad32(ent_rows, target_entropy):
+    """arl_sacd_alpha_grad's entry 0 at log_alpha = 0 (expf(0) is exactly 1), every operation in fp32."""
+    mean = alpha_grad_sum32(ent_rows) / F32(np.asarray(ent_rows).size)
+    return F32(1) * (mean - F32(target_entropy))
+
+
+def plain_sum32(ent_rows):
+    """the rows added in ascending order in fp32: the order the kernel does NOT use."""
+    s = F32(0)
+    for v in np.asarray(ent_rows, F32):
+        s = s + v
+    return s
