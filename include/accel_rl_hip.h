@@ -1058,9 +1058,12 @@ int arl_qrdqn_loss(const float* pred, const float* tgt_next, const float* pol_ne
  * Cosine: the argument is reduced in integers.  |tau| = s 2^e (s its 24-bit significand): the angle i tau (in units of
  * pi) is i s 2^e exactly; it is taken modulo 2 and folded by cos(2 - t) = cos t, cos(1 - t) = -cos t and
  * cos(1/2 - t) = sin t to t in [0, 1/4], all on integers, then cospif(t) or sinpif(t) of the device library is taken.
- * t has at most 24 significant bits (converts exactly) whenever |tau| >= 2^-5 or tau is a drawn fraction; below that
- * it is rounded once to fp32 (relative 2^-24).  i = 0 gives exactly 1, an odd multiple of 1/2 exactly 0.  A tau_in of
- * magnitude 2^24 or more is an even integer (cos = 1); a tau_in that is not finite is not checked and also gives 1. */
+ * t is a multiple of tau's last place 2^e and at most 1/4, so it has at most 24 significant bits (converts exactly)
+ * whenever |tau| >= 2^-3 or tau is a drawn fraction (last place 2^-24); below that -- 25 bits in [2^-4, 2^-3), 26 in
+ * [2^-5, 2^-4), one more per binade -- it is rounded once to fp32 (relative 2^-24).  |tau| < 2^-14 is not folded at
+ * all (i tau < 2^-8).  The sign of tau_in is ignored (cos is even) and a subnormal tau_in is reduced like any other
+ * value.  i = 0 gives exactly 1, an odd multiple of 1/2 exactly 0.  A tau_in of magnitude 2^24 or more is an even
+ * integer (cos = 1); a tau_in that is not finite is not checked and also gives 1. */
 int arl_iqn_embed(const float* tau_in_or_null, const int64_t* state_or_null, int64_t row0, int64_t call_offset,
                   int64_t rows, int32_t r, float* tau, float* cosf, void* stream);
 
