@@ -19,6 +19,7 @@ PPO_TIE_THEANO, PPO_TIE_MATH, PPO_TIE_BOTH = 0, 1, 2      # ARL_PPO_TIE_*: whose
 PPG_POLICY, PPG_AUX = 0, 1                                # ARL_PPG_*: arl_ppg_head_loss_parts' phase
 OPT_ADAM, OPT_RMSPROP = 0, 1
 VMPO_MAX_ROWS = 65536                                     # ARL_VMPO_MAX_ROWS: rows of one arl_vmpo_weights launch
+RND_MAX_ROWS, RND_MIX_MAX_ENVS, RND_MIX_MAX_ROWS = 1 << 24, 1 << 20, 1 << 22   # ARL_RND_MAX_ROWS, ARL_RND_MIX_MAX_*
 MAX_ACTIONS = 18
 REPLAY_MAX_HORIZON = 16
 RAW_H, RAW_W, OBS_H, OBS_W = 210, 160, 104, 80
@@ -278,6 +279,11 @@ _SIGNATURES = {
     "arl_gru_cell_bwd_reset": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp,
                                       _vp, _vp, _i64, _i64, _vp]),
     "arl_rnn_cell_bwd_reset": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _vp]),
+    "arl_rnd_obs_stats_workspace_bytes": (_i64, [_i32, _i32]),
+    "arl_rnd_obs_stats": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "arl_rnd_obs_prepare": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "arl_rnd_error": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "arl_rnd_reward_mix": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _f64, _f64, _f64, _vp, _vp, _vp, _vp]),
     "arl_opt_step": (_i32, [C.POINTER(ArlOptState), _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
     "arl_opt_step_noclip": (_i32, [C.POINTER(ArlOptState), _i32, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp]),
     "arl_opt_finish": (_i32, [C.POINTER(ArlOptState), _i32, _f32, _vp, _vp, _vp]),
@@ -1513,6 +1519,80 @@ def vmpo_dual_step(duals, slot0, slot1, step_count, lr_mult, temp4, loss4, eps_a
     _check(load().arl_vmpo_dual_step(ptr(duals), ptr(slot0), ptr(slot1), ptr(step_count), ptr(lr_mult), ptr(temp4),
                                      ptr(loss4), float(eps_alpha), int(method), float(learning_rate), float(beta1_or_rho),
                                      float(beta2), float(epsilon), stream_ptr(stream)), "arl_vmpo_dual_step")
+
+
+# ---------------------------------------------------------------------------
+# RND: observation statistics, network input, prediction error, reward mix (csrc/rnd.hip)
+# ---------------------------------------------------------------------------
+
+def _rnd_frames(observations, extra_observations, n_env, horizon):
+    _want(observations, torch.uint8, "observations")
+    _want(extra_observations, torch.uint8, "extra_observations")
+    c, h, w = (int(s) for s in observations.shape[1:])
+    assert observations.shape[0] == n_env * horizon and tuple(extra_observations.shape) == (n_env, c, h, w), \
+        "observations [n_env * horizon, C, H, W] and extra_observations [n_env, C, H, W]"
+    return c, h, w
+
+
+def rnd_obs_stats_workspace(h, w, device):
+    return torch.empty(load().arl_rnd_obs_stats_workspace_bytes(h, w) // 8, dtype=torch.float64, device=device)
+
+
+def rnd_obs_stats(observations, extra_observations, n_env, horizon, count, mean, m2, workspace, stream=None):
+    """Chan-merge the per-pixel moments of the batch's next-observation frames (newest plane) into (count, mean, m2)."""
+    c, h, w = _rnd_frames(observations, extra_observations, n_env, horizon)
+    for t, n in ((count, "count"), (mean, "mean"), (m2, "m2"), (workspace, "workspace")):
+        _want(t, torch.float64, n)
+    assert count.numel() == 1 and mean.numel() == m2.numel() == h * w, "count f64[1], mean and m2 f64[H * W]"
+    assert workspace.numel() * 8 >= load().arl_rnd_obs_stats_workspace_bytes(h, w), "workspace too small"
+    _check(load().arl_rnd_obs_stats(ptr(observations), ptr(extra_observations), n_env, horizon, c, h, w, ptr(count),
+                                    ptr(mean), ptr(m2), ptr(workspace), stream_ptr(stream)), "arl_rnd_obs_stats")
+
+
+def rnd_obs_prepare(observations, extra_observations, idx, n_env, horizon, count, mean, m2, out, stream=None):
+    """out f32[B, H, W, 4]: channel 0 = the normalised, clamped next-observation frame of rows idx (None: rows 0 .. B - 1)."""
+    c, h, w = _rnd_frames(observations, extra_observations, n_env, horizon)
+    for t, n in ((count, "count"), (mean, "mean"), (m2, "m2")):
+        _want(t, torch.float64, n)
+    _want(out, torch.float32, "out")
+    if idx is not None:
+        _want(idx, torch.int32, "idx")
+    batch = out.shape[0]
+    assert count.numel() == 1 and mean.numel() == m2.numel() == h * w, "count f64[1], mean and m2 f64[H * W]"
+    assert out.numel() == batch * h * w * 4 and (idx is None or idx.numel() == batch), "out [B, H, W, 4], idx [B]"
+    _check(load().arl_rnd_obs_prepare(ptr(observations), ptr(extra_observations), ptr(idx), batch, n_env, horizon, c, h, w,
+                                      ptr(count), ptr(mean), ptr(m2), ptr(out), stream_ptr(stream)),
+           "arl_rnd_obs_prepare")
+
+
+def rnd_error(pred, targ, err, dpred=None, loss=None, stream=None):
+    """err[b] = mean_e (pred - targ)^2; with dpred and loss also its gradient for the mean over rows, and that mean."""
+    for t, n in ((pred, "pred"), (targ, "targ"), (err, "err")):
+        _want(t, torch.float32, n)
+    batch, width = pred.shape
+    assert tuple(targ.shape) == (batch, width) and err.numel() == batch, "pred, targ [B, E], err [B]"
+    want = dpred is not None
+    if want:
+        _want(dpred, torch.float32, "dpred")
+        _want(loss, torch.float32, "loss")
+        assert dpred.numel() == batch * width and loss.numel() >= 1, "dpred [B, E], loss [1]"
+    _check(load().arl_rnd_error(ptr(pred), ptr(targ), batch, width, int(want), ptr(err), ptr(dpred), ptr(loss),
+                                stream_ptr(stream)), "arl_rnd_error")
+
+
+def rnd_reward_mix(err, r_ext, n_env, horizon, rho, moments, gamma_int, c_ext, c_int, r_mix, diag2, workspace,
+                   stream=None):
+    """rho, the running moments of the discounted bonus and r_mix = c_ext r_ext + c_int err / std, in one launch."""
+    for t, n in ((err, "err"), (r_ext, "r_ext"), (r_mix, "r_mix"), (diag2, "diag2")):
+        _want(t, torch.float32, n)
+    for t, n in ((rho, "rho"), (moments, "moments"), (workspace, "workspace")):
+        _want(t, torch.float64, n)
+    rows = n_env * horizon
+    assert err.numel() == r_ext.numel() == r_mix.numel() == rows and rho.numel() == n_env and moments.numel() == 3 and \
+        diag2.numel() >= 2 and workspace.numel() >= rows, "reward_mix sizes"
+    _check(load().arl_rnd_reward_mix(ptr(err), ptr(r_ext), n_env, horizon, ptr(rho), ptr(moments), float(gamma_int),
+                                     float(c_ext), float(c_int), ptr(r_mix), ptr(diag2), ptr(workspace),
+                                     stream_ptr(stream)), "arl_rnd_reward_mix")
 
 
 # ---------------------------------------------------------------------------

@@ -572,6 +572,86 @@ int arl_vmpo_dual_step(float* duals, float* slot0, float* slot1_or_null, float* 
                        int32_t method, float learning_rate, float beta1_or_rho, float beta2, float epsilon,
                        void* stream);
 
+/* Random network distillation (RND; csrc/rnd.hip): the stages the exploration bonus adds around its two conv trunks
+ * (which run on the contraction entry points below).  One value head, one reward stream.  float64 on the promoted
+ * inputs, every output rounded once, no float atomics, no process-wide state; every shape is an argument, nothing
+ * synchronises with the host.  A refused call launches nothing and writes nothing.
+ *
+ * The frame RND sees for transition (n, t) of an env-major rollout -- observations u8[n_env * horizon][C][H][W],
+ * extra_observations u8[n_env][C][H][W], planes stacked oldest -> newest -- is the NEWEST plane of the NEXT observation:
+ *       F(n, t) = observations[n * horizon + t + 1][C - 1]   if t + 1 < horizon,   else extra_observations[n][C - 1]
+ * read in place (no copy is made).  Row r of the batch is (n, t) = (r / horizon, r % horizon).
+ * Frame arguments, checked by arl_rnd_obs_stats and arl_rnd_obs_prepare: NULL observations / extra_observations
+ * (ARL_E_ARG); n_env < 1, horizon outside 1 .. ARL_RND_MAX_HORIZON, n_env * horizon > ARL_RND_MAX_ROWS, channels outside
+ * 1 .. 1024, h or w < 1, h * w > ARL_RND_MAX_PIXELS (ARL_E_RANGE).
+ *
+ * Chan's merge, as both running-moment entry points apply it to a state (na, mean, m2) and a batch (nb, mean_b, m2_b):
+ *       w = nb / (na + nb);  delta = mean_b - mean;  mean' = mean + delta * w;
+ *       m2' = (m2 + m2_b) + ((delta * delta) * na) * w;  count' = na + nb            (start from count = 0, mean = m2 = 0)
+ *
+ * arl_rnd_obs_stats: per pixel p, over the R = n_env * horizon frames of the batch,
+ *       Sx = sum F[p], Sxx = sum F[p]^2 as uint64 integers -- exact, so neither the split of the rows across workgroups
+ *       (ARL_RND_STATS_SPLITS of them: split z takes rows z, z + splits, ...) nor the order of the additions shows;
+ *       mean_b = (double) Sx / R;   m2_b = (double) (R * Sxx - Sx * Sx) / R   (the numerator in uint64: R <= 2^24 keeps
+ *       R * Sxx <= 2^48 * 65025 < 2^64 -- that is ARL_RND_MAX_ROWS -- and it is >= 0; a constant pixel gives exactly 0),
+ *       then Chan's merge into (count[0], mean[p], m2[p]) with nb = R; count[0] is written once.
+ *   count f64[1], mean and m2 f64[h * w], workspace >= arl_rnd_obs_stats_workspace_bytes(h, w) bytes (0 for sizes the
+ *   entry point refuses), all 8-byte aligned (ARL_E_ALIGN); a NULL one: ARL_E_ARG.  Two launches.
+ *
+ * arl_rnd_obs_prepare: out f32[batch][h][w][4] (NHWC, 16-byte aligned), row b from batch row r = idx_or_null ? idx[b] : b:
+ *       sd_p = sqrt(m2[p] / count[0] + 1e-8);   z = ((double) F(r)[p] - mean[p]) / sd_p;   z = max(z, -5), then min(z, 5)
+ *       out[b][p] = ((float) z, 0, 0, 0)
+ *   i.e. the four-channel padding the contraction kernels want for a one-plane input.  count[0] must be > 0 (it lives on
+ *   the device and is not checked); idx values are not checked either.  1 <= batch <= ARL_RND_MAX_ROWS, and without idx
+ *   batch <= n_env * horizon (ARL_E_RANGE); out not 16-byte, idx not 4-byte, count / mean / m2 not 8-byte aligned:
+ *   ARL_E_ALIGN; a NULL count, mean, m2 or out: ARL_E_ARG.
+ *
+ * arl_rnd_error: pred, targ f32[batch][width].  One wave per row.  With d_e = (double) pred[b][e] - (double) targ[b][e]:
+ *       lane l adds d_e * d_e over e = 4 (l + 64 k) + (0, 1, 2, 3), k = 0, 1, ... in that order; the wave adds its 64
+ *       lanes by halving shuffles (offsets 32 .. 1);   err[b] = (float) (S / width)
+ *   and with want_grad:
+ *       dpred[b][e] = (float) ((2 * d_e) / ((double) width * (double) batch))
+ *       loss[0]     = (float) (T / batch),  T = sum_b (double) err[b]: thread t of ONE workgroup of 1 024 adds b = t,
+ *                     t + 1 024, ... in ascending order, a wave adds by halving shuffles, the 16 waves add in wave order
+ *   (a second launch).  Without want_grad dpred and loss are not touched and may be NULL.
+ *   width a multiple of 4 in 4 .. ARL_RND_MAX_WIDTH, 1 <= batch <= ARL_RND_MAX_ROWS (ARL_E_RANGE); pred, targ, dpred not
+ *   16-byte, err, loss not 4-byte aligned (ARL_E_ALIGN); a NULL pred, targ, err, or dpred / loss with want_grad: ARL_E_ARG.
+ *
+ * arl_rnd_reward_mix: err, r_ext f32[n_env][horizon]; rho f64[n_env] and moments f64[3] = (count, mean, m2) are carried
+ *   across calls (start from zeros).  One workgroup of 1 024, in this order:
+ *       1. per env n, t ascending:  rho[n] = gamma_int * rho[n] + (double) err[n][t];  v[n][t] = rho[n]   (dones ignored:
+ *          the bonus stream is not episodic)
+ *       2. batch moments of the M = n_env * horizon values v_j, j = n * horizon + t:  mean_b = (sum_j v_j) / M,
+ *          m2_b = sum_j (v_j - mean_b)^2; every sum: thread t adds j = t, t + 1 024, ... ascending, then as loss[0] above
+ *       3. Chan's merge of (M, mean_b, m2_b) into moments -- BEFORE this batch is normalised
+ *       4. sd = sqrt(m2 / count + 1e-8);  a = c_ext * (double) r_ext[j];  b = c_int * ((double) err[j] / sd);
+ *          r_mix[j] = (float) (b == 0 ? a : a + b)        (so c_ext = 1, c_int = 0 and finite err return r_ext's bits)
+ *       diag2 = ((float) ((sum_j (double) err[j]) / M), (float) sd)
+ *   workspace: f64[n_env * horizon], 8-byte aligned like rho and moments; float pointers 4-byte (ARL_E_ALIGN).
+ *   A single workgroup walks everything: n_env <= ARL_RND_MIX_MAX_ENVS (2^20), horizon <= ARL_RND_MAX_HORIZON, n_env *
+ *   horizon <= ARL_RND_MIX_MAX_ROWS (2^22: 4 096 values per thread, 16 MiB of err -- past that the launch is no longer
+ *   the few-KB-to-MB latency case it is written for) (ARL_E_RANGE).  ARL_E_ARG: a NULL pointer, gamma_int outside
+ *   [0, 1] or not finite, c_ext or c_int not finite, r_mix equal to err or r_ext.                                     */
+#define ARL_RND_MAX_ROWS     16777216
+#define ARL_RND_MAX_PIXELS   16777216
+#define ARL_RND_MAX_HORIZON  4096
+#define ARL_RND_MAX_WIDTH    65536
+#define ARL_RND_STATS_SPLITS 32
+#define ARL_RND_MIX_MAX_ENVS 1048576
+#define ARL_RND_MIX_MAX_ROWS 4194304
+int64_t arl_rnd_obs_stats_workspace_bytes(int32_t h, int32_t w);
+int arl_rnd_obs_stats(const uint8_t* observations, const uint8_t* extra_observations, int64_t n_env, int32_t horizon,
+                      int32_t channels, int32_t h, int32_t w, double* count, double* mean, double* m2, void* workspace,
+                      void* stream);
+int arl_rnd_obs_prepare(const uint8_t* observations, const uint8_t* extra_observations, const int32_t* idx_or_null,
+                        int64_t batch, int64_t n_env, int32_t horizon, int32_t channels, int32_t h, int32_t w,
+                        const double* count, const double* mean, const double* m2, float* out, void* stream);
+int arl_rnd_error(const float* pred, const float* targ, int64_t batch, int32_t width, int32_t want_grad, float* err,
+                  float* dpred, float* loss, void* stream);
+int arl_rnd_reward_mix(const float* err, const float* r_ext, int64_t n_env, int32_t horizon, double* rho, double* moments,
+                       double gamma_int, double c_ext, double c_int, float* r_mix, float* diag2, void* workspace,
+                       void* stream);
+
 /* ------------------------------------------------------------------------- *
  * The policy network's dense contractions on the matrix cores (fp32 MFMA)
  * ------------------------------------------------------------------------- */
