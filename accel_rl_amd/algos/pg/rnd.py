@@ -39,20 +39,14 @@ class PredictorOptimizer(BaseOptimizer):
     a captured graph keeps its addresses."""
 
     def __init__(self, learning_rate, update_method, update_method_args=None):
-        self._learning_rate = learning_rate
-        self._update_method = update_method
-        self._update_args = update_method.resolve(**(update_method_args or dict()))
-        self._grad_norm_clip = 0.           # arl_opt_step: clip <= 0 is "no clip"
+        self._set_update_rule(learning_rate, update_method, update_method_args,
+                              grad_norm_clip=0.)        # arl_opt_step: clip <= 0 is "no clip"
 
     def initialize(self, target, lr_mult):
         self._setup_bucket(target, lr_mult)
 
     def step(self):
         self._apply_update(1.0)
-
-    @property
-    def parallelism_tag(self):
-        return "single"
 
 
 class RndMixin(object):

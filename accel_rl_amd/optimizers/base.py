@@ -42,7 +42,25 @@ def iterate_traj_idxs(batch_size, data_length, horizon=1, shuffle=False):
         yield rows[chosen].reshape(-1), chosen
 
 
+def kernel_args(method, resolved):
+    """(beta1 or rho, beta2, epsilon) as arl_opt_step takes them, from `method.resolve(...)`'s dict."""
+    if method.name == "adam":
+        return resolved["beta1"], resolved["beta2"], resolved["epsilon"]
+    return resolved["rho"], 0.0, resolved["epsilon"]
+
+
+def sub_args(given, defaults, error, message):
+    """`defaults` overridden by `given` (a dict or None): the argument dict of a second update rule inside an optimizer
+    (V-MPO's duals, FQF's fraction layer, SAC's temperature).  A key that `defaults` does not have is refused with
+    `error(message % sorted unknown keys)`."""
+    unknown = sorted(set(given or ()) - set(defaults))
+    if unknown:
+        raise error(message % unknown)
+    return dict(defaults, **(given or dict()))
+
+
 class BaseOptimizer(object):
+    """The single-GPU answers are the defaults: nothing to share, no averaging (optimizers/sync.py overrides all three)."""
 
     def initialize(self, inputs, losses, constraints, target, givens=None, lr_mult=1):
         raise NotImplementedError
@@ -52,41 +70,62 @@ class BaseOptimizer(object):
 
     @property
     def parallelism_tag(self):
-        raise NotImplementedError
+        return "single"
+
+    def _share_grad(self):
+        pass
+
+    def _avg_factor(self):
+        return 1.0
+
+    def _set_update_rule(self, learning_rate, update_method, update_method_args, grad_norm_clip):
+        """The constructor arguments every optimizer takes (unknown update_method_args: TypeError, here)."""
+        self._learning_rate = learning_rate
+        self._update_method = update_method
+        self._update_args = update_method.resolve(**(update_method_args or dict()))
+        self._grad_norm_clip = grad_norm_clip
 
     # ---- shared: flat bucket + HIP update ------------------------------------
+    @staticmethod
+    def _new_state(n, params, grads, method, lr_mult, norm_log_len, first=0, slot_len=None):
+        """An ArlOptState over entries [first, first + n) of the fp32 tensors params / grads for `method`, with fresh
+        slots (slot1: adam only) of `slot_len` entries (default n), step count, partials and a norm log of
+        `norm_log_len` entries.  The state holds what it points at in `.tensors`, lr_mult included."""
+        dev = params.device
+        slot_len = n if slot_len is None else slot_len
+        keep = dict(slot0=torch.zeros(slot_len, dtype=torch.float32, device=dev),
+                    slot1=torch.zeros(slot_len, dtype=torch.float32, device=dev) if method.name == "adam" else None,
+                    step_count=torch.zeros(1, dtype=torch.float32, device=dev),
+                    partials=torch.zeros(_lib.OPT_PARTIALS, dtype=torch.float64, device=dev),
+                    norm_log=torch.zeros(norm_log_len, dtype=torch.float32, device=dev),
+                    lr_mult=lr_mult, params=params, grads=grads)
+        st = _lib.ArlOptState()
+        st.n_params = n
+        st.params, st.grads = params.data_ptr() + 4 * first, grads.data_ptr() + 4 * first
+        st.slot0 = keep["slot0"].data_ptr()
+        st.slot1 = keep["slot1"].data_ptr() if keep["slot1"] is not None else None
+        st.step_count, st.lr_mult = keep["step_count"].data_ptr(), lr_mult.data_ptr()
+        st.partials, st.grad_norm_log = keep["partials"].data_ptr(), keep["norm_log"].data_ptr()
+        st.norm_log_len = norm_log_len
+        st.tensors = keep
+        return st
+
     def _setup_bucket(self, target, lr_mult, givens=None):
         self._target = target
-        dev = target.device
-        n = target.flat_params.numel()
-        self._slot0 = torch.zeros(n, dtype=torch.float32, device=dev)
-        self._slot1 = torch.zeros(n, dtype=torch.float32, device=dev) \
-            if self._update_method.name == "adam" else None
-        self._step_count = torch.zeros(1, dtype=torch.float32, device=dev)
         if not isinstance(lr_mult, torch.Tensor):
-            lr_mult = torch.full((1,), float(lr_mult), dtype=torch.float32, device=dev)
+            lr_mult = torch.full((1,), float(lr_mult), dtype=torch.float32, device=target.device)
         self._lr_mult = lr_mult
-        self._partials = torch.zeros(_lib.OPT_PARTIALS, dtype=torch.float64, device=dev)
-        self._norm_log = torch.zeros(NORM_LOG_LEN, dtype=torch.float32, device=dev)
+        st = self._new_state(target.flat_params.numel(), target.flat_params, target.flat_grads, self._update_method,
+                             lr_mult, NORM_LOG_LEN)
+        self._opt_state = st
+        self._slot0, self._slot1, self._step_count = st.tensors["slot0"], st.tensors["slot1"], st.tensors["step_count"]
+        self._norm_log = st.tensors["norm_log"]
+        self._kernel_args = kernel_args(self._update_method, self._update_args)
         self._n_updates = 0
         self._step_pp = self._norm_parts = None      # the no-clip update's state (see _apply_update)
         self._hole = None                            # (first, count): range whose update this backward pass handed out
         self._call_hole = None                       # ... as fixed by the call's first update
         self._hole_count = 0                         # ... its length (0: plain updates)
-        st = _lib.ArlOptState()
-        st.n_params = n
-        st.params, st.grads = target.flat_params.data_ptr(), target.flat_grads.data_ptr()
-        st.slot0 = self._slot0.data_ptr()
-        st.slot1 = self._slot1.data_ptr() if self._slot1 is not None else None
-        st.step_count, st.lr_mult = self._step_count.data_ptr(), self._lr_mult.data_ptr()
-        st.partials, st.grad_norm_log = self._partials.data_ptr(), self._norm_log.data_ptr()
-        st.norm_log_len = NORM_LOG_LEN
-        self._opt_state = st
-        a = self._update_args
-        if self._update_method.name == "adam":
-            self._kernel_args = (a["beta1"], a["beta2"], a["epsilon"])
-        else:
-            self._kernel_args = (a["rho"], 0.0, a["epsilon"])
 
     def _backward(self, losses, minibatch):
         """Gradient of the summed loss into the flat gradient bucket (overwritten); returns the summed loss."""

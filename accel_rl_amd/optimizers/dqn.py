@@ -5,7 +5,8 @@ the gradient in the policy's flat bucket (the algorithm builds it)."""
 import numpy as np
 import torch
 
-from accel_rl_amd.optimizers.base import BaseOptimizer
+from accel_rl_amd import _lib
+from accel_rl_amd.optimizers.base import BaseOptimizer, kernel_args, sub_args
 from accel_rl_amd.util.misc import capture_graph
 
 
@@ -17,10 +18,7 @@ class DqnOptimizer(BaseOptimizer):
     def __init__(self, learning_rate, update_method, update_method_args=None, grad_norm_clip=None,
                  scale_conv_grads=False, use_graph=True):
         self._scale_conv_grads = scale_conv_grads      # dueling networks: conv gradients x 2^-1/2 (:34-36)
-        self._learning_rate = learning_rate
-        self._update_method = update_method
-        self._update_args = update_method.resolve(**(update_method_args or dict()))
-        self._grad_norm_clip = grad_norm_clip
+        self._set_update_rule(learning_rate, update_method, update_method_args, grad_norm_clip)
         self._use_graph = use_graph
         self._static = self._graph = self._graph_out = None
         self._ring, self._pack_rows = None, 0
@@ -71,7 +69,6 @@ class DqnOptimizer(BaseOptimizer):
             if capturing and packed and self._ring is not None and self._ring.shape[1] == 2 * b:
                 # inside the graph the statistics of an update are ONE ring append of both rows (the loss's sum and the
                 # downsampled priorities are taken from the ring after the update loop: algos/dqn/dqn.py)
-                from accel_rl_amd import _lib
                 _lib.ring_append(torch.as_strided(loss, (2 * b,), (1,)), self._ring, self._ring_count)
             else:
                 loss = loss.sum()
@@ -118,10 +115,6 @@ class DqnOptimizer(BaseOptimizer):
             self._stage_event.record(torch.cuda.current_stream(dev))
         return tuple(self._static)
 
-    @property
-    def parallelism_tag(self):
-        return "single"
-
 
 class FqfOptimizer(DqnOptimizer):
     """DqnOptimizer for a policy whose flat bucket ends in a fraction-proposal layer (AtariFqfPolicy.frac_offset): the
@@ -135,11 +128,8 @@ class FqfOptimizer(DqnOptimizer):
         super().__init__(learning_rate, update_method, update_method_args=update_method_args,
                          grad_norm_clip=grad_norm_clip, scale_conv_grads=scale_conv_grads, use_graph=use_graph)
         from accel_rl_amd.optimizers import update_methods
-        frac = dict(learning_rate=2.5e-9, update_method=update_methods.rmsprop, update_method_args=None)
-        unknown = set(fraction_args or ()) - set(frac)
-        if unknown:
-            raise TypeError("unexpected fraction_args: %s" % sorted(unknown))
-        frac.update(fraction_args or dict())
+        frac = sub_args(fraction_args, dict(learning_rate=2.5e-9, update_method=update_methods.rmsprop,
+                                            update_method_args=None), TypeError, "unexpected fraction_args: %s")
         self._frac_learning_rate, self._frac_method = frac["learning_rate"], frac["update_method"]
         args = frac["update_method_args"]
         if args is None:
@@ -147,7 +137,6 @@ class FqfOptimizer(DqnOptimizer):
         self._frac_args = self._frac_method.resolve(**args)
 
     def _setup_bucket(self, target, lr_mult, givens=None):
-        from accel_rl_amd import _lib
         off = getattr(target, "frac_offset", None)
         if off is None:
             raise TypeError("FqfOptimizer updates a policy with a fraction layer (AtariFqfPolicy), got %s" %
@@ -157,39 +146,17 @@ class FqfOptimizer(DqnOptimizer):
         assert 0 < off and off % 4 == 0 and n > 0
         self._frac_offset = off
         self._opt_state.n_params = off                  # the main range: everything before the fraction layer
-        dev = target.device
-        self._frac_slot0 = torch.zeros(n, dtype=torch.float32, device=dev)
-        self._frac_slot1 = torch.zeros(n, dtype=torch.float32, device=dev) if self._frac_method.name == "adam" else None
-        self._frac_step_count = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._frac_partials = torch.zeros(_lib.OPT_PARTIALS, dtype=torch.float64, device=dev)
-        self._frac_norm_log = torch.zeros(self._norm_log.numel(), dtype=torch.float32, device=dev)
-        st = _lib.ArlOptState()
-        st.n_params = n
-        st.params, st.grads = target.flat_params.data_ptr() + 4 * off, target.flat_grads.data_ptr() + 4 * off
-        st.slot0 = self._frac_slot0.data_ptr()
-        st.slot1 = self._frac_slot1.data_ptr() if self._frac_slot1 is not None else None
-        st.step_count, st.lr_mult = self._frac_step_count.data_ptr(), self._lr_mult.data_ptr()
-        st.partials, st.grad_norm_log = self._frac_partials.data_ptr(), self._frac_norm_log.data_ptr()
-        st.norm_log_len = 1                             # one update per call (_set_updates_per_call(1))
+        # (norm log of 1: one update per call, _set_updates_per_call(1))
+        st = self._new_state(n, target.flat_params, target.flat_grads, self._frac_method, self._lr_mult, 1, first=off)
         self._frac_state = st
-        a = self._frac_args
-        if self._frac_method.name == "adam":
-            self._frac_kernel_args = (a["beta1"], a["beta2"], a["epsilon"])
-        else:
-            self._frac_kernel_args = (a["rho"], 0.0, a["epsilon"])
+        self._frac_slot0, self._frac_slot1, self._frac_step_count = \
+            st.tensors["slot0"], st.tensors["slot1"], st.tensors["step_count"]
+        self._frac_kernel_args = kernel_args(self._frac_method, self._frac_args)
 
     def _apply_update(self, avg_factor=1.0):
-        from accel_rl_amd import _lib
         super()._apply_update(avg_factor)
         b1, b2, eps = self._frac_kernel_args
         _lib.opt_step(self._frac_state, self._frac_method.kernel_id, self._frac_learning_rate, avg_factor, 0.0, b1, b2, eps)
-
-
-def _method_kernel_args(method, resolved):
-    """(beta1 or rho, beta2, epsilon) as arl_opt_step takes them."""
-    if method.name == "adam":
-        return resolved["beta1"], resolved["beta2"], resolved["epsilon"]
-    return resolved["rho"], 0.0, resolved["epsilon"]
 
 
 class SacOptimizer(DqnOptimizer):
@@ -207,35 +174,13 @@ class SacOptimizer(DqnOptimizer):
             raise NotImplementedError("scale_conv_grads belongs to dueling networks, which SAC-Discrete does not build")
         super().__init__(learning_rate, update_method, update_method_args=update_method_args,
                          grad_norm_clip=grad_norm_clip, scale_conv_grads=False, use_graph=use_graph)
-        alpha = dict(learning_rate=learning_rate, update_method=update_method, update_method_args=None)
-        unknown = set(alpha_args or ()) - set(alpha)
-        if unknown:
-            raise TypeError("unexpected alpha_args: %s" % sorted(unknown))
-        alpha.update(alpha_args or dict())
+        alpha = sub_args(alpha_args, dict(learning_rate=learning_rate, update_method=update_method,
+                                          update_method_args=None), TypeError, "unexpected alpha_args: %s")
         self._alpha_learning_rate, self._alpha_method = alpha["learning_rate"], alpha["update_method"]
         args = alpha["update_method_args"]
         if args is None:                    # the networks' arguments where the method is theirs, else the method's defaults
             args = (update_method_args or dict()) if self._alpha_method is update_method else dict()
-        self._alpha_kernel_args = _method_kernel_args(self._alpha_method, self._alpha_method.resolve(**args))
-
-    def _range_state(self, n, params, grads, method):
-        """A fresh ArlOptState (and the tensors it points to) over `n` entries of params / grads."""
-        from accel_rl_amd import _lib
-        dev = params.device
-        keep = dict(slot0=torch.zeros(max(n, 4), dtype=torch.float32, device=dev),
-                    slot1=torch.zeros(max(n, 4), dtype=torch.float32, device=dev) if method.name == "adam" else None,
-                    step_count=torch.zeros(1, dtype=torch.float32, device=dev),
-                    partials=torch.zeros(_lib.OPT_PARTIALS, dtype=torch.float64, device=dev),
-                    norm_log=torch.zeros(1, dtype=torch.float32, device=dev))
-        st = _lib.ArlOptState()
-        st.n_params = n
-        st.params, st.grads = params.data_ptr(), grads.data_ptr()
-        st.slot0 = keep["slot0"].data_ptr()
-        st.slot1 = keep["slot1"].data_ptr() if keep["slot1"] is not None else None
-        st.step_count, st.lr_mult = keep["step_count"].data_ptr(), self._lr_mult.data_ptr()
-        st.partials, st.grad_norm_log = keep["partials"].data_ptr(), keep["norm_log"].data_ptr()
-        st.norm_log_len = 1                             # one update per call (_set_updates_per_call(1))
-        return st, keep
+        self._alpha_kernel_args = kernel_args(self._alpha_method, self._alpha_method.resolve(**args))
 
     def _setup_bucket(self, target, lr_mult, givens=None):
         from accel_rl_amd.policies.dqn.atari_sac_discrete_policy import AtariSacDiscretePolicy
@@ -243,19 +188,21 @@ class SacOptimizer(DqnOptimizer):
             raise TypeError("SacOptimizer updates an AtariSacDiscretePolicy (actor, two critics, log_alpha), got %s" %
                             type(target).__name__)
         super()._setup_bucket(target, lr_mult, givens)  # the actor: DqnOptimizer's own state
-        self._ranges = [(self._opt_state, None)]
+        # (norm logs of 1: one update per call, _set_updates_per_call(1); slots of at least 4 entries)
+        self._ranges = [self._opt_state]
         for critic in (target.q1, target.q2):
-            self._ranges.append(self._range_state(critic.flat_params.numel(), critic.flat_params, critic.flat_grads,
-                                                  self._update_method))
-        self._alpha_range = self._range_state(1, target.log_alpha, target.log_alpha_grad, self._alpha_method)
+            n = critic.flat_params.numel()
+            self._ranges.append(self._new_state(n, critic.flat_params, critic.flat_grads, self._update_method,
+                                                self._lr_mult, 1, slot_len=max(n, 4)))
+        self._alpha_state = self._new_state(1, target.log_alpha, target.log_alpha_grad, self._alpha_method,
+                                            self._lr_mult, 1, slot_len=4)
 
     def _apply_update(self, avg_factor=1.0):
-        from accel_rl_amd import _lib
         b1, b2, eps = self._kernel_args
-        for st, _ in self._ranges:
+        for st in self._ranges:
             _lib.opt_step(st, self._update_method.kernel_id, self._learning_rate, avg_factor, self._grad_norm_clip,
                           b1, b2, eps)
         b1, b2, eps = self._alpha_kernel_args
-        _lib.opt_step(self._alpha_range[0], self._alpha_method.kernel_id, self._alpha_learning_rate, avg_factor, 0.0,
+        _lib.opt_step(self._alpha_state, self._alpha_method.kernel_id, self._alpha_learning_rate, avg_factor, 0.0,
                       b1, b2, eps)
         self._n_updates += 1

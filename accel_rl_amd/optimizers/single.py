@@ -5,17 +5,14 @@ import torch
 
 from accel_rl_amd import _lib
 
-from accel_rl_amd.optimizers.base import BaseOptimizer, iterate_mb_idxs, iterate_traj_idxs
+from accel_rl_amd.optimizers.base import BaseOptimizer, iterate_mb_idxs, iterate_traj_idxs, kernel_args, sub_args
 
 
 class A2cOptimizer(BaseOptimizer):
     """One gradient step on the whole batch."""
 
     def __init__(self, learning_rate, update_method, update_method_args=None, grad_norm_clip=None):
-        self._learning_rate = learning_rate
-        self._update_method = update_method
-        self._update_args = update_method.resolve(**(update_method_args or dict()))
-        self._grad_norm_clip = grad_norm_clip
+        self._set_update_rule(learning_rate, update_method, update_method_args, grad_norm_clip)
 
     def initialize(self, inputs, losses, constraints, target, givens=None, lr_mult=1):
         self._input_names = list(inputs)
@@ -37,31 +34,24 @@ class A2cOptimizer(BaseOptimizer):
         self._apply_update(self._avg_factor())
         return loss, self._recent_grad_norms(1)
 
-    def _share_grad(self):
-        pass
-
-    def _avg_factor(self):
-        return 1.0
-
-    @property
-    def parallelism_tag(self):
-        return "single"
-
 
 class PpoOptimizer(BaseOptimizer):
     """epochs x minibatches over a batch that stays resident in HBM; minibatch rows
     are selected by host-shuffled index vectors (np.random.shuffle, one
-    permutation per epoch, tail dropped -- optimizers/util.py:8-18)."""
+    permutation per epoch, tail dropped -- optimizers/util.py:8-18).
+
+    The minibatch loop (`_minibatches`) is the only one: a subclass says where a minibatch's rows come from
+    (`_epoch_minibatches`, `_minibatch`), what runs before a minibatch (`_before_minibatch`), whether the co-run hook is
+    offered (`corun_update`) and whether minibatch_size None means the whole batch (`_none_is_whole_batch`)."""
+
+    _none_is_whole_batch = False        # (plain PPO: minibatch_size is required)
 
     def __init__(self, learning_rate, update_method, update_method_args, epochs, minibatch_size,
                  grad_norm_clip=None, shuffle=True, num_slices=1):
-        self._learning_rate = learning_rate
-        self._update_method = update_method
-        self._update_args = update_method.resolve(**(update_method_args or dict()))
+        self._set_update_rule(learning_rate, update_method, update_method_args, grad_norm_clip)
         self._epochs = epochs
         self._minibatch_size = minibatch_size
         self._shuffle = shuffle
-        self._grad_norm_clip = grad_norm_clip
 
     def initialize(self, inputs, losses, constraints, target, givens=None, lr_mult=1):
         self._input_names = list(inputs)
@@ -76,41 +66,61 @@ class PpoOptimizer(BaseOptimizer):
     # Split for hipGraph capture: everything that draws from the host RNG happens in
     # prepare_host(); device_updates() only enqueues static-shape device work.
     def prepare_host(self, data_length):
-        """Minibatch permutations for ALL epochs up front, into one pinned buffer: same
+        """Minibatch permutations for ALL epochs up front, into one (pinned) int32 buffer: same
         RNG consumption order as the reference (np.random.shuffle once per epoch,
         optimizers/util.py:10-11; nothing else draws inside optimize)."""
-        bs = self._minibatch_size
-        flat = [mb for _ in range(self._epochs)
-                for mb in iterate_mb_idxs(bs, data_length, self._shuffle)]
+        if self._minibatch_size is None and self._none_is_whole_batch:
+            self._minibatch_size = int(data_length)         # (known at the first call)
+        flat = [mb for _ in range(self._epochs) for mb in self._epoch_minibatches(data_length)]
         if self._idx_host is None:
-            shape = (max(len(flat), 1), bs)
-            self._idx_host = torch.zeros(shape, dtype=torch.int32).pin_memory()
-            self._idx_dev = torch.zeros(shape, dtype=torch.int32, device=self._target.device)
+            shape = (max(len(flat), 1), len(flat[0]) if flat else self._minibatch_size)
+            self._idx_host = torch.zeros(shape, dtype=torch.int32)
+            if torch.cuda.is_available():
+                self._idx_host = self._idx_host.pin_memory()
+            self._idx_dev = None                            # (its device twin: the first device_updates allocates it)
         self._n_minibatches = len(flat)
         self._set_updates_per_call(len(flat))
         if flat:
             self._idx_host.copy_(torch.from_numpy(np.stack(flat).astype(np.int32)))
 
+    def _epoch_minibatches(self, data_length):
+        """One epoch's rows of the index buffer (one draw from the host RNG): here the minibatches' row indices."""
+        return iterate_mb_idxs(self._minibatch_size, data_length, self._shuffle)
+
     def device_updates(self, inputs):
         data = dict(zip(self._input_names, inputs))      # "_f_load": already on the device
         if not self._n_minibatches:
             return [], []
+        if self._idx_dev is None:
+            self._idx_dev = torch.zeros(tuple(self._idx_host.shape), dtype=torch.int32, device=self._target.device)
         _lib.copy_bytes(self._idx_dev, self._idx_host)
         if self._overlap_allreduce:
             return self._overlapped_minibatches(data)
-        losses = []
         corun = self._corun_hook() if self.parallelism_tag == "single" else None
+
+        def plain(mb):
+            if corun is not None:
+                mb["dense_w_hook"] = corun
+            loss = self._backward(self._losses, mb)
+            self._share_grad()
+            return loss
+        return self._minibatches(data, plain)
+
+    def _minibatches(self, data, step):
+        """The loop: per minibatch `step(mb)` leaves the (shared) gradient in the bucket and returns the loss, then
+        the update."""
+        losses = []
         try:
             for k in range(self._n_minibatches):
-                mb = self._minibatch(data, self._idx_dev[k])
-                if corun is not None:
-                    mb["dense_w_hook"] = corun
-                losses.append(self._backward(self._losses, mb))
-                self._share_grad()
+                self._before_minibatch(k)
+                losses.append(step(self._minibatch(data, self._idx_dev[k])))
                 self._apply_update(self._avg_factor())
         finally:
             self._hole = None           # (a backward pass that raised leaves no hole behind for the next call)
         return losses, self._recent_grad_norms(self._n_minibatches)
+
+    def _before_minibatch(self, k):
+        pass
 
     def _minibatch(self, data, idx):
         return dict(data, idx=idx)               # the kernels gather the minibatch's rows by idx themselves
@@ -125,16 +135,14 @@ class PpoOptimizer(BaseOptimizer):
     _overlap_allreduce = False
 
     def _overlapped_minibatches(self, data):
-        losses = []
-        for k in range(self._n_minibatches):
+        def overlapped(mb):
             pending = []
-            mb = self._minibatch(data, self._idx_dev[k])
             mb["split_hook"] = lambda: pending.append(self._share_grad_async(tail=True))
-            losses.append(self._backward(self._losses, mb))
+            loss = self._backward(self._losses, mb)
             pending.append(self._share_grad_async(tail=False) if pending else self._share_grad_async(None))
             self._wait_all(pending)
-            self._apply_update(self._avg_factor())
-        return losses, self._recent_grad_norms(self._n_minibatches)
+            return loss
+        return self._minibatches(data, overlapped)
 
     @staticmethod
     def _wait_all(pending):
@@ -146,69 +154,46 @@ class PpoOptimizer(BaseOptimizer):
         """All-reduce of the gradient bucket's tail (True), head (False) or all of it (None); a Work or None."""
         return None
 
-    def _share_grad(self):
-        pass
-
-    def _avg_factor(self):
-        return 1.0
-
-    @property
-    def parallelism_tag(self):
-        return "single"
-
 
 class VtraceOptimizer(PpoOptimizer):
     """PpoOptimizer whose every epoch starts with a call back into the algorithm: `_epoch_hook(epoch)` runs before the
     first minibatch of each epoch, epoch 0 included (IMPALA recomputes its V-trace targets there from the parameters as
-    they stand, into the tensors the minibatches gather from).  The host side is the parent's: prepare_host draws every
-    epoch's permutations up front.  minibatch_size None = the whole batch, one update per epoch (known at the first
-    prepare_host)."""
+    they stand, into the tensors the minibatches gather from).  That is the one difference in the loop; besides it,
+    minibatch_size None = the whole batch, one update per epoch, and the co-run hook is not offered."""
 
     _epoch_hook = None          # set by the algorithm (IMPALA.initialize); None: plain PpoOptimizer epochs
+    _none_is_whole_batch = True
+    corun_update = False
 
-    def prepare_host(self, data_length):
-        if self._minibatch_size is None:
-            self._minibatch_size = int(data_length)
-        super().prepare_host(data_length)
-
-    def device_updates(self, inputs):
-        data = dict(zip(self._input_names, inputs))
-        if not self._n_minibatches:
-            return [], []
-        _lib.copy_bytes(self._idx_dev, self._idx_host)
+    def _before_minibatch(self, k):
         per_epoch = self._n_minibatches // self._epochs
-        losses = []
-        for k in range(self._n_minibatches):
-            if k % per_epoch == 0 and self._epoch_hook is not None:
-                self._epoch_hook(k // per_epoch)
-            losses.append(self._backward(self._losses, self._minibatch(data, self._idx_dev[k])))
-            self._share_grad()
-            self._apply_update(self._avg_factor())
-        return losses, self._recent_grad_norms(self._n_minibatches)
+        if k % per_epoch == 0 and self._epoch_hook is not None:
+            self._epoch_hook(k // per_epoch)
 
 
 class VmpoOptimizer(PpoOptimizer):
-    """PpoOptimizer that also owns V-MPO's duals (eta, alpha): after the network's step of every minibatch, one
-    arl_vmpo_dual_step moves both on the gradients the minibatch left behind -- temp4[1] (arl_vmpo_weights, which the
-    algorithm points at `temp4`) and eps_alpha - loss4[2] (the head's mean KL) -- and projects them onto x >= 1e-8.
-    `duals`, their optimiser slots, their step count and `temp4` are allocated at initialize(), so a captured graph keeps
-    its addresses.  dual_args = dict(learning_rate, update_method, update_method_args), each defaulting to the
-    network's; the learning-rate multiplier is the network's.  minibatch_size None = the whole batch."""
+    """PpoOptimizer that also owns V-MPO's duals (eta, alpha).  The one difference in the loop: after the network's
+    step of every minibatch, one arl_vmpo_dual_step moves both on the gradients the minibatch left behind -- temp4[1]
+    (arl_vmpo_weights, which the algorithm points at `temp4`) and eps_alpha - loss4[2] (the head's mean KL) -- and
+    projects them onto x >= 1e-8.  `duals`, their optimiser slots, their step count and `temp4` are allocated at
+    initialize(), so a captured graph keeps its addresses.  dual_args = dict(learning_rate, update_method,
+    update_method_args), each defaulting to the network's; the learning-rate multiplier is the network's.
+    minibatch_size None = the whole batch."""
+
+    _none_is_whole_batch = True
 
     def __init__(self, learning_rate, update_method, update_method_args, epochs, minibatch_size, dual_args=None,
                  dual_init=(1.0, 5.0), eps_alpha=0.005, **kwargs):
         super().__init__(learning_rate, update_method, update_method_args, epochs, minibatch_size, **kwargs)
-        dual = dict(dual_args or dict())
-        unknown = sorted(set(dual) - {"learning_rate", "update_method", "update_method_args"})
-        if unknown:
-            raise ValueError("dual_args: unknown keys %s (learning_rate, update_method, update_method_args)" % unknown)
-        self._dual_lr = dual.get("learning_rate", learning_rate)
-        self._dual_method = dual.get("update_method", update_method)
-        if "update_method" in dual:                 # (another rule does not inherit the network's arguments)
-            dual.setdefault("update_method_args", dict())
-        a = self._dual_method.resolve(**(dual.get("update_method_args", update_method_args) or dict()))
-        self._dual_kernel_args = (a["beta1"], a["beta2"], a["epsilon"]) if self._dual_method.name == "adam" else \
-            (a["rho"], 0.0, a["epsilon"])
+        given = dict(dual_args or dict())
+        if "update_method" in given:                # (another rule does not inherit the network's arguments)
+            given.setdefault("update_method_args", dict())
+        dual = sub_args(given, dict(learning_rate=learning_rate, update_method=update_method,
+                                    update_method_args=update_method_args), ValueError,
+                        "dual_args: unknown keys %s (learning_rate, update_method, update_method_args)")
+        self._dual_lr, self._dual_method = dual["learning_rate"], dual["update_method"]
+        self._dual_kernel_args = kernel_args(self._dual_method,
+                                             self._dual_method.resolve(**(dual["update_method_args"] or dict())))
         self.dual_init = (float(dual_init[0]), float(dual_init[1]))
         self.eps_alpha = float(eps_alpha)
 
@@ -221,11 +206,6 @@ class VmpoOptimizer(PpoOptimizer):
         self._dual_slot1 = torch.zeros(2, dtype=torch.float32, device=dev) if self._dual_method.name == "adam" else None
         self._dual_step_count = torch.zeros(1, dtype=torch.float32, device=dev)
         self._loss4 = None
-
-    def prepare_host(self, data_length):
-        if self._minibatch_size is None:
-            self._minibatch_size = int(data_length)
-        super().prepare_host(data_length)
 
     def _backward(self, losses, minibatch):
         self._loss4 = losses(minibatch)             # (pi_loss, v_loss, mean KL, their sum): the dual step reads [2]
@@ -242,22 +222,21 @@ class VmpoOptimizer(PpoOptimizer):
 class TrajPpoOptimizer(PpoOptimizer):
     """PPO for recurrent policies: epochs x minibatches of WHOLE trajectory segments (optimizers/util.py:21-32,
     iterate_traj_idxs; the reference's own PpoOptimizer slices rows and cuts trajectories apart).  `minibatch_size`
-    keeps the reference's meaning -- rows -- so a minibatch is `minibatch_size // horizon` segments.  The host draws
-    the segment numbers (one np.random.shuffle of the segments per epoch); per minibatch one arl_traj_minibatch launch
-    builds the row indices, the segments' stored initial states and 1 / sum(valids) on the device, and the policy's
-    forward / BPTT runs on those rows.  Static shapes, no host synchronisation: captured like PpoOptimizer's call."""
+    keeps the reference's meaning -- rows -- so a minibatch is `minibatch_size // horizon` segments.  The one difference
+    from PpoOptimizer: the index buffer holds segment numbers, not rows (one np.random.shuffle of the segments per
+    epoch), and per minibatch one arl_traj_minibatch launch builds the row indices, the segments' stored initial states
+    and 1 / sum(valids) on the device; the policy's forward / BPTT runs on those rows.  Static shapes, no host
+    synchronisation: captured like PpoOptimizer's call."""
 
     trajectory_minibatches = True       # AdvActorCriticBase.initialize lets a recurrent policy through
     corun_update = False                # (a feed-forward-policy feature: the recurrent backward pass offers no hole)
-    _overlap_allreduce = False
 
     def initialize(self, inputs, losses, constraints, target, givens=None, lr_mult=1, horizon=None, data_length=None):
         if horizon is None or data_length is None:
             raise TypeError("TrajPpoOptimizer.initialize needs horizon and data_length (the algorithm passes them)")
-        self._horizon, bs = int(horizon), self._minibatch_size
-        self.check_sizes(bs, int(data_length), self._horizon)
+        self._horizon = int(horizon)
+        self.check_sizes(self._minibatch_size, int(data_length), self._horizon)
         super().initialize(inputs, losses, constraints, target, givens=givens, lr_mult=lr_mult)
-        self._seg_host = self._seg_dev = None
 
     @staticmethod
     def check_sizes(minibatch_size, data_length, horizon):
@@ -268,31 +247,9 @@ class TrajPpoOptimizer(PpoOptimizer):
                              "horizon (%d), and the batch a multiple of minibatch_size" %
                              (minibatch_size, data_length, horizon))
 
-    def prepare_host(self, data_length):
-        """Segment numbers of every minibatch of ALL epochs into one (pinned) int32 buffer: the same RNG consumption
-        as the reference function (np.random.shuffle of the segments once per epoch, nothing else)."""
-        per = self._minibatch_size // self._horizon
-        flat = [segs for _ in range(self._epochs)
-                for _, segs in iterate_traj_idxs(self._minibatch_size, data_length, self._horizon, self._shuffle)]
-        if getattr(self, "_seg_host", None) is None:
-            self._seg_host = torch.zeros((len(flat), per), dtype=torch.int32)
-            if torch.cuda.is_available():
-                self._seg_host = self._seg_host.pin_memory()
-        self._n_minibatches = len(flat)
-        self._set_updates_per_call(len(flat))
-        self._seg_host.copy_(torch.from_numpy(np.stack(flat).astype(np.int32)))
-
-    def device_updates(self, inputs):
-        data = dict(zip(self._input_names, inputs))
-        if self._seg_dev is None:
-            self._seg_dev = torch.zeros(tuple(self._seg_host.shape), dtype=torch.int32, device=self._target.device)
-        _lib.copy_bytes(self._seg_dev, self._seg_host)
-        losses = []
-        for k in range(self._n_minibatches):
-            losses.append(self._backward(self._losses, self._minibatch(data, self._seg_dev[k])))
-            self._share_grad()
-            self._apply_update(self._avg_factor())
-        return losses, self._recent_grad_norms(self._n_minibatches)
+    def _epoch_minibatches(self, data_length):
+        """The segment numbers of one epoch's minibatches: the same RNG consumption as the reference function."""
+        return [segs for _, segs in iterate_traj_idxs(self._minibatch_size, data_length, self._horizon, self._shuffle)]
 
     def _minibatch(self, data, seg):
         """One arl_traj_minibatch launch: traj_idx, traj_state and inv_count of the chosen segments."""

@@ -329,7 +329,7 @@ def test_optimizer_steps_match_the_oracle_adam(kind):
     before = state()
     np.random.seed(3)
     opt.prepare_host(nb * t_len)
-    seg_mbs = opt._seg_host.numpy().copy()
+    seg_mbs = opt._idx_host.numpy().copy()
     assert seg_mbs.shape == (2, 4) and sorted(seg_mbs.reshape(-1)) == list(range(nb))
     _, norms = opt.device_updates(inputs)
     torch.cuda.synchronize()

@@ -24,7 +24,7 @@ def _optimizer(minibatch_size, horizon, epochs, shuffle=True):
     from accel_rl_amd.optimizers.single import TrajPpoOptimizer
     opt = TrajPpoOptimizer(learning_rate=1e-3, update_method=update_methods.adam, update_method_args=dict(epsilon=1e-5),
                            epochs=epochs, minibatch_size=minibatch_size, shuffle=shuffle)
-    opt._horizon, opt._seg_host, opt._n_updates = horizon, None, 0
+    opt._horizon, opt._idx_host, opt._n_updates = horizon, None, 0
     opt._opt_state = types.SimpleNamespace(norm_log_len=1)
     return opt
 
@@ -45,7 +45,7 @@ def test_prepare_host_draws_the_reference_segments(shuffle):
             opt.prepare_host(n)
             after = np.random.randint(0, 2 ** 31 - 1, size=2)
             np.testing.assert_array_equal(after, after_ref)    # same amount of the stream consumed
-            got = opt._seg_host.numpy()
+            got = opt._idx_host.numpy()
             per_epoch = n // bs
             assert got.dtype == np.int32 and got.shape == (epochs * per_epoch, bs // horizon)
             assert opt._n_minibatches == epochs * per_epoch
