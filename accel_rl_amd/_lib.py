@@ -284,6 +284,10 @@ _SIGNATURES = {
     "arl_rnd_obs_prepare": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "arl_rnd_error": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "arl_rnd_reward_mix": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _f64, _f64, _f64, _vp, _vp, _vp, _vp]),
+    "arl_acer_retrace_scan": (_i32, [_vp] * 4 + [_i32, _vp, _vp, _vp, _vp, _f64, _f64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "arl_acer_loss": (_i32, [_vp] * 6 + [_i64, _i32, _i32, _f64, _f64, _f64, _f64, _vp, _vp, _vp]),
+    "arl_acer_avg_step": (_i32, [_vp, _vp, _i64, _f32, _vp]),
+    "arl_gather_segments": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "arl_opt_step": (_i32, [C.POINTER(ArlOptState), _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
     "arl_opt_step_noclip": (_i32, [C.POINTER(ArlOptState), _i32, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp]),
     "arl_opt_finish": (_i32, [C.POINTER(ArlOptState), _i32, _f32, _vp, _vp, _vp]),
@@ -1487,6 +1491,80 @@ def vtrace_scan(prob, old_prob, actions, values, last_values, rewards, dones, di
                                   ptr(dones), float(discount), float(vtrace_lambda), float(rho_bar), float(c_bar),
                                   float(pg_rho_bar), n_env, horizon, n_actions, ptr(returns), ptr(advantages), ptr(stats),
                                   stream_ptr(stream)), "arl_vtrace_scan")
+
+
+# ---------------------------------------------------------------------------
+# ACER: Retrace scan, head loss, average-network step, segment gather (csrc/acer.hip)
+# ---------------------------------------------------------------------------
+
+def acer_retrace_scan(prob, prob_last, q, q_last, old_prob, actions, rewards, dones, discount, retrace_lambda, n_env,
+                      horizon, qret, v_out=None, stats=None, stream=None):
+    """Retrace(lambda) targets (arl_acer_retrace_scan): prob, old_prob [n_env * horizon, A], prob_last [n_env, A], rows
+    env-major; q / q_last are VIEWS of the Q half of the network output (rows [.., q_stride], the first A columns read):
+    their row stride is taken from the tensors.  stats (optional) f32 [n_env, 2] = (sum of rho, steps with rho > 1)."""
+    for t, n in ((prob, "prob"), (prob_last, "prob_last"), (q, "q"), (q_last, "q_last"), (old_prob, "old_prob"),
+                 (rewards, "rewards"), (qret, "qret"), (v_out, "v_out"), (stats, "stats")):
+        if t is not None:
+            _want(t, torch.float32, n)
+    _want(actions, torch.uint8, "actions")
+    if dones.dtype not in (torch.uint8, torch.bool):
+        raise TypeError("dones must be uint8/bool")
+    steps = n_env * horizon
+    n_actions = prob_last.numel() // n_env
+    assert prob.numel() == old_prob.numel() == steps * n_actions and prob_last.numel() == n_env * n_actions, "prob sizes"
+    assert actions.numel() == rewards.numel() == dones.numel() == qret.numel() == steps, "per-step sizes"
+    assert v_out is None or v_out.numel() == steps, "v_out size"
+    assert stats is None or stats.numel() == 2 * n_env, "stats size"
+    for t, rows in ((q, steps), (q_last, n_env)):
+        if not (t.dim() == 2 and t.shape[0] == rows and t.shape[1] >= n_actions and t.stride(1) == 1 and t.is_cuda):
+            raise ValueError("q / q_last: device rows [%d, >= %d] with unit column stride" % (rows, n_actions))
+    stride = q.stride(0)                        # (a one-row view keeps the stride of the block it was cut from)
+    if n_env > 1 and q_last.stride(0) != stride:
+        raise ValueError("q and q_last must share one row stride")
+    _check(load().arl_acer_retrace_scan(ptr(prob), ptr(prob_last), q.data_ptr(), q_last.data_ptr(), stride,
+                                        ptr(old_prob), ptr(actions), ptr(rewards), ptr(dones), float(discount),
+                                        float(retrace_lambda), n_env, horizon, n_actions, ptr(qret), ptr(v_out),
+                                        ptr(stats), stream_ptr(stream)), "arl_acer_retrace_scan")
+
+
+def acer_loss(out, out_avg, old_prob, actions, qret, idx, n_actions, c, delta, q_coeff, ent_coeff, dout, stats,
+              stream=None):
+    """ACER's output stage (arl_acer_loss): out, out_avg, dout f32 [B, 2S]; old_prob / actions / qret full-batch arrays
+    read at idx (None: row b); stats f32 [5, B] = pi_loss_rows | q_loss_rows | ent_rows | trust scale | rho(a_t)."""
+    batch = stats.numel() // 5
+    for t, n in ((out, "out"), (out_avg, "out_avg"), (old_prob, "old_prob"), (qret, "qret"), (dout, "dout"),
+                 (stats, "stats")):
+        _want(t, torch.float32, n)
+    _want(actions, torch.uint8, "actions")
+    if idx is not None:
+        _want(idx, torch.int32, "idx")
+        assert idx.numel() == batch, "idx size"
+    assert stats.numel() == 5 * batch and out.numel() == out_avg.numel() == dout.numel() and \
+        out.numel() % (2 * batch) == 0, "out / out_avg / dout / stats size"
+    _check(load().arl_acer_loss(ptr(out), ptr(out_avg), ptr(old_prob), ptr(actions), ptr(qret), ptr(idx), batch,
+                                n_actions, out.numel() // (2 * batch), float(c), float(delta), float(q_coeff),
+                                float(ent_coeff), ptr(dout), ptr(stats), stream_ptr(stream)), "arl_acer_loss")
+
+
+def acer_avg_step(avg, params, alpha, stream=None):
+    """avg <- alpha avg + (1 - alpha) params (arl_acer_avg_step), fp32, no fma."""
+    _want(avg, torch.float32, "avg")
+    _want(params, torch.float32, "params")
+    assert avg.numel() == params.numel(), "avg / params size"
+    _check(load().arl_acer_avg_step(ptr(avg), ptr(params), avg.numel(), float(alpha), stream_ptr(stream)),
+           "arl_acer_avg_step")
+
+
+def gather_segments(src, index, dst, stream=None):
+    """dst[i] = src[index[i]] over the leading axis (arl_gather_segments): index i32 on the device, clamped into range."""
+    _want(index, torch.int32, "index")
+    n_seg, n_src = dst.shape[0], src.shape[0]
+    if src.dtype != dst.dtype or tuple(src.shape[1:]) != tuple(dst.shape[1:]) or index.numel() != n_seg:
+        raise ValueError("gather_segments: src %s %s, dst %s %s, index of %d" %
+                         (tuple(src.shape), src.dtype, tuple(dst.shape), dst.dtype, index.numel()))
+    seg_bytes = src[0].numel() * src.element_size()
+    _check(load().arl_gather_segments(ptr(src), ptr(index), n_seg, n_src, seg_bytes, ptr(dst), stream_ptr(stream)),
+           "arl_gather_segments")
 
 
 # ---------------------------------------------------------------------------

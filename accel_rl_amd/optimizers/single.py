@@ -219,6 +219,39 @@ class VmpoOptimizer(PpoOptimizer):
                             eps)
 
 
+class AcerOptimizer(PpoOptimizer):
+    """PpoOptimizer that also moves ACER's average network.  The one difference in the loop: after the network's step of
+    every update, one arl_acer_avg_step moves the target's second bucket (`flat_target`, the average network) towards the
+    parameters: avg = alpha avg + (1 - alpha) params.  `whole_batch_update` is one more update of the same kind -- the same
+    slots and step count -- on data that is not the call's own (ACER's replayed trajectories); it needs a norm clip (the
+    clip-free update closes its step count and norm log once per call, _finish_updates) and says so.  minibatch_size None = the
+    whole batch; the co-run hook is not offered."""
+
+    _none_is_whole_batch = True
+    corun_update = False
+
+    def __init__(self, learning_rate, update_method, update_method_args, epochs, minibatch_size, avg_alpha=0.99, **kwargs):
+        super().__init__(learning_rate, update_method, update_method_args, epochs, minibatch_size, **kwargs)
+        if not (isinstance(avg_alpha, (int, float, np.floating)) and 0 <= avg_alpha <= 1):
+            raise ValueError("avg_alpha must lie in [0, 1], got %r" % (avg_alpha,))
+        self.avg_alpha = float(avg_alpha)
+
+    def _apply_update(self, avg_factor=1.0):
+        super()._apply_update(avg_factor)
+        _lib.acer_avg_step(self._target.flat_target, self._target.flat_params, self.avg_alpha)
+
+    def whole_batch_update(self, inputs):
+        """One update on all rows of `inputs` (the tuple order of initialize's names), no index; returns the loss."""
+        if self._grad_norm_clip is None:
+            raise NotImplementedError("whole_batch_update needs grad_norm_clip: the clip-free update is closed once per "
+                                      "call (_finish_updates)")
+        mb = dict(zip(self._input_names, inputs))
+        mb["idx"] = None
+        loss = self._backward(self._losses, mb)
+        self._apply_update(self._avg_factor())
+        return loss
+
+
 class TrajPpoOptimizer(PpoOptimizer):
     """PPO for recurrent policies: epochs x minibatches of WHOLE trajectory segments (optimizers/util.py:21-32,
     iterate_traj_idxs; the reference's own PpoOptimizer slices rows and cuts trajectories apart).  `minibatch_size`

@@ -23,7 +23,7 @@ import torch
 from accel_rl_amd import _lib
 from accel_rl_amd.policies.atari_cnn_policy import ObsRows, _norm_c
 from accel_rl_amd.policies.dqn.atari_dqn_policy import AtariDqnPolicy
-from accel_rl_amd.policies.dqn.q_policy_base import QPolicyBase
+from accel_rl_amd.policies.dqn.q_policy_base import QPolicyBase, SoftmaxServeMixin
 
 
 def split_param_vector(flat, sizes):
@@ -36,7 +36,7 @@ def split_param_vector(flat, sizes):
     return [flat[e - n:e] for e, n in zip(ends, sizes)]
 
 
-class AtariSacDiscretePolicy(QPolicyBase):
+class AtariSacDiscretePolicy(SoftmaxServeMixin, QPolicyBase):
 
     def __init__(self, conv_filters, conv_filter_sizes, conv_strides, conv_pads, hidden_sizes=(), pixel_scale=255.,
                  initial_alpha=1.0, deterministic=False, dueling=False, shared_last_bias=False,
@@ -93,36 +93,7 @@ class AtariSacDiscretePolicy(QPolicyBase):
         if init is not None:
             self.set_param_values(init)
 
-    # ---- serving -------------------------------------------------------------------------------------------------
-    def _serve(self, out, override, onehot, greedy=None):
-        _lib.sacd_act(out, override, self.n_act, onehot, greedy, deterministic=self._deterministic)
-
-    def serve_supported(self):
-        return False
-
-    def set_deterministic(self, flag):
-        """Serve the first maximum of the logits (evaluation) instead of the soft-max row."""
-        self._deterministic = bool(flag)
-
-    def get_deterministic(self):
-        return self._deterministic
-
-    def set_epsilon(self, value):
-        pass                                  # (no epsilon-greedy: the policy is stochastic by itself)
-
-    def get_epsilon(self):
-        return 0.
-
-    def host_draws(self, horizon, n_envs, n_groups=2):
-        """One rollout's action randomness: the reference-order uniforms np.random.rand(horizon * n_envs), which the
-        sampler feeds its categorical kernel, and an override table that forces nothing (all -1)."""
-        u = np.random.rand(horizon * n_envs)
-        self._select_overrides(horizon, n_envs, lambda: (
-            torch.full((horizon, n_envs), -1, dtype=torch.int32).pin_memory(),
-            torch.full((horizon, n_envs), -1, dtype=torch.int32, device=self.device)))
-        self._draws[n_envs] = u.reshape(horizon, n_envs)
-        return u
-
+    # ---- serving: SoftmaxServeMixin, and the host sampler's groups ------------------------------------------------
     def serve_group(self, observations, row0, n_envs):
         """QPolicyBase.serve_group for a sampler that feeds its categorical kernel the uniform 0.5: the group's actions
         are drawn here, from the group's slice of host_draws' uniforms, and served as one-hot rows."""
@@ -140,14 +111,6 @@ class AtariSacDiscretePolicy(QPolicyBase):
                 _lib.sample_categorical(prob, torch.from_numpy(u[self._step, row0:row0 + b].copy()).to(self.device), acts)
                 self._serve(logits, acts.to(torch.int32), prob)
             return prob, torch.zeros(b, dtype=torch.float32, device=self.device)
-
-    def get_actions(self, observations, deterministic=False):
-        if deterministic or self._deterministic:
-            return self.greedy_actions(observations).cpu().numpy(), dict()
-        return self._sample(self.prob_value(observations)[0]).cpu().numpy(), dict()
-
-    def get_action(self, observation, deterministic=False):
-        return int(self.get_actions(observation[None], deterministic)[0][0]), dict()
 
     def update_target(self):
         self.q1.update_target()

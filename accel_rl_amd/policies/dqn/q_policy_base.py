@@ -90,6 +90,51 @@ class EpsGreedyTargetMixin(object):
         self.flat_target.copy_(self.flat_params)
 
 
+class SoftmaxServeMixin(object):
+    """Serving of a Q-policy-based class whose network puts out LOGITS of a stochastic policy (AtariSacDiscretePolicy's
+    actor, AtariAcerPolicy): csrc/sac.hip:arl_sacd_act gives the soft-max row, from which the sampler's categorical
+    kernel draws with the real uniforms of host_draws (the override table forces nothing), or -- deterministic mode,
+    for evaluation -- a one-hot row at the first maximum.  The host class sets `_deterministic` and `_draws` (a dict)
+    in its constructor."""
+
+    def _serve(self, out, override, onehot, greedy=None):
+        _lib.sacd_act(out, override, self.n_act, onehot, greedy, deterministic=self._deterministic)
+
+    def serve_supported(self):
+        return False
+
+    def set_deterministic(self, flag):
+        """Serve the first maximum of the logits (evaluation) instead of the soft-max row."""
+        self._deterministic = bool(flag)
+
+    def get_deterministic(self):
+        return self._deterministic
+
+    def set_epsilon(self, value):
+        pass                                  # (no epsilon-greedy: the policy is stochastic by itself)
+
+    def get_epsilon(self):
+        return 0.
+
+    def host_draws(self, horizon, n_envs, n_groups=2):
+        """One rollout's action randomness: the reference-order uniforms np.random.rand(horizon * n_envs), which the
+        sampler feeds its categorical kernel, and an override table that forces nothing (all -1)."""
+        u = np.random.rand(horizon * n_envs)
+        self._select_overrides(horizon, n_envs, lambda: (
+            torch.full((horizon, n_envs), -1, dtype=torch.int32).pin_memory(),
+            torch.full((horizon, n_envs), -1, dtype=torch.int32, device=self.device)))
+        self._draws[n_envs] = u.reshape(horizon, n_envs)
+        return u
+
+    def get_actions(self, observations, deterministic=False):
+        if deterministic or self._deterministic:
+            return self.greedy_actions(observations).cpu().numpy(), dict()
+        return self._sample(self.prob_value(observations)[0]).cpu().numpy(), dict()
+
+    def get_action(self, observation, deterministic=False):
+        return int(self.get_actions(observation[None], deterministic)[0][0]), dict()
+
+
 class QPolicyBase(EpsGreedyTargetMixin, AtariCnnPolicy):
     """Subclasses give `_head_width` (columns of the output layer as stored), `_serve(out, override, onehot,
     greedy)` (the action kernel; or, where the network is not `_logits`, `_serve_obs`) and the four `_head_*` layout

@@ -2043,6 +2043,101 @@ int arl_noisy_catdqn_loss_parts(const arl_noisy_logit_src* pred, const arl_noisy
                                 float v_min, float v_max, float gamma_n, float* dlogits, float* loss_rows, float* kl,
                                 const struct arl_dgrad_wt* wt_items_or_null, int32_t n_wt, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * ACER (Wang et al. 2017, "Sample Efficient Actor-Critic with Experience Replay"; the reference has none).
+ * csrc/acer.hip.  One network puts out a row f32[2S], S a multiple of 4 with S >= A (the policy uses S = A rounded up to
+ * a multiple of 32): columns [0, A) are the logits z, columns [S, S + A) the action values Q; padding is ignored on
+ * input and written as exact zeros on output.  pi_a and lp_a of a logit row are the fp32 soft-max and log-soft-max
+ * defined at arl_sacd_loss (the same device function).  eps = 1e-6 (a double) wherever a probability is a divisor, as
+ * in the public implementation.  All four entry points: plain C++ HIP, no atomics (two launches on the same
+ * inputs give the same bits), 64-bit indexing, no host synchronisation; a refused call launches nothing and writes
+ * nothing.
+ * ------------------------------------------------------------------------- */
+
+/* Retrace(lambda) targets of Q, computed backwards over a rollout from the CURRENT network against the behaviour policy
+ * the sampler recorded.  Rows env-major: row e * horizon + t.
+ *   prob       f32[n_env * horizon][A]   the current policy's soft-max rows (arl_sacd_act on the network output at
+ *                                        stride 2S: the scan itself calls no device-library function)
+ *   prob_last  f32[n_env][A]             ... on the observations after the last step
+ *   q, q_last  the Q half of the network output on the same rows: entry (row, a) at q[row * q_stride + a]
+ *   old_prob   f32[n_env * horizon][A]   the behaviour policy mu
+ *   actions    u8[n_env * horizon]       a byte >= A is read as A - 1
+ *   rewards    f32[n_env * horizon]      dones u8[n_env * horizon] (0 / non-zero)
+ *   qret_out   f32[n_env * horizon] (out);  v_out_or_null f32[n_env * horizon] (out, optional)
+ *   stats_or_null f32[n_env][2] (out, optional): [0] = the sum of rho over the env's steps, added in float64 in walk
+ *              order (t = T - 1 .. 0, from 0.0) and rounded once; [1] = the number of steps with rho > 1
+ * Everything is float64 from the promoted inputs on, in exactly this expression order and without contraction:
+ *   V(row) = sum_a (double) prob[row][a] * (double) q[row][a]          a ascending, the sum starts at 0.0
+ *   qret   = V(last row of env e), from prob_last and q_last
+ *   for t = T - 1 .. 0, a = min(actions[row], A - 1):
+ *     qret = (double) r_t + (done_t ? 0.0 : discount * qret)
+ *     qret_out[row] = (float) qret;   v_out[row] = (float) V_t
+ *     rho  = (double) prob[row][a] / ((double) old_prob[row][a] + eps)
+ *     cbar = lambda * (rho < 1.0 ? rho : 1.0)
+ *     qret = cbar * (qret - (double) q[row][a]) + V_t
+ * qret is carried as a double across steps, never as the rounded float that was stored: equal to a float64 restatement
+ * bit for bit.  One wave per env: V, rho and Q(a) of the steps in parallel, one lane walks the T steps.
+ * Refused before any HIP call: a NULL pointer other than the two optional ones (ARL_E_ARG); n_env outside 1 .. 2^31 - 1,
+ * horizon outside 1 .. 4096, n_actions outside 1 .. ARL_MAX_ACTIONS, q_stride < n_actions, not a multiple of 4 or > 2^20
+ * (ARL_E_RANGE); discount or lambda not finite or outside [0, 1], an output overlapping an input or another output
+ * (ARL_E_ARG); a float pointer not 4-byte aligned (ARL_E_ALIGN).                                                      */
+int arl_acer_retrace_scan(const float* prob, const float* prob_last, const float* q, const float* q_last,
+                          int32_t q_stride, const float* old_prob, const uint8_t* actions, const float* rewards,
+                          const uint8_t* dones, double discount, double lambda, int64_t n_env, int32_t horizon,
+                          int32_t n_actions, float* qret_out, float* v_out_or_null, float* stats_or_null, void* stream);
+
+/* The output stage of one ACER minibatch in one launch, one lane per sample.
+ *   out      f32[batch][2S]   the live network's output;   out_avg f32[batch][2S] the average network's on the same rows
+ *                             (only its logits are read);  S = half_stride
+ *   old_prob f32[n][A], actions u8[n], qret f32[n]: read at row src = idx_or_null ? idx_or_null[b] : b (the caller
+ *                             answers for idx, as for arl_q_regress_loss)
+ *   dout     f32[batch][2S] (out);   stats f32[5][batch] (out)
+ * Per sample, with (fp32) pi, lp of out's logits and pibar of out_avg's, everything below in float64 from the promoted
+ * values P_a = (double) pi_a, L_a = (double) lp_a, B_a = (double) pibar_a, Q_a, mu_a = (double) old_prob[src][a],
+ * R = (double) qret[src], t = min(actions[src], A - 1); every sum over the actions runs a ascending and starts at 0.0:
+ *   V     = sum_a P_a * Q_a;   adv = R - V
+ *   rho_a = P_a / (mu_a + eps);   f = (rho_t < c ? rho_t : c) * adv
+ *   w_a   = 1.0 - c / (rho_a + eps), replaced by 0.0 unless > 0.0
+ *   g_a   = ((a == t ? f / (P_a + eps) : 0.0) + w_a * (Q_a - V)) - ent_coeff * (L_a + 1.0)
+ *           (the gradient with respect to the probabilities of the truncated term, the bias-correction term and the
+ *            entropy bonus; Q, V and the weights are constants)
+ *   k_a   = -(B_a / (P_a + eps))
+ *   kg    = sum_a k_a * g_a;   kk = sum_a k_a * k_a
+ *   s     = kk > 0.0 ? max((kg - delta) / kk, 0.0) : 0.0      (kk == 0.0 -- an all-zero pibar row -- projects nothing)
+ *   zs_a  = g_a - s * k_a;   pz = sum_a P_a * zs_a
+ *   dout[b][j]     = (float) (-(P_j * (zs_j - pz)) / (double) batch),  j < A
+ *   dout[b][S + t] = (float) ((q_coeff * (Q_t - R)) / (double) batch);  every other column: exact zero
+ *   stats[0][b] = (float) (-(obj + ent_coeff * H) / batch), the policy-objective row, a diagnostic:
+ *                 obj = f * L_t, then for a ascending obj = obj + ((w_a * (Q_a - V)) * P_a) * L_a;  H = -(sum_a P_a * L_a)
+ *   stats[1][b] = (float) (((0.5 * q_coeff) * ((Q_t - R) * (Q_t - R))) / batch)
+ *   stats[2][b] = (float) H;   stats[3][b] = (float) s;   stats[4][b] = (float) rho_t
+ * Stated limits: delta = +inf switches the projection off (s == 0.0 exactly); c = +inf switches the correction term off
+ * (w_a == 0.0) and leaves the importance weight untruncated.
+ * Refused before any HIP call: a NULL pointer other than idx_or_null, c not > 0, delta not >= 0 (a NaN fails both), q_coeff
+ * or ent_coeff not finite, dout or stats overlapping out, out_avg or one another (ARL_E_ARG); batch outside 1 .. 2^31 - 1,
+ * n_actions outside 1 .. ARL_MAX_ACTIONS, half_stride < n_actions, not a multiple of 4 or > 2^19 (ARL_E_RANGE); a float
+ * pointer or idx not 4-byte aligned (ARL_E_ALIGN).                                                                    */
+int arl_acer_loss(const float* out, const float* out_avg, const float* old_prob, const uint8_t* actions,
+                  const float* qret, const int32_t* idx_or_null, int64_t batch, int32_t n_actions, int32_t half_stride,
+                  double c, double delta, double q_coeff, double ent_coeff, float* dout, float* stats, void* stream);
+
+/* The average network's step over a flat bucket, fp32:
+ *   beta = 1.0f - alpha (once, on the host);   avg[i] = (alpha * avg[i]) + (beta * params[i])
+ * two rounded products and one rounded sum, never an fma.  16-byte accesses with a scalar tail where both pointers are
+ * 16-byte aligned, 4-byte accesses otherwise: the same bits either way.
+ * Refused: a NULL pointer, alpha outside [0, 1] or NaN, avg overlapping params (ARL_E_ARG); n outside 1 .. 2^31 - 1
+ * (ARL_E_RANGE); a pointer not 4-byte aligned (ARL_E_ALIGN).                                                          */
+int arl_acer_avg_step(float* avg, const float* params, int64_t n, float alpha, void* stream);
+
+/* dst segment i = src segment index[i], i < n_seg; segments are seg_bytes long and contiguous, src holds n_src_seg of
+ * them.  index is i32[n_seg] ON THE DEVICE (a captured graph replays with new draws); nothing is read back by the host,
+ * so an index < 0 is taken as 0 and one >= n_src_seg as n_src_seg - 1.  16-byte copies where seg_bytes is a multiple of
+ * 16 and src and dst are 16-byte aligned, byte copies otherwise.
+ * Refused: a NULL pointer, dst overlapping src or index (ARL_E_ARG); n_seg or n_src_seg outside 1 .. 2^31 - 1, seg_bytes
+ * outside 1 .. 2^31 (ARL_E_RANGE); index not 4-byte aligned (ARL_E_ALIGN).                                            */
+int arl_gather_segments(const void* src, const int32_t* index, int64_t n_seg, int64_t n_src_seg, int64_t seg_bytes,
+                        void* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
