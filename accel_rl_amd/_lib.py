@@ -463,6 +463,11 @@ def _want(t, dtype, name):
         raise TypeError("%s must be %s, got %s" % (name, dtype, t.dtype))
 
 
+def _want_flags(t, name):
+    if t.dtype not in (torch.uint8, torch.bool):
+        raise TypeError("%s must be uint8/bool" % name)
+
+
 # ---------------------------------------------------------------------------
 # thin typed wrappers (device tensors in, device tensors out)
 # ---------------------------------------------------------------------------
@@ -472,8 +477,7 @@ def gae_scan(rewards, values, dones, last_values, discount, gae_lambda, n_env, h
     for t, n in ((rewards, "rewards"), (values, "values"), (last_values, "last_values"),
                  (advantages, "advantages"), (returns, "returns")):
         _want(t, torch.float32, n)
-    if dones.dtype not in (torch.uint8, torch.bool):
-        raise TypeError("dones must be uint8/bool")
+    _want_flags(dones, "dones")
     assert rewards.numel() == values.numel() == dones.numel() == n_env * horizon
     assert last_values.numel() == n_env and advantages.numel() == returns.numel() == n_env * horizon
     _check(load().arl_gae_scan(ptr(rewards), ptr(values), ptr(dones), ptr(last_values),
@@ -1459,8 +1463,7 @@ def qlambda_scan(q, q_last, rewards, dones, discount, q_lambda, n_env, horizon, 
     """Q(lambda) returns (arl_qlambda_scan): q [n_env * horizon, q_stride], q_last [n_env, q_stride], rows env-major."""
     for t, n in ((q, "q"), (q_last, "q_last"), (rewards, "rewards"), (returns, "returns")):
         _want(t, torch.float32, n)
-    if dones.dtype not in (torch.uint8, torch.bool):
-        raise TypeError("dones must be uint8/bool")
+    _want_flags(dones, "dones")
     stride = q_last.numel() // n_env
     assert q.numel() == n_env * horizon * stride and q_last.numel() == n_env * stride, "q / q_last size"
     assert rewards.numel() == dones.numel() == returns.numel() == n_env * horizon, "rewards / dones / returns size"
@@ -1477,8 +1480,7 @@ def vtrace_scan(prob, old_prob, actions, values, last_values, rewards, dones, di
                  (rewards, "rewards"), (returns, "returns"), (advantages, "advantages")):
         _want(t, torch.float32, n)
     _want(actions, torch.uint8, "actions")
-    if dones.dtype not in (torch.uint8, torch.bool):
-        raise TypeError("dones must be uint8/bool")
+    _want_flags(dones, "dones")
     steps = n_env * horizon
     n_actions = prob.numel() // steps
     assert prob.numel() == old_prob.numel() == steps * n_actions, "prob / old_prob size"
@@ -1507,8 +1509,7 @@ def acer_retrace_scan(prob, prob_last, q, q_last, old_prob, actions, rewards, do
         if t is not None:
             _want(t, torch.float32, n)
     _want(actions, torch.uint8, "actions")
-    if dones.dtype not in (torch.uint8, torch.bool):
-        raise TypeError("dones must be uint8/bool")
+    _want_flags(dones, "dones")
     steps = n_env * horizon
     n_actions = prob_last.numel() // n_env
     assert prob.numel() == old_prob.numel() == steps * n_actions and prob_last.numel() == n_env * n_actions, "prob sizes"
@@ -1739,8 +1740,7 @@ def r2d2_loss(q, q_tgt, actions, returns, terminals, is_weights, batch, burn_in,
                     (loss_rows, "loss_rows"), (priorities, "priorities")):
         _want(t, torch.float32, name)
     _want(actions, torch.uint8, "actions")
-    if terminals.dtype not in (torch.uint8, torch.bool):
-        raise TypeError("terminals must be uint8/bool")
+    _want_flags(terminals, "terminals")
     rows = batch * (burn_in + train_len + n)
     assert actions.numel() == returns.numel() == terminals.numel() == rows, "per-row input sizes"
     assert q.numel() == q_tgt.numel() == dq.numel() and q.numel() % rows == 0, "q / q_tgt / dq size"

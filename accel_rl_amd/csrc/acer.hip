@@ -21,7 +21,7 @@ namespace {
 
 using namespace arlq;
 
-constexpr int AC_MAX_HORIZON = 4096, AC_CHUNK = 1024;
+constexpr int AC_CHUNK = 1024;
 constexpr double AC_EPS = 1e-6;
 
 // V = sum_a p_a q_a in float64, a ascending, the sum starts at 0.0
@@ -255,13 +255,6 @@ __global__ __launch_bounds__(256) void gather_segments_kernel(const uint8_t* __r
     }
 }
 
-bool ac_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
-}
-
-bool ac_unit(double x) { return x >= 0.0 && x <= 1.0; }                // (a NaN fails both comparisons)
-
 }  // namespace
 
 extern "C" int arl_acer_retrace_scan(const float* prob, const float* prob_last, const float* q, const float* q_last,
@@ -271,29 +264,19 @@ extern "C" int arl_acer_retrace_scan(const float* prob, const float* prob_last, 
                                      float* v_out_or_null, float* stats_or_null, void* stream) {
     ARL_REQUIRE(prob && prob_last && q && q_last && old_prob && actions && rewards && dones && qret_out, ARL_E_ARG,
                 "null pointer");
-    ARL_REQUIRE(n_env >= 1 && n_env <= INT32_MAX, ARL_E_RANGE, "1 <= n_env <= 2^31 - 1");
-    ARL_REQUIRE(horizon >= 1 && horizon <= AC_MAX_HORIZON, ARL_E_RANGE, "1 <= horizon <= 4096");
+    ARL_ENV_SCAN_SIZES(n_env, horizon);
     ARL_REQUIRE(n_actions >= 1 && n_actions <= ARL_MAX_ACTIONS, ARL_E_RANGE, "1 <= n_actions <= 18");
-    ARL_REQUIRE(q_stride >= n_actions && (q_stride & 3) == 0 && q_stride <= (1 << 20), ARL_E_RANGE,
-                "n_actions <= q_stride <= 2^20, q_stride % 4 == 0");
-    ARL_REQUIRE(ac_unit(discount) && ac_unit(lambda), ARL_E_ARG, "discount and lambda must lie in [0, 1]");
+    ARL_ENV_SCAN_Q_STRIDE(q_stride, n_actions);
+    ARL_REQUIRE(arl::unit_interval(discount) && arl::unit_interval(lambda), ARL_E_ARG,
+                "discount and lambda must lie in [0, 1]");
     const int64_t steps = n_env * horizon;
     // (the Q rows: from the first row's first entry to the last row's last action)
-    const struct { const void* p; int64_t bytes; } in[8] = {
+    const arl::Span in[8] = {
         {prob, steps * n_actions * 4}, {prob_last, n_env * n_actions * 4},
         {q, ((steps - 1) * q_stride + n_actions) * 4}, {q_last, ((n_env - 1) * q_stride + n_actions) * 4},
         {old_prob, steps * n_actions * 4}, {actions, steps}, {rewards, steps * 4}, {dones, steps}};
-    const struct { const void* p; int64_t bytes; } out[3] = {
-        {qret_out, steps * 4}, {v_out_or_null, steps * 4}, {stats_or_null, n_env * 8}};
-    for (int o = 0; o < 3; ++o) {
-        if (!out[o].p) continue;
-        for (int i = 0; i < 8; ++i)
-            ARL_REQUIRE(!ac_overlap(out[o].p, out[o].bytes, in[i].p, in[i].bytes), ARL_E_ARG,
-                        "an output must not overlap an input");
-        for (int k = o + 1; k < 3; ++k)
-            ARL_REQUIRE(!out[k].p || !ac_overlap(out[o].p, out[o].bytes, out[k].p, out[k].bytes), ARL_E_ARG,
-                        "the outputs must not overlap one another");
-    }
+    const arl::Span out[3] = {{qret_out, steps * 4}, {v_out_or_null, steps * 4}, {stats_or_null, n_env * 8}};
+    if (!arl::check_disjoint(__func__, in, 8, out, 3)) return ARL_E_ARG;
     ARL_REQUIRE(arl::aligned4(prob) && arl::aligned4(prob_last) && arl::aligned4(q) && arl::aligned4(q_last) &&
                 arl::aligned4(old_prob) && arl::aligned4(rewards) && arl::aligned4(qret_out) &&
                 arl::aligned4(v_out_or_null) && arl::aligned4(stats_or_null), ARL_E_ALIGN,
@@ -316,9 +299,9 @@ extern "C" int arl_acer_loss(const float* out, const float* out_avg, const float
     ARL_REQUIRE(c > 0.0 && delta >= 0.0, ARL_E_ARG, "c must be > 0 and delta >= 0 (+inf allowed, NaN not)");
     ARL_REQUIRE(std::isfinite(q_coeff) && std::isfinite(ent_coeff), ARL_E_ARG, "q_coeff and ent_coeff must be finite");
     const int64_t row_bytes = batch * 2 * half_stride * 4;
-    ARL_REQUIRE(!ac_overlap(dout, row_bytes, out, row_bytes) && !ac_overlap(dout, row_bytes, out_avg, row_bytes) &&
-                !ac_overlap(stats, batch * 20, out, row_bytes) && !ac_overlap(stats, batch * 20, out_avg, row_bytes) &&
-                !ac_overlap(stats, batch * 20, dout, row_bytes), ARL_E_ARG, "dout and stats must not overlap out, "
+    ARL_REQUIRE(!arl::overlap(dout, row_bytes, out, row_bytes) && !arl::overlap(dout, row_bytes, out_avg, row_bytes) &&
+                !arl::overlap(stats, batch * 20, out, row_bytes) && !arl::overlap(stats, batch * 20, out_avg, row_bytes) &&
+                !arl::overlap(stats, batch * 20, dout, row_bytes), ARL_E_ARG, "dout and stats must not overlap out, "
                 "out_avg or one another");
     ARL_REQUIRE(arl::aligned4(out) && arl::aligned4(out_avg) && arl::aligned4(old_prob) && arl::aligned4(qret) &&
                 arl::aligned4(idx_or_null) && arl::aligned4(dout) && arl::aligned4(stats), ARL_E_ALIGN,
@@ -335,7 +318,7 @@ extern "C" int arl_acer_avg_step(float* avg, const float* params, int64_t n, flo
     ARL_REQUIRE(avg && params, ARL_E_ARG, "null pointer");
     ARL_REQUIRE(alpha >= 0.f && alpha <= 1.f, ARL_E_ARG, "alpha must lie in [0, 1]");          // (a NaN fails)
     ARL_REQUIRE(n >= 1 && n <= INT32_MAX, ARL_E_RANGE, "1 <= n < 2^31");
-    ARL_REQUIRE(!ac_overlap(avg, n * 4, params, n * 4), ARL_E_ARG, "avg must not overlap params");
+    ARL_REQUIRE(!arl::overlap(avg, n * 4, params, n * 4), ARL_E_ARG, "avg must not overlap params");
     ARL_REQUIRE(arl::aligned4(avg) && arl::aligned4(params), ARL_E_ALIGN, "avg and params must be 4-byte aligned");
     const float beta = 1.f - alpha;
     const bool vec = arl::aligned16(avg) && arl::aligned16(params);
@@ -354,8 +337,8 @@ extern "C" int arl_gather_segments(const void* src, const int32_t* index, int64_
     ARL_REQUIRE(n_seg >= 1 && n_seg <= INT32_MAX && n_src_seg >= 1 && n_src_seg <= INT32_MAX, ARL_E_RANGE,
                 "1 <= n_seg, n_src_seg <= 2^31 - 1");
     ARL_REQUIRE(seg_bytes >= 1 && seg_bytes <= ((int64_t)1 << 31), ARL_E_RANGE, "1 <= seg_bytes <= 2^31");
-    ARL_REQUIRE(!ac_overlap(dst, n_seg * seg_bytes, src, n_src_seg * seg_bytes) &&
-                !ac_overlap(dst, n_seg * seg_bytes, index, n_seg * 4), ARL_E_ARG, "dst must not overlap src or index");
+    ARL_REQUIRE(!arl::overlap(dst, n_seg * seg_bytes, src, n_src_seg * seg_bytes) &&
+                !arl::overlap(dst, n_seg * seg_bytes, index, n_seg * 4), ARL_E_ARG, "dst must not overlap src or index");
     ARL_REQUIRE(arl::aligned4(index), ARL_E_ALIGN, "index must be 4-byte aligned");
     const bool vec = (seg_bytes & 15) == 0 && arl::aligned16(src) && arl::aligned16(dst);
     const int64_t items = vec ? seg_bytes >> 4 : seg_bytes;

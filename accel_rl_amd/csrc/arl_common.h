@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <cmath>
+
 #include "accel_rl_hip.h"
 #include "accel_rl_hip_dev.h"
 
@@ -25,6 +27,30 @@ inline int check_launch(const char* what) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+inline bool overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
+}
+inline bool unit_interval(double x) { return x >= 0.0 && x <= 1.0; }      // (a NaN fails both comparisons)
+inline bool finite_positive(double x) { return std::isfinite(x) && x > 0.0; }
+
+struct Span { const void* p; int64_t bytes; };
+
+// every non-null output against every input and every later output; false with the error set as "<fn>: .."
+inline bool check_disjoint(const char* fn, const Span* in, int n_in, const Span* out, int n_out) {
+    const char* clash = nullptr;
+    for (int o = 0; o < n_out && !clash; ++o) {
+        if (!out[o].p) continue;
+        for (int i = 0; i < n_in && !clash; ++i)
+            if (overlap(out[o].p, out[o].bytes, in[i].p, in[i].bytes)) clash = "an output must not overlap an input";
+        for (int k = o + 1; k < n_out && !clash; ++k)
+            if (out[k].p && overlap(out[o].p, out[o].bytes, out[k].p, out[k].bytes))
+                clash = "the outputs must not overlap one another";
+    }
+    if (clash) set_error("%s: %s", fn, clash);
+    return !clash;
+}
 
 // grid for a streaming kernel: enough blocks to fill 256 CUs x 8, never more than needed
 inline unsigned stream_grid(int64_t work_items, int per_block) {
@@ -57,6 +83,17 @@ struct CellFlags {
             return (code);                      \
         }                                       \
     } while (0)
+
+// Limits shared by the three per-env float64 scans (csrc/qlambda_scan.hip, csrc/vtrace_scan.hip, arl_acer_retrace_scan in
+// csrc/acer.hip; stated in accel_rl_hip.h): host-side comparisons before the launch.
+#define ARL_ENV_SCAN_SIZES(n_env, horizon)                                                                     \
+    do {                                                                                                       \
+        ARL_REQUIRE((n_env) >= 1 && (n_env) <= INT32_MAX, ARL_E_RANGE, "1 <= n_env <= 2^31 - 1");              \
+        ARL_REQUIRE((horizon) >= 1 && (horizon) <= 4096, ARL_E_RANGE, "1 <= horizon <= 4096");                 \
+    } while (0)
+#define ARL_ENV_SCAN_Q_STRIDE(q_stride, n_actions)                                                             \
+    ARL_REQUIRE((q_stride) >= (n_actions) && ((q_stride) & 3) == 0 && (q_stride) <= (1 << 20), ARL_E_RANGE,    \
+                "n_actions <= q_stride <= 2^20, q_stride % 4 == 0")
 
 // Limits shared by the six recurrent-cell entry points (csrc/lstm.hip, csrc/gru.hip; stated in accel_rl_hip.h):
 // host-side comparisons before the launch, no device work.

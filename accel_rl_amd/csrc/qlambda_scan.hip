@@ -10,7 +10,7 @@
 
 namespace {
 
-constexpr int QL_MAX_HORIZON = 4096, QL_MAX_ACTIONS = 64;
+constexpr int QL_MAX_ACTIONS = 64;
 
 __global__ __launch_bounds__(64) void qlambda_scan_kernel(const float* __restrict__ q, const float* __restrict__ q_last,
                                                           const float* __restrict__ rewards,
@@ -54,31 +54,23 @@ __global__ __launch_bounds__(64) void qlambda_scan_kernel(const float* __restric
     for (int t = lane; t < T; t += 64) returns[e * T + t] = rr[t];
 }
 
-bool ql_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
-}
-
 }  // namespace
 
 extern "C" int arl_qlambda_scan(const float* q, const float* q_last, const float* rewards, const uint8_t* dones,
                                 double discount, double lambda, int64_t n_env, int32_t horizon, int32_t n_actions,
                                 int32_t q_stride, float* returns, void* stream) {
     ARL_REQUIRE(q && q_last && rewards && dones && returns, ARL_E_ARG, "null pointer");
-    ARL_REQUIRE(n_env >= 1 && n_env <= INT32_MAX, ARL_E_RANGE, "1 <= n_env <= 2^31 - 1");
-    ARL_REQUIRE(horizon >= 1 && horizon <= QL_MAX_HORIZON, ARL_E_RANGE, "1 <= horizon <= 4096");
+    ARL_ENV_SCAN_SIZES(n_env, horizon);
     ARL_REQUIRE(n_actions >= 1 && n_actions <= QL_MAX_ACTIONS, ARL_E_RANGE, "1 <= n_actions <= 64");
-    ARL_REQUIRE(q_stride >= n_actions && (q_stride & 3) == 0 && q_stride <= (1 << 20), ARL_E_RANGE,
-                "n_actions <= q_stride <= 2^20, q_stride % 4 == 0");
-    ARL_REQUIRE(discount >= 0.0 && discount <= 1.0 && lambda >= 0.0 && lambda <= 1.0, ARL_E_ARG,
-                "discount and lambda must lie in [0, 1]");           // (a NaN fails both comparisons)
+    ARL_ENV_SCAN_Q_STRIDE(q_stride, n_actions);
+    ARL_REQUIRE(arl::unit_interval(discount) && arl::unit_interval(lambda), ARL_E_ARG,
+                "discount and lambda must lie in [0, 1]");
     ARL_REQUIRE(arl::aligned16(q) && arl::aligned16(q_last) && arl::aligned4(rewards) && arl::aligned4(returns),
                 ARL_E_ALIGN, "q and q_last 16-byte, rewards and returns 4-byte aligned");
     const int64_t steps = n_env * horizon;
-    ARL_REQUIRE(!ql_overlap(returns, steps * 4, q, steps * q_stride * 4) &&
-                !ql_overlap(returns, steps * 4, q_last, n_env * q_stride * 4) &&
-                !ql_overlap(returns, steps * 4, rewards, steps * 4) && !ql_overlap(returns, steps * 4, dones, steps),
-                ARL_E_ARG, "returns must not overlap an input");
+    const arl::Span in[4] = {{q, steps * q_stride * 4}, {q_last, n_env * q_stride * 4}, {rewards, steps * 4}, {dones, steps}};
+    const arl::Span out[1] = {{returns, steps * 4}};
+    if (!arl::check_disjoint(__func__, in, 4, out, 1)) return ARL_E_ARG;
     hipLaunchKernelGGL(qlambda_scan_kernel, dim3((unsigned)n_env), dim3(64), (size_t)horizon * 9 + 16, (hipStream_t)stream,
                        q, q_last, rewards, dones, discount, lambda, (int)horizon, (int)n_actions, (int)q_stride, returns);
     return arl::check_launch("qlambda_scan_kernel");

@@ -11,11 +11,9 @@
 // then store the chunk's results together.  An associative scan would change the rounding; none is used.
 #include "arl_common.h"
 
-#include <math.h>
-
 namespace {
 
-constexpr int VT_MAX_HORIZON = 4096, VT_CHUNK = 1024;
+constexpr int VT_CHUNK = 1024;
 
 __global__ __launch_bounds__(64) void vtrace_scan_kernel(
     const float* __restrict__ prob, const float* __restrict__ old_prob, const uint8_t* __restrict__ actions,
@@ -80,14 +78,6 @@ __global__ __launch_bounds__(64) void vtrace_scan_kernel(
     }
 }
 
-bool vt_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
-}
-
-bool vt_unit(double x) { return x >= 0.0 && x <= 1.0; }               // (a NaN fails both comparisons)
-bool vt_bar(double x) { return isfinite(x) && x > 0.0; }
-
 }  // namespace
 
 extern "C" int arl_vtrace_scan(const float* prob, const float* old_prob, const uint8_t* actions, const float* values,
@@ -97,27 +87,18 @@ extern "C" int arl_vtrace_scan(const float* prob, const float* old_prob, const u
                                float* stats_or_null, void* stream) {
     ARL_REQUIRE(prob && old_prob && actions && values && last_values && rewards && dones && returns && advantages,
                 ARL_E_ARG, "null pointer");
-    ARL_REQUIRE(n_env >= 1 && n_env <= INT32_MAX, ARL_E_RANGE, "1 <= n_env <= 2^31 - 1");
-    ARL_REQUIRE(horizon >= 1 && horizon <= VT_MAX_HORIZON, ARL_E_RANGE, "1 <= horizon <= 4096");
+    ARL_ENV_SCAN_SIZES(n_env, horizon);
     ARL_REQUIRE(n_actions >= 1 && n_actions <= ARL_MAX_ACTIONS, ARL_E_RANGE, "1 <= n_actions <= 18");
-    ARL_REQUIRE(vt_unit(discount) && vt_unit(lambda), ARL_E_ARG, "discount and lambda must lie in [0, 1]");
-    ARL_REQUIRE(vt_bar(rho_bar) && vt_bar(c_bar) && vt_bar(pg_rho_bar), ARL_E_ARG,
-                "rho_bar, c_bar and pg_rho_bar must be finite and > 0");
+    ARL_REQUIRE(arl::unit_interval(discount) && arl::unit_interval(lambda), ARL_E_ARG,
+                "discount and lambda must lie in [0, 1]");
+    ARL_REQUIRE(arl::finite_positive(rho_bar) && arl::finite_positive(c_bar) && arl::finite_positive(pg_rho_bar),
+                ARL_E_ARG, "rho_bar, c_bar and pg_rho_bar must be finite and > 0");
     const int64_t steps = n_env * horizon;
-    const struct { const void* p; int64_t bytes; } in[7] = {
+    const arl::Span in[7] = {
         {prob, steps * n_actions * 4}, {old_prob, steps * n_actions * 4}, {actions, steps}, {values, steps * 4},
         {last_values, n_env * 4}, {rewards, steps * 4}, {dones, steps}};
-    const struct { const void* p; int64_t bytes; } out[3] = {
-        {returns, steps * 4}, {advantages, steps * 4}, {stats_or_null, n_env * 8}};
-    for (int o = 0; o < 3; ++o) {
-        if (!out[o].p) continue;
-        for (int i = 0; i < 7; ++i)
-            ARL_REQUIRE(!vt_overlap(out[o].p, out[o].bytes, in[i].p, in[i].bytes), ARL_E_ARG,
-                        "an output must not overlap an input");
-        for (int k = o + 1; k < 3; ++k)
-            ARL_REQUIRE(!out[k].p || !vt_overlap(out[o].p, out[o].bytes, out[k].p, out[k].bytes), ARL_E_ARG,
-                        "the outputs must not overlap one another");
-    }
+    const arl::Span out[3] = {{returns, steps * 4}, {advantages, steps * 4}, {stats_or_null, n_env * 8}};
+    if (!arl::check_disjoint(__func__, in, 7, out, 3)) return ARL_E_ARG;
     ARL_REQUIRE(arl::aligned4(prob) && arl::aligned4(old_prob) && arl::aligned4(values) && arl::aligned4(last_values) &&
                 arl::aligned4(rewards) && arl::aligned4(returns) && arl::aligned4(advantages) &&
                 arl::aligned4(stats_or_null), ARL_E_ALIGN, "every float pointer must be 4-byte aligned");

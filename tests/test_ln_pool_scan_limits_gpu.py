@@ -1,6 +1,7 @@
 """The LayerNorm, pooling and return-scan kernels at the limits their entry points accept (csrc/layernorm.hip,
-csrc/qlambda_scan.hip, csrc/vtrace_scan.hip, csrc/resnet.hip).  The feature tests (test_pqn_gpu.py, test_vtrace_gpu.py,
-test_resnet_gpu.py) stay as they are; this file runs the shapes they leave out:
+csrc/qlambda_scan.hip, csrc/vtrace_scan.hip, the Retrace scan of csrc/acer.hip, csrc/resnet.hip).  The feature tests
+(test_pqn_gpu.py, test_vtrace_gpu.py, test_acer_gpu.py, test_resnet_gpu.py) stay as they are; this file runs the shapes
+they leave out:
 
 - LayerNorm: widths just past every dispatch boundary and with dead or half-dead float4 slots (8, 36, 68, 256, 260, 516,
   768, 1020), the forward's second (ragged) trip over 2048 blocks at every LPR, both backward variants, dz over dy and
@@ -9,8 +10,8 @@ test_resnet_gpu.py) stay as they are; this file runs the shapes they leave out:
   partials folded by noisy_ref.fold_f32; the first-order bounds of DESIGN.md 22 are asserted alongside;
 - the Q(lambda) scan at horizons round the lane wrap up to the limit of 4096 (36 KiB of LDS), action counts that leave
   one to three entries of the last float4 live, the action and stride limits, a block index above 65535;
-- the V-trace scan at horizons with a ragged first chunk, dones and clipped ratios planted on both sides of every chunk
-  edge, a block index above 65535;
+- the V-trace and the Retrace scan at horizons with a ragged first chunk, dones and clipped ratios planted on both sides
+  of every chunk edge, a block index above 65535;
 - the residual network's four grid-stride kernels past the wrap at 2048 x 256 threads, and at the channel limit.
 
 Out of scope: the 64-bit branch of split_index and rows * width >= 2^31 need buffers of tens of GiB; pooling windows made
@@ -19,11 +20,13 @@ import numpy as np
 import pytest
 import torch
 
+import acer_ref as ar
 import ln_ref as lr
 import pqn_ref as pr
 import resnet_ref as rr
 import vtrace_ref as vr
 from ln_ref import EPS, LN_ROWS, LN_SECOND_TRIP, LN_WIDTHS
+from test_acer_gpu import _scan as rt_scan
 from test_pqn_gpu import _scan_case as ql_case
 from test_resnet_host import pool_input
 from test_vtrace_gpu import KEYS, _launch as vt_launch, _on_device as vt_on_device, _scan_case as vt_case
@@ -256,15 +259,19 @@ def test_qlambda_scan_block_index_above_65535(L):
 
 # ---- V-trace scan ------------------------------------------------------------------------------------------------------
 
-VT_CHUNK = 1024
+CHUNK = 1024                    # VT_CHUNK of csrc/vtrace_scan.hip and AC_CHUNK of csrc/acer.hip: change it with them
+
+
+def _chunk_edges(horizon):
+    """The walk comes from the end: step k closes a chunk, step k - 1 opens the next, k = T - 1024, T - 2048, .."""
+    return list(range(horizon - CHUNK, 0, -CHUNK))
 
 
 def _vt_inputs(horizon, n_act):
-    """test_vtrace_gpu._scan_case for two envs, and on both sides of every chunk edge k = T - 1024, T - 2048, .. (the walk
-    comes from the end: step k closes a chunk, step k - 1 opens the next): a done at k - 1 in env 0, a done at k in env 1,
-    and in env 1 a ratio of 8 (above every rho_bar used) at k - 1 and at k."""
+    """test_vtrace_gpu._scan_case for two envs, and on both sides of every chunk edge k (_chunk_edges): a done at k - 1
+    in env 0, a done at k in env 1, and in env 1 a ratio of 8 (above every rho_bar used) at k - 1 and at k."""
     c = vt_case(2, horizon, n_act)
-    edges = list(range(horizon - VT_CHUNK, 0, -VT_CHUNK))
+    edges = _chunk_edges(horizon)
     for k in edges:
         c["dones"][0, k - 1] = 1
         c["dones"][0, k] = 0
@@ -282,7 +289,7 @@ def test_vtrace_scan_across_ragged_chunks_and_planted_edges(L, horizon, n_act):
     """T % 1024 != 0 leaves a ragged chunk at lo = 0; acc_next, vs_next, v_next, ratio_sum and n_clipped cross every edge
     with a done on either side of it."""
     c, edges = _vt_inputs(horizon, n_act)
-    assert len(edges) == (horizon - 1) // VT_CHUNK
+    assert len(edges) == (horizon - 1) // CHUNK
     dc = vt_on_device(c)
     ratio = vr.ratios64(c["prob"], c["old_prob"], c["actions"])
     for k in edges:
@@ -317,6 +324,49 @@ def test_vtrace_scan_block_index_above_65535(L):
             _same_bits(got[0], vs.astype(np.float32), "returns")
             _same_bits(got[1], adv.astype(np.float32), "advantages")
             _same_bits(got[2], stats, "stats")
+
+
+# ---- Retrace scan ------------------------------------------------------------------------------------------------------
+
+def _rt_want(c, lam):
+    return ar.retrace(c["prob"], c["prob_last"], c["q"], c["q_last"], c["old_prob"], c["actions"], c["rewards"],
+                      c["dones"], 0.99, lam, c["n_env"], c["horizon"])
+
+
+def _rt_same(got, want, what):
+    for g, w, name in zip(got, want, ("qret", "v", "stats")):
+        _same_bits(g, w, (name,) + what)
+
+
+@pytest.mark.parametrize("horizon,n_act", [(1023, 18), (1025, 18), (2049, 18), (1025, 1)])
+def test_retrace_scan_across_ragged_chunks_and_planted_edges(L, horizon, n_act):
+    """acer_ref.scan_case for two envs (action bytes of 255 among them), and on both sides of every chunk edge k: a done
+    at k - 1 in env 0, a done at k in env 1, and in env 1 a rho of about 8 at k - 1 and at k, so that qret, rho_sum and
+    n_above cross every edge with a done on either side of it."""
+    c = ar.scan_case(horizon + n_act, 2, horizon, n_act, 64, act255=True)
+    edges = _chunk_edges(horizon)
+    assert len(edges) == (horizon - 1) // CHUNK
+    dones, acts = c["dones"].reshape(2, horizon), c["actions"].reshape(2, horizon)
+    prob, old = c["prob"].reshape(2, horizon, n_act), c["old_prob"].reshape(2, horizon, n_act)
+    for k in edges:
+        dones[0, k - 1], dones[0, k], dones[1, k - 1], dones[1, k] = 1, 0, 0, 1
+        for t in (k - 1, k):
+            a = min(int(acts[1, t]), n_act - 1)
+            assert prob[1, t, a] >= 1e-3
+            old[1, t, a] = prob[1, t, a] / np.float32(8)
+    for lam in (0.0, 0.95, 1.0):
+        want = _rt_want(c, lam)
+        assert np.isfinite(want[0]).all() and want[2][1, 1] >= 2 * len(edges)
+        _rt_same(rt_scan(L, c, lam), want, (horizon, n_act, lam))
+    if horizon == 2049:                                         # determinism: a second launch, the same bits
+        _rt_same(rt_scan(L, c, 0.95), rt_scan(L, c, 0.95), ("two launches",))
+
+
+def test_retrace_scan_block_index_above_65535(L):
+    c = ar.scan_case(11, 70001, 1, 6, 8, mu_zero=True, act255=True)
+    c["dones"][::3] = 1
+    for lam in (0.0, 1.0):
+        _rt_same(rt_scan(L, c, lam), _rt_want(c, lam), (70001, lam))
 
 
 # ---- the residual network's streaming kernels --------------------------------------------------------------------------

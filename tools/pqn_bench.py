@@ -1,5 +1,8 @@
 """Measurements behind DESIGN.md 22 (PQN), one MI355X, one process; prints one JSON line per part.
 
+  scan    arl_qlambda_scan at 128 x 32 (PQN's own batch), 1 024 x 128 and 16 384 x 32 (more blocks than stay resident at
+          once), 18 actions at a stride of 32: a captured graph of 50 back-to-back launches, device events around 4
+          replays, 15 windows; median / min / max per launch
   ln      arl_ln_relu_fwd / arl_ln_relu_bwd at the three training shapes next to arl_copy_bytes (a 16-byte-per-lane copy)
           of the SAME bytes: every variant a captured graph of 20 launches, the variants taking turns inside one process;
           median / min / p90 per launch over the rounds, and the kernels' rate as a share of the copy's
@@ -8,7 +11,7 @@
           captured graph and taking turns; library entry-point calls per update counted on the eager call
   steps   env-steps/s of whole PQN iterations (rollout + returns + 2 epochs x 32 minibatches), 128 envs x horizon 32
 
-usage: python tools/pqn_bench.py [ln] [update] [steps]"""
+usage: python tools/pqn_bench.py [scan] [ln] [update] [steps]"""
 import json
 import os
 import sys
@@ -49,6 +52,35 @@ def _turns(variants, rounds=40, inner=20):
             b.synchronize()
             out[name].append(a.elapsed_time(b) * 1e3 / inner)
     return {k: _stats(v) for k, v in out.items()}
+
+
+def bench_scan(per_graph=50, replays=4, windows=15, n_act=18, stride=32):
+    out = dict()
+    for n_env, horizon in ((128, 32), (1024, 128), (16384, 32)):
+        steps = n_env * horizon
+        q, q_last = torch.randn(steps, stride, device=DEV), torch.randn(n_env, stride, device=DEV)
+        rewards, returns = torch.randn(steps, device=DEV), torch.zeros(steps, device=DEV)
+        dones = (torch.rand(steps, device=DEV) < 0.02).to(torch.uint8)
+
+        def many():
+            for _ in range(per_graph):
+                _lib.qlambda_scan(q, q_last, rewards, dones, 0.99, 0.65, n_env, horizon, n_act, returns)
+        g = _graph_of(many)
+        for _ in range(3):
+            g.replay()
+        torch.cuda.synchronize()
+        us = []
+        for _ in range(windows):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(replays):
+                g.replay()
+            b.record()
+            b.synchronize()
+            us.append(a.elapsed_time(b) * 1e3 / (per_graph * replays))
+        out["%dx%d" % (n_env, horizon)] = dict(median_us=round(float(np.median(us)), 3), min_us=round(min(us), 3),
+                                               max_us=round(max(us), 3))
+    print(json.dumps(dict(part="scan", n_actions=n_act, q_stride=stride, us_per_launch=out)), flush=True)
 
 
 def bench_ln(inner=20):
@@ -206,8 +238,10 @@ def bench_steps(spec=1, n_env=128, horizon=32, warmup=6, steps=20):
 
 
 if __name__ == "__main__":
-    parts = sys.argv[1:] or ["ln", "update", "steps"]
+    parts = sys.argv[1:] or ["scan", "ln", "update", "steps"]
     _lib.load()
+    if "scan" in parts:
+        bench_scan()
     if "ln" in parts:
         bench_ln()
     if "update" in parts:
