@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libaccel_rl_hip.so")
 SOURCES = ["mfma_conv_p1.hip", "mfma_conv_p2.hip", "mfma_conv_p3.hip", "mfma_conv_p4.hip", "mfma_conv_p5.hip", "mfma_conv_p6.hip",
            "mfma_conv_p7.hip", "mfma_conv_p8.hip", "mfma_conv.hip", "img_conv.hip", "batch_ops.hip", "scan.hip", "env.hip", "serve_step.hip", "optim.hip", "learner.hip", "replay.hip",
            "dqn.hip", "lstm.hip", "gru.hip", "noisy.hip", "traj.hip", "handover.hip", "iqn.hip", "fqf.hip", "layernorm.hip", "qlambda_scan.hip", "sac.hip",
-           "vtrace_scan.hip", "resnet.hip", "ppg.hip", "r2d2.hip", "vmpo.hip", "rnd.hip", "acer.hip"]
+           "vtrace_scan.hip", "resnet.hip", "ppg.hip", "r2d2.hip", "vmpo.hip", "rnd.hip", "acer.hip", "popart.hip"]
 ARCH = "gfx950"
 
 

@@ -20,6 +20,7 @@ PPG_POLICY, PPG_AUX = 0, 1                                # ARL_PPG_*: arl_ppg_h
 OPT_ADAM, OPT_RMSPROP = 0, 1
 VMPO_MAX_ROWS = 65536                                     # ARL_VMPO_MAX_ROWS: rows of one arl_vmpo_weights launch
 RND_MAX_ROWS, RND_MIX_MAX_ENVS, RND_MIX_MAX_ROWS = 1 << 24, 1 << 20, 1 << 22   # ARL_RND_MAX_ROWS, ARL_RND_MIX_MAX_*
+POPART_MAX_ROWS, POPART_MAX_HID = 1 << 22, 1 << 16        # ARL_POPART_MAX_ROWS, ARL_POPART_MAX_HID
 MAX_ACTIONS = 18
 REPLAY_MAX_HORIZON = 16
 RAW_H, RAW_W, OBS_H, OBS_W = 210, 160, 104, 80
@@ -284,6 +285,8 @@ _SIGNATURES = {
     "arl_rnd_obs_prepare": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "arl_rnd_error": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "arl_rnd_reward_mix": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _f64, _f64, _f64, _vp, _vp, _vp, _vp]),
+    "arl_popart_denorm": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "arl_popart_step": (_i32, [_vp, _vp, _vp, _i64, _f64, _f64, _f64, _vp, _vp, _vp, _i32, _vp, _vp]),
     "arl_acer_retrace_scan": (_i32, [_vp] * 4 + [_i32, _vp, _vp, _vp, _vp, _f64, _f64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "arl_acer_loss": (_i32, [_vp] * 6 + [_i64, _i32, _i32, _f64, _f64, _f64, _f64, _vp, _vp, _vp]),
     "arl_acer_avg_step": (_i32, [_vp, _vp, _i64, _f32, _vp]),
@@ -1672,6 +1675,39 @@ def rnd_reward_mix(err, r_ext, n_env, horizon, rho, moments, gamma_int, c_ext, c
     _check(load().arl_rnd_reward_mix(ptr(err), ptr(r_ext), n_env, horizon, ptr(rho), ptr(moments), float(gamma_int),
                                      float(c_ext), float(c_int), ptr(r_mix), ptr(diag2), ptr(workspace),
                                      stream_ptr(stream)), "arl_rnd_reward_mix")
+
+
+# ---------------------------------------------------------------------------
+# PopArt: denormalised values for the scans, the statistics / head / target step (csrc/popart.hip)
+# ---------------------------------------------------------------------------
+
+def popart_denorm(value_n, last_n, stats, value, last_value, stream=None):
+    """value = sigma * value_n + mu and last_value likewise from last_n, under stats f64[4] = (mu, nu, sigma, n_updates)."""
+    for t, n in ((value_n, "value_n"), (last_n, "last_n"), (value, "value"), (last_value, "last_value")):
+        _want(t, torch.float32, n)
+    _want(stats, torch.float64, "stats")
+    rows, n_last = value_n.numel(), last_n.numel()
+    assert value.numel() == rows and last_value.numel() == n_last and stats.numel() == 4, "popart_denorm sizes"
+    _check(load().arl_popart_denorm(ptr(value_n), rows, ptr(last_n), n_last, ptr(stats), ptr(value), ptr(last_value),
+                                    stream_ptr(stream)), "arl_popart_denorm")
+
+
+def popart_step(returns, advantages, valids, beta, sigma_min, sigma_max, stats, w_value, b_value, diag2, stream=None):
+    """One launch: the batch's moments -> stats -> the value row / bias rewritten (outputs preserved) -> returns (and
+    advantages, unless None) normalised in place; diag2 = (mu', sigma')."""
+    for t, n in ((returns, "returns"), (w_value, "w_value"), (b_value, "b_value"), (diag2, "diag2")):
+        _want(t, torch.float32, n)
+    _want(stats, torch.float64, "stats")
+    rows = returns.numel()
+    if advantages is not None:
+        _want(advantages, torch.float32, "advantages")
+    if valids is not None:
+        _want(valids, torch.int8, "valids")
+    assert (advantages is None or advantages.numel() == rows) and (valids is None or valids.numel() == rows) and \
+        stats.numel() == 4 and b_value.numel() == 1 and diag2.numel() >= 2, "popart_step sizes"
+    _check(load().arl_popart_step(ptr(returns), ptr(advantages), ptr(valids), rows, float(beta), float(sigma_min),
+                                  float(sigma_max), ptr(stats), ptr(w_value), ptr(b_value), w_value.numel(), ptr(diag2),
+                                  stream_ptr(stream)), "arl_popart_step")
 
 
 # ---------------------------------------------------------------------------

@@ -280,7 +280,7 @@ class AdvActorCriticBase(RLAlgorithm):
         opt = self._opt_buf
         last_values = self.policy.value(samples_data["extra_observations"]).contiguous()   # :112
         r, d = samples_data["rewards"], samples_data["dones"]
-        v = samples_data["agent_infos"]["value"]
+        v, last_values = self._scan_values(samples_data["agent_infos"]["value"], last_values)
         if self.gae_lambda == 1:                                    # :115-121
             _lib.nstep_return(r, d, v, last_values, self.discount, n, t,
                               opt["returns"], opt["advantages"], promo=self._promo)
@@ -295,6 +295,11 @@ class AdvActorCriticBase(RLAlgorithm):
         if self.standardize_adv:                                     # :136-143
             _lib.standardize(opt["advantages"], valids, self._std_ws, 1e-6)
         return opt
+
+    def _scan_values(self, values, last_values):
+        """The recorded and the bootstrap values as the return / advantage scans read them: the network's own outputs
+        (a mixin whose network puts out something else -- PopArt's normalised value -- maps them here)."""
+        return values, last_values
 
     def prep_opt_inputs(self, itr, samples_data, opt_data):
         """reference: aac_base.py:147-170"""

@@ -102,6 +102,7 @@ class IMPALA(AdvActorCriticBase):
         s, opt = self._samples, self._opt_buf
         prob, value = self.policy.prob_value_rows(s["observations"], self.rows_per_pass, tag="vt_rows")
         _, last_value = self.policy.prob_value_rows(s["extra_observations"], self.rows_per_pass, tag="vt_last")
+        value, last_value = self._scan_values(value, last_value)
         _lib.vtrace_scan(prob, s["agent_infos"]["prob"], s["actions"], value, last_value, s["rewards"], s["dones"],
                          self.discount, self.vtrace_lambda, self.rho_bar, self.c_bar, self.pg_rho_bar, self._n_env,
                          self._horizon, opt["returns"], opt["advantages"], stats=self._vt_stats)

@@ -264,6 +264,17 @@ class AtariCnnPolicy(object):
     def _head_internal_shapes(self, fan, n_act):
         return [(n_act + 1, fan), (n_act + 1,)]
 
+    def value_head(self):
+        """(w_row f32[hid], b f32[1]): the value row of W_head and the value bias, as views into flat_params (row n_act
+        starts n_act * hid floats into W_head: 4-byte aligned, no more).  A writer says so (note_params_changed).  Only
+        for this class's output layers: a subclass that lays them out otherwise has no such row to hand out."""
+        if type(self)._head_internal_shapes is not AtariCnnPolicy._head_internal_shapes:
+            raise NotImplementedError("%s: its output layers are not AtariCnnPolicy's W_head[(A + 1), hid]; there is no "
+                                      "value row to hand out" % type(self).__name__)
+        a, (w, b) = self.n_act, self._w[self._k_head:self._k_head + 2]
+        hid = w.numel() // (a + 1)
+        return w[a * hid:(a + 1) * hid], b[a:a + 1]
+
     def _head_to_reference(self, wh, bh):
         a = self.n_act
         return [wh[:a].T, bh[:a], wh[a:].T, bh[a:]]

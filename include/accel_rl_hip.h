@@ -652,6 +652,51 @@ int arl_rnd_reward_mix(const float* err, const float* r_ext, int64_t n_env, int3
                        double gamma_int, double c_ext, double c_int, float* r_mix, float* diag2, void* workspace,
                        void* stream);
 
+/* PopArt (adaptive value normalisation, single task; csrc/popart.hip): what an actor-critic whose value output is a
+ * NORMALISED value n adds between its rollout and its optimiser step.  The unnormalised value of a state is sigma n + mu.
+ * float64 on the promoted inputs, every output rounded once, no float atomics, no process-wide state; nothing
+ * synchronises with the host.  A refused call launches nothing and writes nothing.
+ *
+ * stats f64[4] = (mu, nu, sigma, n_updates): first moment, second moment, the clamped standard deviation, the number of
+ *   updates applied; lives on the device, carried across calls, starts as (0, 1, 1, 0); 8-byte aligned (ARL_E_ALIGN).
+ *
+ * arl_popart_denorm: value[i] = (float) (sigma * (double) value_n[i] + mu) for i < rows and last_value[k] likewise from
+ *   last_n[k] for k < n_last -- one streaming launch over both arrays; the statistics are only read.
+ *   1 <= rows <= ARL_POPART_MAX_ROWS, 1 <= n_last <= rows (ARL_E_RANGE); a NULL pointer, or an output that overlaps an
+ *   input or the other output: ARL_E_ARG (the recorded values are another owner's buffer and are never written); float
+ *   pointers not 4-byte aligned: ARL_E_ALIGN.
+ *
+ * arl_popart_step: returns f32[rows] (the regression targets G, unnormalised), advantages f32[rows] or NULL, valids
+ *   i8[rows] or NULL (every row counts); w_value f32[hid] and b_value f32[1] are the value row and the value bias of the
+ *   output layer (row A of W_head[(A + 1)][hid] starts A * hid floats in: 4-byte alignment is all that is asked).  One
+ *   workgroup of 1 024, in this order:
+ *       1. cnt = sum_i v_i, S1 = sum_i v_i G_i, S2 = sum_i v_i G_i G_i with v_i = (valids[i] != 0) and G_i promoted --
+ *          rows with v_i = 0 are skipped, not multiplied, so what they hold does not matter; every sum: thread t adds
+ *          i = t, t + 1 024, ... ascending, a wave adds by halving shuffles (offsets 32 .. 1), the 16 waves add in wave
+ *          order;   m1 = S1 / cnt,  m2 = S2 / cnt
+ *       2. if cnt > 0 and m1 and m2 are finite:
+ *              mu' = (1 - beta) * mu + beta * m1;   nu' = (1 - beta) * nu + beta * m2;
+ *              sigma' = min(max(sqrt(max(nu' - mu' * mu', 0)), sigma_min), sigma_max);   n_updates' = n_updates + 1
+ *          else stats, w_value and b_value keep their bits, step 3 is skipped and step 4 runs with mu' = mu, sigma' = sigma
+ *       3. ratio = sigma / sigma' (one division);   w_value[j] = (float) ((double) w_value[j] * ratio), j < hid;
+ *          b_value[0] = (float) (((sigma * (double) b_value[0] + mu) - mu') / sigma')
+ *          -- so sigma' n' + mu' = sigma n + mu for every hidden row, up to one float32 rounding of each weight
+ *       4. returns[i] = (float) (((double) G_i - mu') / sigma');  advantages[i] = (float) ((double) advantages[i] / sigma');
+ *          rows with v_i = 0 are written 0 in both
+ *       diag2 = ((float) mu', (float) sigma')
+ *   beta = 0 with stats (0, 1, 1, .) is the identity on every array (a -0.0 bias aside).  No debiasing of the moments.
+ *   1 <= rows <= ARL_POPART_MAX_ROWS (2^22: 4 096 rows per thread -- past that a single workgroup is no longer the
+ *   latency case this is written for), 1 <= hid <= ARL_POPART_MAX_HID (ARL_E_RANGE); ARL_E_ARG: a NULL returns, stats,
+ *   w_value, b_value or diag2, beta outside [0, 1] or NaN, sigma_min or sigma_max not finite, sigma_min <= 0, sigma_min >
+ *   sigma_max, advantages overlapping returns; float pointers not 4-byte, stats not 8-byte aligned: ARL_E_ALIGN.       */
+#define ARL_POPART_MAX_ROWS 4194304
+#define ARL_POPART_MAX_HID  65536
+int arl_popart_denorm(const float* value_n, int64_t rows, const float* last_n, int64_t n_last, const double* stats,
+                      float* value, float* last_value, void* stream);
+int arl_popart_step(float* returns, float* advantages_or_null, const int8_t* valids_or_null, int64_t rows, double beta,
+                    double sigma_min, double sigma_max, double* stats, float* w_value, float* b_value, int32_t hid,
+                    float* diag2, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * The policy network's dense contractions on the matrix cores (fp32 MFMA)
  * ------------------------------------------------------------------------- */
