@@ -213,6 +213,13 @@ _SIGNATURES = {
                                         C.POINTER(ArlFoldItem), _vp, C.POINTER(ArlFoldItem), C.POINTER(ArlCorunJob),
                                         C.POINTER(_i32), C.POINTER(ArlWgradPlan), _vp]),
     "arl_conv2d_bwd_weight_group": (_i32, [C.POINTER(ArlWgradPlan), _i32, _vp]),
+    "arl_conv2d_fwd_bits": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _i32, _vp, _vp]),
+    "arl_conv2d_u8_fwd_bits": (_i32, [_vp, _i64, _vp, _f32, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _i32, _vp]),
+    "arl_conv2d_bwd_data_bits": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), C.POINTER(ArlCorunJob),
+                                        C.POINTER(_i32), _vp]),
+    "arl_conv2d_bwd_pair_bits": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _vp, _i64,
+                                        C.POINTER(ArlFoldItem), _vp, C.POINTER(ArlFoldItem), C.POINTER(ArlCorunJob),
+                                        C.POINTER(_i32), C.POINTER(ArlWgradPlan), _vp]),
     "arl_relu_bwd_bias_parts": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, C.POINTER(ArlFoldItem), _vp]),
     "arl_replay_append": (_i32, [C.POINTER(ArlReplay), _vp, _vp, _vp, _vp, _i32, _i32, _f64, _i32, _vp]),
     "arl_replay_extract": (_i32, [C.POINTER(ArlReplay), _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -793,14 +800,36 @@ def conv_workspace(device):
     return torch.empty(load().arl_conv_workspace_bytes() // 4, dtype=torch.float32, device=device)
 
 
-def conv2d_fwd(x, w, bias, y, geom, relu, workspace, stream=None):
-    """y[B,Ho,Wo,K] = act(conv(x[B,H,W,C], w[K,kh,kw,C]) + bias); all fp32 contiguous memory."""
+def relu_bits_shape(rows, channels):
+    """Shape of the i32 tensor that holds an f32[rows][channels] activation's rectifier mask as bits (32 channels per
+    word, bit c % 32 of word c // 32 = y[row][c] > 0; accel_rl_hip.h: arl_conv2d_fwd_bits)."""
+    assert channels % 32 == 0, "rectifier bits need a multiple of 32 channels"
+    return (rows, channels // 32)
+
+
+def _want_bits(bits, n_values, name):
+    """A rectifier-bits tensor for n_values activations (None passes).  Its channel count and alignment are the library's
+    to check: it refuses, with its own error codes, what it cannot serve."""
+    if bits is not None:
+        _want(bits, torch.int32, name)
+        assert bits.numel() * 32 >= n_values, name + " size"
+
+
+def conv2d_fwd(x, w, bias, y, geom, relu, workspace, stream=None, y_bits=None):
+    """y[B,Ho,Wo,K] = act(conv(x[B,H,W,C], w[K,kh,kw,C]) + bias); all fp32 contiguous memory.
+    y_bits (i32, relu_bits_shape): the launch also writes y's rectifier mask as bits."""
     for t, n in ((x, "x"), (w, "w"), (y, "y")):
         _want(t, torch.float32, n)
     ho, wo = conv_out_hw(geom)
     assert x.numel() == geom.batch * geom.in_h * geom.in_w * geom.in_c, "x size"
     assert w.numel() == geom.out_c * geom.kh * geom.kw * geom.in_c, "w size"
     assert y.numel() == geom.batch * ho * wo * geom.out_c, "y size"
+    if y_bits is not None:
+        _want_bits(y_bits, y.numel(), "y_bits")
+        _check(load().arl_conv2d_fwd_bits(x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(),
+                                          y.data_ptr(), y_bits.data_ptr(), C.byref(geom), int(bool(relu)),
+                                          ptr(workspace), stream_ptr(stream)), "arl_conv2d_fwd_bits")
+        return
     _check(load().arl_conv2d_fwd(x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(),
                                  y.data_ptr(), C.byref(geom), int(bool(relu)), ptr(workspace),
                                  stream_ptr(stream)), "arl_conv2d_fwd")
@@ -845,12 +874,19 @@ def _u8_rows(obs, idx, geom):
         assert obs.shape[0] == geom.batch, "obs rows"
 
 
-def conv2d_u8_fwd(obs, idx, scale, w, bias, y, geom, relu, stream=None):
-    """y[B,Ho,Wo,K] = act(conv(float(obs[idx]) * scale, w[K,C,kh,kw]) + bias), obs u8[n,C,H,W] read in place."""
+def conv2d_u8_fwd(obs, idx, scale, w, bias, y, geom, relu, stream=None, y_bits=None):
+    """y[B,Ho,Wo,K] = act(conv(float(obs[idx]) * scale, w[K,C,kh,kw]) + bias), obs u8[n,C,H,W] read in place.
+    y_bits: as conv2d_fwd."""
     _u8_rows(obs, idx, geom)
     ho, wo = conv_out_hw(geom)
     assert w.numel() == geom.out_c * geom.kh * geom.kw * geom.in_c, "w size"
     assert y.numel() == geom.batch * ho * wo * geom.out_c, "y size"
+    if y_bits is not None:
+        _want_bits(y_bits, y.numel(), "y_bits")
+        _check(load().arl_conv2d_u8_fwd_bits(obs.data_ptr(), obs.shape[0], ptr(idx), float(scale), w.data_ptr(), ptr(bias),
+                                             y.data_ptr(), y_bits.data_ptr(), C.byref(geom), int(bool(relu)),
+                                             stream_ptr(stream)), "arl_conv2d_u8_fwd_bits")
+        return
     _check(load().arl_conv2d_u8_fwd(obs.data_ptr(), obs.shape[0], ptr(idx), float(scale), w.data_ptr(), ptr(bias),
                                     y.data_ptr(), C.byref(geom), int(bool(relu)), stream_ptr(stream)),
            "arl_conv2d_u8_fwd")
@@ -868,14 +904,21 @@ def conv2d_dgrad_weights(layers, stream=None):
     _check(load().arl_conv2d_dgrad_weights(items, len(layers), stream_ptr(stream)), "arl_conv2d_dgrad_weights")
 
 
-def conv2d_bwd_data(dy, w, mask, dx, geom, stream=None, corun=None, wt=None):
+def conv2d_bwd_data(dy, w, mask, dx, geom, stream=None, corun=None, wt=None, mask_bits=None):
     """corun: an ArlCorunJob the launch may carry; returns True if it did (else the caller runs it: corun_job_run).
-    wt: conv2d_dgrad_weights' copy of w (same results; the split kernels read it instead of w)."""
+    wt: conv2d_dgrad_weights' copy of w (same results; the split kernels read it instead of w).
+    mask_bits: the mask's rectifier bits from the forward's y_bits (same results; read instead of the floats)."""
     ho, wo = conv_out_hw(geom)
     assert dy.numel() == geom.batch * ho * wo * geom.out_c, "dy size"
     assert dx.numel() == geom.batch * geom.in_h * geom.in_w * geom.in_c, "dx size"
     assert mask is None or mask.numel() == dx.numel()
     taken = _i32(0)
+    if mask_bits is not None:
+        _want_bits(mask_bits, dx.numel(), "mask_bits")
+        _check(load().arl_conv2d_bwd_data_bits(dy.data_ptr(), w.data_ptr(), ptr(wt), ptr(mask), mask_bits.data_ptr(),
+                                               dx.data_ptr(), C.byref(geom), None if corun is None else C.byref(corun),
+                                               C.byref(taken), stream_ptr(stream)), "arl_conv2d_bwd_data_bits")
+        return bool(taken.value)
     _check(load().arl_conv2d_bwd_data(dy.data_ptr(), w.data_ptr(), ptr(wt), None if mask is None else mask.data_ptr(),
                                       dx.data_ptr(), C.byref(geom), None if corun is None else C.byref(corun),
                                       C.byref(taken), stream_ptr(stream)), "arl_conv2d_bwd_data")
@@ -978,8 +1021,9 @@ class FoldList(object):
         return self._bias_done(dbias)
 
     def conv2d_bwd_pair(self, dy, w, mask, dx, x, dw, geom, workspace, dbias=None, stream=None, corun=None, wt=None,
-                        defer=False):
+                        defer=False, mask_bits=None):
         """dx (times mask > 0 if given) and (deferred) dw [+ dbias] of one layer in a single launch.
+        mask_bits: as conv2d_bwd_data.
         corun: an ArlCorunJob the data-gradient launch may carry; `self.corun_taken` says whether it did.
         wt: conv2d_dgrad_weights' copy of w for the data gradient.
         defer: a layer that does not pair runs its data gradient now and leaves its weight gradient to run_wgrads()."""
@@ -991,7 +1035,15 @@ class FoldList(object):
         slot = self._n - 1
         pb, ib = self._bias_slot(dbias)
         taken = _i32(0)
-        if defer:
+        if mask_bits is not None:
+            _want_bits(mask_bits, dx.numel(), "mask_bits")
+            _check(load().arl_conv2d_bwd_pair_bits(dy.data_ptr(), w.data_ptr(), ptr(wt), ptr(mask), mask_bits.data_ptr(),
+                                                   dx.data_ptr(), x.data_ptr(), dw.data_ptr(), C.byref(geom),
+                                                   ptr(workspace), workspace.numel() * workspace.element_size(), item,
+                                                   pb, ib, None if corun is None else C.byref(corun), C.byref(taken),
+                                                   self._next_plan(stream) if defer else None, stream_ptr(stream)),
+                   "arl_conv2d_bwd_pair_bits")
+        elif defer:
             _check(load().arl_conv2d_bwd_pair_plan(dy.data_ptr(), w.data_ptr(), ptr(wt), ptr(mask), dx.data_ptr(),
                                                    x.data_ptr(), dw.data_ptr(), C.byref(geom), ptr(workspace),
                                                    workspace.numel() * workspace.element_size(), item, pb, ib,

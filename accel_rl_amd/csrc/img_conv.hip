@@ -21,6 +21,7 @@
 
 namespace arlc {
 
+template <bool BITS>                // BITS: the output's rectifier mask as bits too (a.y_bits, conv1_tile)
 __global__ __launch_bounds__(C1_NT) void conv1_img_kernel(const Conv1ImgArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr int MAXLD = (C1_MAX_IMG / 16 + C1_NT - 1) / C1_NT;
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(C1_NT) void conv1_img_kernel(const Conv1ImgArgs a) 
     int buf = 0;
     for (int img = blockIdx.x; img < a.n_img; img += gridDim.x, buf ^= 1) {
         const char* im = sI + buf * npix;
-        for (int tp = wave; tp < tiles; tp += C1_NW) conv1_tile(a, im, sW, img, tp, lane, bq);
+        for (int tp = wave; tp < tiles; tp += C1_NW) conv1_tile<BITS>(a, im, sW, img, tp, lane, bq);
         // the next image's bytes (in flight while this one was computed) -> the other buffer, which every wave left at
         // the last barrier; the image after that starts its way from memory
         if (img + (int)gridDim.x < a.n_img) {
@@ -80,21 +81,24 @@ bool g_no_img_kernels = false;          // arl_dev_conv_variant(1): the tap-gath
 // arl_conv2d_u8_fwd's geometries that take the image-stationary kernel; < 0: not one of them (nothing launched)
 int launch_conv1_img(const unsigned char* obs, int64_t obs_rows, const int32_t* idx, float scale, const float* w, const float* bias, float* y,
                      int64_t batch, int C, int H, int W, int K, int kh, int kw, int stride, int Ho, int Wo, int relu,
-                     hipStream_t s, unsigned char* copy_out, long long copy_stride, int* zero_word) {
+                     hipStream_t s, unsigned char* copy_out, long long copy_stride, int* zero_word, unsigned* y_bits) {
     const int npix = C * H * W;
     const size_t lds = (size_t)(C * 64 / 16) * 3072 + 2 * (size_t)npix;
     if (g_no_img_kernels || !t_ctx.split || t_ctx.split == 1 || (K != 32 && K != 16) || kh != 8 || kw != 8 || npix % 16 != 0 || npix > C1_MAX_IMG ||
         lds > 160 * 1024 || ((uintptr_t)obs & 15) || (W & 3) || (stride & 3) || batch > 0x7fffffff)
         return -1;
     Conv1ImgArgs a = {obs, idx, w, bias, y, scale, (int)batch, C, H, W, Ho, Wo, stride, relu, K,
-                      (int)(obs_rows < 0x7fffffff ? obs_rows : 0x7fffffff), copy_out, copy_stride, zero_word};
+                      (int)(obs_rows < 0x7fffffff ? obs_rows : 0x7fffffff), copy_out, copy_stride, zero_word, y_bits};
     {   // per launch: the attribute belongs to the CURRENT device's copy of the kernel (no process-wide flag)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_img_kernel),
+        hipError_t e = hipFuncSetAttribute(y_bits ? reinterpret_cast<const void*>(conv1_img_kernel<true>)
+                                                  : reinterpret_cast<const void*>(conv1_img_kernel<false>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) { arl::set_error("hipFuncSetAttribute(conv1_img_kernel): %s", hipGetErrorString(e)); return (int)e; }
     }
     const int cus = 256;
-    hipLaunchKernelGGL(conv1_img_kernel, dim3((unsigned)(batch < cus ? batch : cus)), dim3(C1_NT), lds, s, a);
+    if (K != 32) ARL_REQUIRE(!y_bits, ARL_E_RANGE, "rectifier bits: 32 filters");
+    if (y_bits) hipLaunchKernelGGL(conv1_img_kernel<true>, dim3((unsigned)(batch < cus ? batch : cus)), dim3(C1_NT), lds, s, a);
+    else hipLaunchKernelGGL(conv1_img_kernel<false>, dim3((unsigned)(batch < cus ? batch : cus)), dim3(C1_NT), lds, s, a);
     log_launch(ARL_DEV_K_CONV1_IMG, {0, 0, 0, 0, 0, 0}, launch_flags(true, false, true, false, false), 1,
                dim3((unsigned)(batch < cus ? batch : cus)), lds);
     return arl::check_launch("conv1_img_kernel");

@@ -22,6 +22,7 @@ struct Conv1ImgArgs {
     unsigned char* copy_out;
     long long copy_stride;
     int* zero_word;
+    unsigned* y_bits;           // u32 [B][OH][OW] (32 filters only): bit c of a pixel's word = y[..][c] > 0, or null
 };
 
 __device__ __forceinline__ u32x2 bytes_to_bf16x4(unsigned v) {     // four packed bytes -> four bf16, exact
@@ -64,6 +65,7 @@ __device__ __forceinline__ void conv1_bias_quads(const float* __restrict__ bias,
 
 // One 32-pixel row tile tp of image `img` whose u8 planes [C][H][W] sit at `im` in LDS: 16-k steps in (plane, filter
 // row) order, weight planes l, m, h per step (split_products<.., 1, 3, true>), scale + bias + rectifier, 16-byte stores.
+template <bool BITS = false>                        // BITS: also a.y_bits (conv1_img_kernel's twin; the served step has none)
 __device__ __forceinline__ void conv1_tile(const Conv1ImgArgs& a, const char* im, const char* sW, const int img,
                                            const int tp, const int lane, const float4 (&bq)[4]) {
     constexpr int KH = 8;
@@ -91,6 +93,7 @@ __device__ __forceinline__ void conv1_tile(const Conv1ImgArgs& a, const char* im
 #pragma unroll
         for (int pl = 2; pl >= 0; --pl) acc = mfma_bf16(fb[pl], fa, acc);   // (split_products<.., 1, 3, true>: l, m, h)
     }
+    unsigned ob = 0u;                               // BITS: the lane's 16 bits of its pixel's mask word
     if (m < rows) {                                 // lane = pixel m, channels 8 q + 4 half + 0..3
         float* dst = a.y + ((size_t)img * rows + m) * N + 4 * half;
 #pragma unroll
@@ -100,7 +103,14 @@ __device__ __forceinline__ void conv1_tile(const Conv1ImgArgs& a, const char* im
                                    acc[4 * q + 2] * a.scale + bq[q].z, acc[4 * q + 3] * a.scale + bq[q].w);
             if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
             *reinterpret_cast<float4*>(dst + 8 * q) = v;
+            if constexpr (BITS)
+                ob |= ((v.x > 0.f ? 1u : 0u) | (v.y > 0.f ? 2u : 0u) | (v.z > 0.f ? 4u : 0u) | (v.w > 0.f ? 8u : 0u)) << (8 * q + 4 * half);
         }
+    }
+    // the output's rectifier mask as bits (32 filters): lane l and lane l ^ 32 hold the two halves of a pixel's word
+    if constexpr (BITS) {
+        const unsigned word = or_halves(ob);
+        if (half == 0 && m < rows) a.y_bits[(size_t)img * rows + m] = word;
     }
 }
 

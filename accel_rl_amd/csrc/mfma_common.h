@@ -84,6 +84,12 @@ struct OutDesc {
     unsigned out_bytes;     // size of the whole output tensor (strided epilogue's buffer descriptor)
     int relu, dense;        // dense: out[m*N + n]
     int OH, OW, omul, oadd_y, oadd_x;   // else out[((b*OH + oy*omul + oadd_y)*OW + ox*omul + oadd_x)*N + n]
+    // Rectifier masks as bits (N % 32 == 0; store_tiles_quads only): word (element offset) / 32 holds, in bit c % 32, whether
+    // channel c of that row is > 0.  mask_bits: read in place of `mask`; out_bits: written next to `out`.  Null: off.  Only
+    // the BITS instantiations look at them (launch_igemm_split, launch_pair: a launch of any other kernel drops mask_bits
+    // -- `mask` stays set and is compared as ever -- and refuses out_bits).
+    const unsigned* mask_bits;
+    unsigned* out_bits;
 };
 
 struct GemmArgs {
@@ -215,19 +221,51 @@ template <int NP> __device__ __forceinline__ void split_pair_n(float x0, float x
 // sixteen.  row_off[i] = element offset of the lane's row in tile i (or < 0: row out of range);
 // bias_q[j][q] = the lane's four bias values of quad q of column tile j (zeros without a bias);
 // N % 4 == 0 (checked on the host).  mask: same layout as out, out = 0 where mask <= 0.
-template <int TM, int TN, bool SCALED = false>
-__device__ __forceinline__ void store_tiles_quads(const f32x16 (&acc)[TM][TN], __amdgpu_buffer_rsrc_t rs,
-                                                  const long long (&row_off)[TM], int N, int col_base, int lane,
-                                                  const float4 (&bias_q)[TN][4], const float* mask, int relu,
-                                                  const float4 (*pre)[TM] = nullptr, float scale = 1.f) {
+// x of lane l | x of lane l ^ 32, in every lane: one v_permlane32_swap (vector unit: no trip through LDS)
+__device__ __forceinline__ unsigned or_halves(unsigned x) {
+    const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);       // {lower | lower, upper | upper}
+    return r[0] | r[1];
+}
+
+// BITS (a template flag of the kernels that take part, see igemm_body: with 0 every instantiation is the code it always
+// was, register for register): 1 = the rectifier mask is read as bits (mask_bits; bits_pre = the words igemm_body fetched a
+// k-tile ahead, [TM][TN]), 2 = the output's own mask is written as bits (out_bits) -- two twins, so that a data gradient
+// does not carry the forward's packing code (and its registers) and the other way round.  A lane owns row l31 and the channels 32 j + 8 q + 4 half + 0..3, so a word is the OR of the 16 bits
+// of lane l and of lane l ^ 32: one exchange per tile, the lanes of half 0 store, consecutive rows = consecutive words of
+// one column tile.  The floats stored are those of the BITS == false body: only where a comparison is read from changes.
+template <int TM, int TN, bool SCALED, int BITS>
+__device__ __forceinline__ void store_tiles_quads_impl(const f32x16 (&acc)[TM][TN], __amdgpu_buffer_rsrc_t rs,
+                                                       const long long (&row_off)[TM], int N, int col_base, int lane,
+                                                       const float4 (&bias_q)[TN][4], const float* mask, int relu,
+                                                       const float4 (*pre)[TM], float scale, const unsigned* mask_bits,
+                                                       const unsigned (*bits_pre)[TN], unsigned* out_bits) {
     const int half = lane >> 5;
+    // the mask as bits: one dword per row and 32 columns -- every word of the wave's tiles is asked for before the first
+    // store (one load latency per epilogue), unless igemm_body has fetched them a k-tile ahead (bits_pre)
+    unsigned mball[TM][TN];
+    const bool by_bits = BITS == 1 && mask_bits;        // uniform
+    if (by_bits) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int nb = col_base + j * 32;
+                mball[i][j] = ~0u;
+                if (bits_pre) mball[i][j] = bits_pre[i][j];
+                else if (row_off[i] >= 0 && nb < N) mball[i][j] = mask_bits[(row_off[i] + nb) >> 5];
+            }
+    }
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         // the rectifier mask of a column tile: every load issued before the first one is consumed (one latency
         // per column tile instead of one per store; per-workgroup timestamps had the epilogue of the stride-2
         // data gradient at 10 k cycles of a 66 k lifetime)
         float4 mk[4][TM];
-        if (mask && pre) {                              // (TN == 1: loaded in the prologue, see igemm_body)
+        unsigned mb[TM], ob[TM];
+        if (by_bits) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i) mb[i] = mball[i][j] >> (4 * half);
+        } else if (mask && pre) {                       // (TN == 1: loaded in the prologue, see igemm_body)
 #pragma unroll
             for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -243,6 +281,8 @@ __device__ __forceinline__ void store_tiles_quads(const f32x16 (&acc)[TM][TN], _
                 }
         }
 #pragma unroll
+        for (int i = 0; i < TM; ++i) ob[i] = 0u;
+#pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int n = col_base + j * 32 + 8 * q + 4 * half;
             const float4 bq = bias_q[j][q];
@@ -256,18 +296,46 @@ __device__ __forceinline__ void store_tiles_quads(const f32x16 (&acc)[TM][TN], _
                                   acc[i][j][4 * q + 2] + bq.z, acc[i][j][4 * q + 3] + bq.w);
                 if (relu) { val.x = fmaxf(val.x, 0.f); val.y = fmaxf(val.y, 0.f); val.z = fmaxf(val.z, 0.f); val.w = fmaxf(val.w, 0.f); }
                 const unsigned voff = ok ? (unsigned)((row_off[i] + n) << 2) : OOB;
-                if (mask) {
+                if (by_bits) {
+                    const unsigned m4 = mb[i] >> (8 * q);
+                    if (!(m4 & 1u)) val.x = 0.f;
+                    if (!(m4 & 2u)) val.y = 0.f;
+                    if (!(m4 & 4u)) val.z = 0.f;
+                    if (!(m4 & 8u)) val.w = 0.f;
+                } else if (mask) {
                     const float4 m = mk[q][i];
                     if (!(m.x > 0.f)) val.x = 0.f;
                     if (!(m.y > 0.f)) val.y = 0.f;
                     if (!(m.z > 0.f)) val.z = 0.f;
                     if (!(m.w > 0.f)) val.w = 0.f;
                 }
+                if (BITS == 2 && out_bits)
+                    ob[i] |= ((val.x > 0.f ? 1u : 0u) | (val.y > 0.f ? 2u : 0u) | (val.z > 0.f ? 4u : 0u) | (val.w > 0.f ? 8u : 0u))
+                             << (8 * q + 4 * half);
                 u32x4 raw = {__float_as_uint(val.x), __float_as_uint(val.y), __float_as_uint(val.z), __float_as_uint(val.w)};
                 __builtin_amdgcn_raw_buffer_store_b128(raw, rs, voff, 0, 0);
             }
         }
+        if (BITS == 2 && out_bits) {                    // uniform: every lane of the wave takes part in the exchange
+            const int nb = col_base + j * 32;
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                const unsigned word = or_halves(ob[i]);
+                if (half == 0 && row_off[i] >= 0 && nb < N) out_bits[(row_off[i] + nb) >> 5] = word;
+            }
+        }
     }
+}
+
+template <int TM, int TN, bool SCALED = false, int BITS = 0>
+__device__ __forceinline__ void store_tiles_quads(const f32x16 (&acc)[TM][TN], __amdgpu_buffer_rsrc_t rs,
+                                                  const long long (&row_off)[TM], int N, int col_base, int lane,
+                                                  const float4 (&bias_q)[TN][4], const float* mask, int relu,
+                                                  const float4 (*pre)[TM] = nullptr, float scale = 1.f,
+                                                  const unsigned* mask_bits = nullptr, const unsigned (*bits_pre)[TN] = nullptr,
+                                                  unsigned* out_bits = nullptr) {
+    store_tiles_quads_impl<TM, TN, SCALED, BITS>(acc, rs, row_off, N, col_base, lane, bias_q, mask, relu, pre, scale,
+                                                 mask_bits, bits_pre, out_bits);
 }
 
 // arguments of the weight-gradient kernels (generic: mfma_generic.h; scalar-addressed / split: mfma_wgrad.h)

@@ -184,11 +184,12 @@ bool fwd_plan(int M, int N, int K, int* splits, int* per) {
 
 // parts: leave a split reduction unfolded and describe it (arl_conv2d_fwd_parts); null = fold here
 int fwd_impl(const float* x, const float* w, const float* bias_or_null, float* y, const arl_conv_geom* geom, int32_t relu,
-             void* workspace, void* stream, arl_fold_item* parts = nullptr) {
+             void* workspace, void* stream, arl_fold_item* parts = nullptr, uint32_t* y_bits = nullptr) {
     Geom g;
     int rc = check_geom(geom, &g);
     if (rc) return rc;
     ARL_REQUIRE(x && w && y && workspace, ARL_E_ARG, "null pointer");
+    if ((rc = check_relu_bits(y_bits, g.K))) return rc;
     ARL_REQUIRE(arl::aligned16(x) && arl::aligned16(w) && arl::aligned16(y) && arl::aligned16(workspace) &&
                     (!bias_or_null || arl::aligned16(bias_or_null)), ARL_E_ALIGN, "16-byte alignment");
     hipStream_t s = (hipStream_t)stream;
@@ -218,6 +219,8 @@ int fwd_impl(const float* x, const float* w, const float* bias_or_null, float* y
     } else {
         a.o.out = y; a.o.bias = bias_or_null; a.o.relu = relu;
     }
+    ARL_REQUIRE(!y_bits || splits == 1, ARL_E_RANGE, "rectifier bits: not written by a split reduction's fold");
+    a.o.out_bits = y_bits;                          // (a launcher whose kernel has no BITS twin refuses: mfma_dispatch.h)
     // scalar-addressed fast path (k-tile of 32 inside one filter row)
     constexpr int FBK = 32;
     const bool single_tap = g.C % FBK == 0;
@@ -312,6 +315,13 @@ extern "C" int arl_conv2d_fwd(const float* x, const float* w, const float* bias_
     return fwd_impl(x, w, bias_or_null, y, geom, relu, workspace, stream);
 }
 
+extern "C" int arl_conv2d_fwd_bits(const float* x, const float* w, const float* bias_or_null, float* y,
+                                   uint32_t* y_bits_or_null, const arl_conv_geom* geom, int32_t relu, void* workspace,
+                                   void* stream) {
+    ARL_ROUTE_SCOPE(geom, nullptr);
+    return fwd_impl(x, w, bias_or_null, y, geom, relu, workspace, stream, nullptr, y_bits_or_null);
+}
+
 namespace {
 // plan_only: describe the fast launch instead of issuing it (fast == false: nothing was done)
 // workspace (optional): lets a dense layer whose output tiles cannot fill the chip split its reduction
@@ -321,11 +331,13 @@ namespace {
 // work): same piece products in the same k order, bit-identical results.
 int dgrad_impl(const float* dy, const float* w, const float* mask_or_null, float* dx, const arl_conv_geom* geom,
                DgradPlan* plan_only, void* stream, void* workspace = nullptr, int64_t workspace_bytes = 0,
-               const float* wt = nullptr) {
+               const float* wt = nullptr, const uint32_t* mask_bits = nullptr) {
     Geom g;
     int rc = check_geom(geom, &g);
     if (rc) return rc;
     ARL_REQUIRE(dy && w && dx, ARL_E_ARG, "null pointer");
+    ARL_REQUIRE(!mask_bits || mask_or_null, ARL_E_ARG, "rectifier bits come on top of the f32 mask, not instead of it");
+    if ((rc = check_relu_bits(mask_bits, g.C))) return rc;
     ARL_REQUIRE(g.kh % g.stride == 0 && g.kw % g.stride == 0, ARL_E_RANGE,
                 "data gradient needs kernel size divisible by stride");
     ARL_REQUIRE(arl::aligned16(dy) && arl::aligned16(w) && arl::aligned16(dx) &&
@@ -352,7 +364,7 @@ int dgrad_impl(const float* dy, const float* w, const float* mask_or_null, float
         a.b.w_bytes = (unsigned)((int64_t)g.K * g.kh * g.kw * g.C * 4);
         a.b.w = w; a.b.ld = g.kh * g.kw * g.C; a.b.kc = g.K; a.b.taps_x = taps_x;
         a.b.i0 = i0; a.b.j0 = j0; a.b.si = st; a.b.kw = g.kw; a.b.c = g.C;
-        a.o.out = dx; a.o.mask = mask_or_null; a.o.dense = (st == 1);
+        a.o.out = dx; a.o.mask = mask_or_null; a.o.mask_bits = mask_bits; a.o.dense = (st == 1);
         a.o.out_bytes = (unsigned)(g.batch * g.H * g.W * g.C * 4);
         a.o.OH = g.H; a.o.OW = g.W; a.o.omul = st; a.o.oadd_y = ph; a.o.oadd_x = pw;
         a.k_per_split = round_up(a.K, BKT);
@@ -399,7 +411,8 @@ int dgrad_impl(const float* dy, const float* w, const float* mask_or_null, float
             if ((int64_t)splits * a.M * a.N * 4 > workspace_bytes) { splits = 1; per = round_up(a.K, BKT); }
             a.k_per_split = per;
             if (splits > 1) {
-                a.o.out = (float*)workspace; a.o.mask = nullptr; a.split_stride = (int64_t)a.M * a.N;
+                a.o.out = (float*)workspace; a.o.mask = nullptr; a.o.mask_bits = nullptr;  // (the fold compares the floats)
+                a.split_stride = (int64_t)a.M * a.N;
             }
             if (g_split) rc = launch_igemm_split<2, 2, 1, 1, FBK, false, false, 3>(a, false, has_pad, s, splits);
             else rc = launch_igemm<2, 2, 1, 1, FBK, false>(a, splits, false, has_pad, s);
@@ -557,8 +570,14 @@ int wgrad_impl(const float* dy, const float* x, float* dw, const arl_conv_geom* 
 extern "C" int arl_conv2d_bwd_data(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
                                    float* dx, const arl_conv_geom* geom, const arl_corun_job* job_or_null,
                                    int32_t* job_taken_or_null, void* stream) {
+    return arl_conv2d_bwd_data_bits(dy, w, wt_or_null, mask_or_null, nullptr, dx, geom, job_or_null, job_taken_or_null, stream);
+}
+
+extern "C" int arl_conv2d_bwd_data_bits(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
+                                        const uint32_t* mask_bits_or_null, float* dx, const arl_conv_geom* geom,
+                                        const arl_corun_job* job_or_null, int32_t* job_taken_or_null, void* stream) {
     ARL_ROUTE_SCOPE(geom, job_or_null);
-    const int rc = dgrad_impl(dy, w, mask_or_null, dx, geom, nullptr, stream, nullptr, 0, wt_or_null);
+    const int rc = dgrad_impl(dy, w, mask_or_null, dx, geom, nullptr, stream, nullptr, 0, wt_or_null, mask_bits_or_null);
     if (job_taken_or_null) *job_taken_or_null = t_ctx.corun_taken ? 1 : 0;
     return rc;
 }
@@ -654,21 +673,32 @@ void fill_u8(GatherDesc* d, const uint8_t* obs, int64_t obs_rows, const int32_t*
 extern "C" int arl_conv2d_u8_fwd(const uint8_t* obs, int64_t obs_rows, const int32_t* idx_or_null, float scale,
                                  const float* w, const float* bias_or_null, float* y, const arl_conv_geom* geom,
                                  int32_t relu, void* stream) {
+    return arl_conv2d_u8_fwd_bits(obs, obs_rows, idx_or_null, scale, w, bias_or_null, y, nullptr, geom, relu, stream);
+}
+
+extern "C" int arl_conv2d_u8_fwd_bits(const uint8_t* obs, int64_t obs_rows, const int32_t* idx_or_null, float scale,
+                                      const float* w, const float* bias_or_null, float* y, uint32_t* y_bits_or_null,
+                                      const arl_conv_geom* geom, int32_t relu, void* stream) {
     launch_log_clear();                             // (the scope opens only after the geometry checks)
     ARL_REQUIRE(w && y, ARL_E_ARG, "null pointer");
     U8Geom g;
     int rc = check_u8(obs, obs_rows, geom, &g);
     if (rc) return rc;
+    if ((rc = check_relu_bits(y_bits_or_null, g.K))) return rc;
     ARL_ROUTE_SCOPE(geom, nullptr);
     ARL_REQUIRE(arl::aligned16(w) && arl::aligned16(y) && (!bias_or_null || arl::aligned16(bias_or_null)), ARL_E_ALIGN,
                 "16-byte alignment");
     if (!g_trace) {                                 // 32 filters of 8 x 8: the whole image in LDS (img_conv.hip)
         rc = launch_conv1_img(obs, obs_rows, idx_or_null, scale, w, bias_or_null, y, g.batch, g.C, g.H, g.W, g.K, g.kh, g.kw, g.stride,
-                              g.Ho, g.Wo, relu, (hipStream_t)stream);
+                              g.Ho, g.Wo, relu, (hipStream_t)stream, nullptr, 0, nullptr, y_bits_or_null);
         if (rc >= 0) return rc;
     }
     GemmArgs a = {};
+    // (off the image-stationary kernel the bf16-split kernel writes the bits too; the fp32 chain's kernels do not)
+    ARL_REQUIRE(!y_bits_or_null || (g_split && g.K > 16 && g.kh % (8 / (g.kw >> 2)) == 0), ARL_E_RANGE,
+                "rectifier bits: not written by the fp32 chain's u8 kernels");
     fill_u8(&a.g, obs, obs_rows, idx_or_null, scale, g);
+    a.o.out_bits = y_bits_or_null;
     a.M = (int)(g.batch * g.Ho * g.Wo); a.N = g.K; a.K = g.C * g.kh * g.kw;
     a.b.w = w; a.b.ld = a.K; a.b.w_bytes = (unsigned)((int64_t)a.N * a.K * 4);
     a.o.dense = 1; a.o.out = y; a.o.bias = bias_or_null; a.o.relu = relu;
@@ -781,7 +811,7 @@ namespace {
 int pair_impl(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null, float* dx, const float* x,
               float* dw, const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes, arl_fold_item* item,
               float* dbias_or_null, arl_fold_item* bias_item_or_null, const arl_corun_job* job_or_null,
-              int32_t* job_taken_or_null, WgradPlan* defer, void* stream) {
+              int32_t* job_taken_or_null, WgradPlan* defer, void* stream, const uint32_t* mask_bits = nullptr) {
     ARL_REQUIRE(item && geom && (!dbias_or_null || bias_item_or_null), ARL_E_ARG, "null pointer");
     if (job_taken_or_null) *job_taken_or_null = 0;
     ARL_ROUTE_SCOPE(geom, job_or_null);
@@ -791,7 +821,7 @@ int pair_impl(const float* dy, const float* w, const float* wt_or_null, const fl
     int splits = 1;
     int64_t total = 0;
     float* bias_part = nullptr;
-    int rc = dgrad_impl(dy, w, mask_or_null, dx, geom, &dp, stream);
+    int rc = dgrad_impl(dy, w, mask_or_null, dx, geom, &dp, stream, nullptr, 0, nullptr, mask_bits);
     if (rc) return rc;
     rc = wgrad_impl(dy, x, dw, geom, workspace, workspace_bytes, &splits, &total,
                     dbias_or_null ? &bias_part : nullptr, &wp, stream);
@@ -812,7 +842,7 @@ int pair_impl(const float* dy, const float* w, const float* wt_or_null, const fl
         // once), the weight gradient's deferred partials the lower half
         const int64_t half = (workspace_bytes / 2) & ~(int64_t)15;
         rc = dgrad_impl(dy, w, mask_or_null, dx, geom, nullptr, stream, (char*)workspace + half, workspace_bytes - half,
-                        wt_or_null);
+                        wt_or_null, mask_bits);
         if (job_taken_or_null) *job_taken_or_null = t_ctx.corun_taken ? 1 : 0;
         if (rc) return rc;
         return wgrad_parts_impl(dy, x, dw, geom, workspace, half, item, dbias_or_null, bias_item_or_null, stream, defer);
@@ -838,6 +868,19 @@ extern "C" int arl_conv2d_bwd_pair(const float* dy, const float* w, const float*
                                    int32_t* job_taken_or_null, void* stream) {
     return pair_impl(dy, w, wt_or_null, mask_or_null, dx, x, dw, geom, workspace, workspace_bytes, item, dbias_or_null,
                      bias_item_or_null, job_or_null, job_taken_or_null, nullptr, stream);
+}
+
+// plan_or_null: as arl_conv2d_bwd_pair_plan (null: as arl_conv2d_bwd_pair)
+extern "C" int arl_conv2d_bwd_pair_bits(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
+                                        const uint32_t* mask_bits_or_null, float* dx, const float* x, float* dw,
+                                        const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes,
+                                        arl_fold_item* item, float* dbias_or_null, arl_fold_item* bias_item_or_null,
+                                        const arl_corun_job* job_or_null, int32_t* job_taken_or_null,
+                                        arl_wgrad_plan* plan_or_null, void* stream) {
+    if (plan_or_null) *plan_or_null = arl_wgrad_plan{};
+    return pair_impl(dy, w, wt_or_null, mask_or_null, dx, x, dw, geom, workspace, workspace_bytes, item, dbias_or_null,
+                     bias_item_or_null, job_or_null, job_taken_or_null, reinterpret_cast<WgradPlan*>(plan_or_null), stream,
+                     mask_bits_or_null);
 }
 
 extern "C" int arl_conv2d_bwd_pair_plan(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,

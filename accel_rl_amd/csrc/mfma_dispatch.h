@@ -27,6 +27,7 @@ int launch_rowgather(const GemmArgs& a, int splits, hipStream_t s) {
     constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
     constexpr int A_SZ = BM * (BK + 4), B_SZ = B_KC ? BN * (BK + 4) : BK * BN;
     const size_t lds = (size_t)2 * (A_SZ + B_SZ) * sizeof(float);
+    ARL_REQUIRE(!a.o.out_bits, ARL_E_RANGE, "rectifier bits: not written by the generic kernels");
     dim3 grid((a.M + BM - 1) / BM, (a.N + BN - 1) / BN, splits);
     hipLaunchKernelGGL((rowgather_gemm_kernel<WGM, WGN, TM, TN, BK, B_KC, TAP_UNIFORM>), grid, dim3(256), lds, s, a);
     log_launch(ARL_DEV_K_ROWGATHER, {WGM, WGN, TM, TN, BK, 0},
@@ -66,6 +67,7 @@ int launch_igemm(const GemmArgs& a, int splits, bool multi_tap, bool has_pad, hi
     constexpr int BM = WGM * TM * (N16 ? 16 : 32), BN = N16 ? WGN * 16 : WGN * TN * 32;
     constexpr int A_SZ = BM * (BK + 4), B_SZ = B_KC ? BN * (BK + 4) : BK * (N16 ? BN + 4 : BN);
     const size_t lds = (size_t)2 * (A_SZ + B_SZ) * sizeof(float);
+    ARL_REQUIRE(!a.o.out_bits, ARL_E_RANGE, "rectifier bits: not written by the fp32 chain's kernels");
     dim3 grid((a.M + BM - 1) / BM, (a.N + BN - 1) / BN, a.n_par ? a.n_par : splits);
     int rc = 0;
 #define ARL_IGEMM(MT, HP)                                                                                  \
@@ -126,6 +128,7 @@ int launch_igemm_occ(const GemmArgs& a, bool multi_tap, bool has_pad, hipStream_
     constexpr int A_SZ = BM * (BK + 4), B_SZ = B_KC ? BN * (BK + 4) : BK * (N16 ? BN + 4 : BN);
     const size_t lds = (size_t)2 * (A_SZ + B_SZ) * sizeof(float);
     static_assert(lds_fits(2 * (A_SZ + B_SZ)), "<= 64 KiB of LDS");
+    ARL_REQUIRE(!a.o.out_bits, ARL_E_RANGE, "rectifier bits: not written by the fp32 chain's kernels");
     dim3 grid((a.M + BM - 1) / BM, (a.N + BN - 1) / BN, a.n_par ? a.n_par : splits);
     arl::OptSeg c = {};
     if constexpr (!B_KC) {                          // a data gradient hosts the call's optimiser job, if any
@@ -155,9 +158,20 @@ int launch_igemm_occ(const GemmArgs& a, bool multi_tap, bool has_pad, hipStream_
 
 // the launch of igemm_split_kernel: two LDS stages of (1 or 3) + 3 bf16 planes; a data gradient hosts the pending
 // optimiser job like launch_igemm_occ
+// Rectifier masks as bits (OutDesc::mask_bits / out_bits): the one-wave-per-row-tile shapes on k-contiguous f32 operands with
+// one tap per k-tile have a BITS twin -- the learner's conv 2 / conv 3 forward (which write them) and data gradients (which
+// read them).  Any other launch compares the f32 mask as ever and refuses to write bits.
 template <int WGM, int WGN, int TM, int TN, int BK, bool B_KC, bool U8, int MINW>
-int launch_igemm_split(const GemmArgs& a, bool multi_tap, bool has_pad, hipStream_t s, int splits = 1) {
+int launch_igemm_split(const GemmArgs& a_in, bool multi_tap, bool has_pad, hipStream_t s, int splits = 1) {
     constexpr int BM = WGM * TM * 32, BN = WGN * TN * 32;
+    constexpr bool CAN_BITS = B_KC && WGM == 4 && WGN == 1 && (U8 || TM == 1);      // (u8: conv 1 off the image-stationary kernel)
+    GemmArgs a = a_in;
+    // (a forward has no mask and a data gradient writes no bits: the twin is the reading one or the writing one)
+    const int bits = !(CAN_BITS && !multi_tap) ? 0 : a.o.out_bits ? 2 : a.o.mask_bits ? 1 : 0;
+    if (!bits) {
+        ARL_REQUIRE(!a.o.out_bits, ARL_E_RANGE, "rectifier bits: not written by this layer's kernel");
+        a.o.mask_bits = nullptr;
+    }
     const int npl = planes_of(g_split);
     const size_t lds = (size_t)2 * ((U8 ? 1 : npl) * BM + npl * BN) * BK * 2;
     const size_t lds_dir = (size_t)2 * npl * BN * BK * 2;       // direct gathered operand: only the weights live in LDS
@@ -169,9 +183,9 @@ int launch_igemm_split(const GemmArgs& a, bool multi_tap, bool has_pad, hipStrea
         const bool ad = WGN == 1 && (U8 || !mt);
         if (!rc) log_launch(ARL_DEV_K_IGEMM_SPLIT, {WGM, WGN, TM, TN, BK, MINW}, launch_flags(B_KC, false, U8, mt, hp, ad, co), splits, grid, ad ? lds_dir : lds);
     };
-#define ARL_SPLIT_K(MT, HP, SPL, CO, AD)                                                                   \
+#define ARL_SPLIT_K(MT, HP, SPL, CO, AD, BT)                                                               \
     do {                                                                                                   \
-        auto k = igemm_split_kernel<WGM, WGN, TM, TN, BK, B_KC, MT, HP, U8, SPL, MINW, CO, AD>;            \
+        auto k = igemm_split_kernel<WGM, WGN, TM, TN, BK, B_KC, MT, HP, U8, SPL, MINW, CO, AD, BT>;        \
         const size_t lds_k = (AD) ? lds_dir : lds;                                                         \
         rc = allow_big_lds(k, lds_k + (CO ? 64 : 0));                                                      \
         if (!rc) hipLaunchKernelGGL(k, grid, dim3(256), lds_k, s, a, c);                                   \
@@ -180,7 +194,17 @@ int launch_igemm_split(const GemmArgs& a, bool multi_tap, bool has_pad, hipStrea
 #define ARL_SPLIT_PIN(MT, HP, SPL, CO)                                                                     \
     do {                                                                                                   \
         constexpr bool AD = WGN == 1 && (U8 || !(MT));                                                     \
-        ARL_SPLIT_K(MT, HP, SPL, CO, AD);                                                                  \
+        if constexpr (CAN_BITS && U8) {                     /* (a forward: the writing twin alone) */      \
+            if (bits == 2) ARL_SPLIT_K(MT, HP, SPL, CO, AD, 2); else ARL_SPLIT_K(MT, HP, SPL, CO, AD, 0);  \
+        } else if constexpr (CAN_BITS && !(MT) && (CO)) {   /* (only a data gradient carries a job) */     \
+            if (bits == 1) ARL_SPLIT_K(MT, HP, SPL, CO, AD, 1); else ARL_SPLIT_K(MT, HP, SPL, CO, AD, 0);  \
+        } else if constexpr (CAN_BITS && !(MT)) {                                                          \
+            if (bits == 1) ARL_SPLIT_K(MT, HP, SPL, CO, AD, 1);                                            \
+            else if (bits == 2) ARL_SPLIT_K(MT, HP, SPL, CO, AD, 2);                                       \
+            else ARL_SPLIT_K(MT, HP, SPL, CO, AD, 0);                                                      \
+        } else {                                                                                           \
+            ARL_SPLIT_K(MT, HP, SPL, CO, AD, 0);                                                           \
+        }                                                                                                  \
     } while (0)
 #define ARL_SPLIT_MODE(MT, HP, CO)                                                                         \
     do {                                                                                                   \
@@ -192,7 +216,7 @@ int launch_igemm_split(const GemmArgs& a, bool multi_tap, bool has_pad, hipStrea
     } else {
         // (data gradients: k-major weights, or k-contiguous ones on the one-wave-per-row-tile shapes)
         if constexpr (!B_KC || (WGM == 4 && WGN == 1 && TM == 1)) {
-            if (!multi_tap && corun_take(&c, &grid)) {
+            if (!multi_tap && bits != 2 && corun_take(&c, &grid)) {   // (a launch that writes bits is a forward: no job)
                 if (has_pad) ARL_SPLIT_MODE(false, true, true); else ARL_SPLIT_MODE(false, false, true);
                 note(false, has_pad, true);
                 return rc ? rc : arl::check_launch("igemm_split_kernel (co-run)");
@@ -290,6 +314,15 @@ inline int check_geom(const arl_conv_geom* g, Geom* o) {
     return 0;
 }
 
+// A rectifier mask as bits (arl_conv2d_*_bits): u32[rows][channels / 32], bit c % 32 of word c / 32 = (y[row][c] > 0).
+// Null = not asked for; anything the kernels cannot serve is refused, never ignored.
+inline int check_relu_bits(const void* bits, int channels) {
+    if (!bits) return 0;
+    ARL_REQUIRE(channels % 32 == 0, ARL_E_RANGE, "rectifier bits: the channel count must be a multiple of 32");
+    ARL_REQUIRE(arl::aligned4(bits), ARL_E_ALIGN, "rectifier bits: 4-byte alignment");
+    return 0;
+}
+
 inline int round_up(int x, int q) { return (x + q - 1) / q * q; }
 
 // ceil(2^32 / d) if floor(n * that / 2^32) == n / d for every 0 <= n < rows (needs rows * d < 2^32), else 0
@@ -344,15 +377,25 @@ int launch_pair(const DgradPlan& d, const WgradPlan& w, bool has_pad, hipStream_
     size_t lds_used = lds;
     if (g_split) {
         const size_t lds_s = (size_t)2 * planes_of(g_split) * ((DBM + DBN) > (WBM + WBN) ? (DBM + DBN) : (WBM + WBN)) * BK * 2;
-#define ARL_PSPLIT(HP, SPL)                                                                                \
+#define ARL_PSPLIT_K(HP, SPL, BT)                                                                          \
     do {                                                                                                   \
-        auto k = bwd_pair_kernel<DWGM, DWGN, DTM, DTN, WWGM, WWGN, WTM, WTN, BK, HP, SPL>;                 \
+        auto k = bwd_pair_kernel<DWGM, DWGN, DTM, DTN, WWGM, WWGN, WTM, WTN, BK, HP, SPL, BT>;             \
         rc = allow_big_lds(k, lds_s + 4096);                                                               \
         if (!rc) hipLaunchKernelGGL(k, dim3(n_ig + n_wg), dim3(256), lds_s, s, d.a, w.a, dgx, dgy, n_ig, wgx, wgy); \
+    } while (0)
+// (the data gradient's rectifier mask as bits: the 16-deep split kernels -- the learner's dense pair -- have a BITS twin)
+#define ARL_PSPLIT(HP, SPL)                                                                                \
+    do {                                                                                                   \
+        if constexpr (BK == 16) {                                                                          \
+            if (d.a.o.mask_bits) ARL_PSPLIT_K(HP, SPL, 1); else ARL_PSPLIT_K(HP, SPL, 0);                  \
+        } else {                                                                                           \
+            ARL_PSPLIT_K(HP, SPL, 0);                                                                      \
+        }                                                                                                  \
     } while (0)
         if (has_pad) ARL_BY_MODE(ARL_PSPLIT(true, 1), ARL_PSPLIT(true, 6), ARL_PSPLIT(true, 9));
         else ARL_BY_MODE(ARL_PSPLIT(false, 1), ARL_PSPLIT(false, 6), ARL_PSPLIT(false, 9));
 #undef ARL_PSPLIT
+#undef ARL_PSPLIT_K
         lds_used = lds_s;
     } else if (has_pad) {
         auto k = bwd_pair_kernel<DWGM, DWGN, DTM, DTN, WWGM, WWGN, WTM, WTN, BK, true>;
@@ -372,7 +415,8 @@ int launch_pair(const DgradPlan& d, const WgradPlan& w, bool has_pad, hipStream_
 // img_conv.hip: the image-stationary kernels (>= 0: launched / error code; -1: not their geometry)
 int launch_conv1_img(const unsigned char* obs, int64_t obs_rows, const int32_t* idx, float scale, const float* w, const float* bias, float* y,
                      int64_t batch, int C, int H, int W, int K, int kh, int kw, int stride, int Ho, int Wo, int relu,
-                     hipStream_t s, unsigned char* copy_out = nullptr, long long copy_stride = 0, int* zero_word = nullptr);
+                     hipStream_t s, unsigned char* copy_out = nullptr, long long copy_stride = 0, int* zero_word = nullptr,
+                     unsigned* y_bits = nullptr);
 
 // ---- the launcher instantiations, dealt out to translation units (mfma_conv_p<k>.hip define ARL_CONV_PART = k and hold the
 // definitions of part k; every other unit sees them as extern templates) so that hipcc builds them side by side

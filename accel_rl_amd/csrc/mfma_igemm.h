@@ -14,7 +14,7 @@ namespace arlc {
 // no padding); a k-tile covers BK / kw8 whole filter rows of one plane, so the tile's address is again
 // per-thread constant + per-tile uniform.
 template <int WGM, int WGN, int TM, int TN, int BK, bool B_KC, bool MULTI_TAP, bool HAS_PAD, bool N16 = false,
-          bool U8 = false, int SPLIT = 0, bool ADIR = false>
+          bool U8 = false, int SPLIT = 0, bool ADIR = false, int BITS = 0>
 __device__ __forceinline__ void igemm_body(const GemmArgs& a, const int bx, const int by, const int bz, float* smem) {
     constexpr bool SP = SPLIT != 0;                 // bf16-split products (see above): other LDS images, other MFMAs
     // ADIR: the gathered operand never enters LDS.  With WGN == 1 a wave owns its 32-row tiles outright, and a lane's
@@ -23,6 +23,9 @@ __device__ __forceinline__ void igemm_body(const GemmArgs& a, const int bx, cons
     // split kernels are otherwise LDS-bound: three planes written and read back per operand tile is more LDS time
     // than the nine products take on the matrix pipe (128x32 tiles: ~1 400 LDS cycles against 1 152 per k-tile and CU).
     static_assert(!ADIR || (SP && WGN == 1 && !MULTI_TAP), "direct operand: split kernels, one wave per row tile");
+    // BITS: rectifier masks as bits (store_tiles_quads: 1 = OutDesc::mask_bits is read, 2 = OutDesc::out_bits is written)
+    // -- instantiated for the kernels of the learner's conv 2 / conv 3 forward and data gradients and of the dense pair only
+    static_assert(!BITS || !N16, "rectifier bits: 32-wide tiles");
     constexpr int MT = N16 ? 16 : 32;               // rows per MFMA tile
     constexpr int BM = WGM * TM * MT, BN = N16 ? WGN * 16 : WGN * TN * 32, CH = BK / 4;
     constexpr int LDA = BK + 4;
@@ -415,7 +418,21 @@ __device__ __forceinline__ void igemm_body(const GemmArgs& a, const int bx, cons
     float4 mk_pre[4][TM];
     // issued at the start of the LAST k-tile: behind every operand load (an earlier issue would sit in front of the
     // tile loads in the in-order vmcnt queue and stall the first LDS store on scattered, cache-cold addresses)
+    unsigned mb_pre[TM][TN];                            // the mask as bits: one dword per row tile and column tile
     auto issue_mask_loads = [&]() {
+        if constexpr (BITS == 1 && PRE_MASK) {               // (the larger tiles ask for their words in the epilogue, all at once)
+            if (a.o.mask_bits) {                        // uniform
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        const int nb = n0 + wn * TN * 32 + j * 32;
+                        mb_pre[i][j] = ~0u;
+                        if (row_off[i] >= 0 && nb < a.N) mb_pre[i][j] = a.o.mask_bits[(row_off[i] + nb) >> 5];
+                    }
+                return;
+            }
+        }
         if (!(PRE_MASK && a.o.mask)) return;
 #pragma unroll
         for (int q = 0; q < (N16 ? 1 : 4); ++q)
@@ -663,8 +680,13 @@ __device__ __forceinline__ void igemm_body(const GemmArgs& a, const int bx, cons
                 __builtin_amdgcn_raw_buffer_store_b128(raw, rsO, ok ? (unsigned)((row_off[i] + n) << 2) : OOB, 0, 0);
             }
         } else {
-            store_tiles_quads<TM, TN, U8>(acc, rsO, row_off, a.N, n0 + wn * TN * 32, lane, bias_q, a.o.mask, a.o.relu,
-                                          PRE_MASK ? mk_pre : nullptr, g.scale);
+            if constexpr (BITS != 0)
+                store_tiles_quads<TM, TN, U8, BITS>(acc, rsO, row_off, a.N, n0 + wn * TN * 32, lane, bias_q, a.o.mask, a.o.relu,
+                                                    PRE_MASK ? mk_pre : nullptr, g.scale, a.o.mask_bits,
+                                                    PRE_MASK ? mb_pre : nullptr, a.o.out_bits);
+            else
+                store_tiles_quads<TM, TN, U8>(acc, rsO, row_off, a.N, n0 + wn * TN * 32, lane, bias_q, a.o.mask, a.o.relu,
+                                              PRE_MASK ? mk_pre : nullptr, g.scale);
         }
     }
     if (a.trace && tid == 0) {
@@ -696,10 +718,12 @@ __global__ __launch_bounds__(256) void igemm_kernel(const GemmArgs a) {
 // bf16-split products (igemm_body, SPLIT): MINW waves per SIMD; CORUN: an optimiser job rides in the grid's first workgroups
 // (arl_corun_job), as in igemm_occ_kernel
 template <int WGM, int WGN, int TM, int TN, int BK, bool B_KC, bool MULTI_TAP, bool HAS_PAD, bool U8, int SPLIT, int MINW,
-          bool CORUN = false, bool ADIR = false>
+          bool CORUN = false, bool ADIR = false, int BITS = 0>
 __global__ __launch_bounds__(256, MINW) void igemm_split_kernel(const GemmArgs a, const arl::OptSeg c) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     pin_gemm_args(a);
+    if constexpr (BITS == 1) asm volatile("" :: "s"(a.o.mask_bits));
+    if constexpr (BITS == 2) asm volatile("" :: "s"(a.o.out_bits));
     int bx = blockIdx.x;
     if constexpr (CORUN) {
         if (bx < c.co_blocks) {
@@ -719,7 +743,7 @@ __global__ __launch_bounds__(256, MINW) void igemm_split_kernel(const GemmArgs a
         const int u = t / gx;
         by = u % gy; bz = u / gy;
     }
-    igemm_body<WGM, WGN, TM, TN, BK, B_KC, MULTI_TAP, HAS_PAD, false, U8, SPLIT, ADIR>(a, bx, by, bz, smem);
+    igemm_body<WGM, WGN, TM, TN, BK, B_KC, MULTI_TAP, HAS_PAD, false, U8, SPLIT, ADIR, BITS>(a, bx, by, bz, smem);
 }
 
 template <int WGM, int WGN, int TM, int TN, int BK, bool B_KC, bool MULTI_TAP, bool HAS_PAD, bool N16, int MINW, bool CORUN = false,

@@ -183,6 +183,8 @@ class AtariCnnPolicy(object):
         self._folds, self._fold_workspaces = _lib.FoldList(), {}
         self._loss_ws = _lib.pg_head_workspace(self.device)
         self._param_writes, self._stored_acts = 0, None
+        # rectifier masks as bits (_relu_bits_layers): {data_ptr of a conv activation: its bits}, for one training pass
+        self._bits, self._bits_pass = {}, False
         self._set_from_reference_arrays(ref)
         if self.initial_param_values is not None:
             self.set_param_values(self.initial_param_values)
@@ -333,18 +335,42 @@ class AtariCnnPolicy(object):
             gs = self._geoms[key] = (conv, dense)
         return gs
 
+    # Rectifier masks as bits.  A data gradient uses one thing of the layer below's f32 output: whether each value is > 0.
+    # In a training pass (loss_and_grads) the forward kernels of the conv layers listed here also write that as one bit per
+    # value (u32[rows][C / 32], _lib.relu_bits_shape) and the data gradient above reads the bits instead of the floats:
+    # 1/32 of the mask's bytes, the same dx bit for bit.  ARL_RELU_BITS (A/B switch): unset = RELU_BITS_DEFAULT; "0" = none
+    # (the f32 masks everywhere, the launches of before); else the 1-based conv layers whose output gets bits, e.g.
+    # "1,3".  Only layers of 32 or 64 filters on a bf16-split route take part (what the kernels serve: accel_rl_hip.h); a
+    # minibatch whose activations come from the rollout's store has no producer and keeps the f32 masks.
+    RELU_BITS_DEFAULT = (1, 2, 3)
+
+    def _relu_bits_layers(self):
+        env = os.environ.get("ARL_RELU_BITS")
+        want = self.RELU_BITS_DEFAULT if env is None else tuple(int(t) for t in env.split(",") if t.strip())
+        if _lib.default_route == _lib.ROUTE_FP32:
+            return ()
+        return tuple(i for i, (nf, ci, sz, st, pad, ho, wo) in enumerate(self._conv_geom)
+                     if (i + 1) in want and nf in (32, 64) and
+                     (self._u8 and sz in (8, 16) and sz % (8 // (sz >> 2)) == 0 if i == 0 else ci % 32 == 0) and
+                     (tuple(pad) == (0, 0) or sz * sz <= 32))
+
     def _convs(self, x, w=None, tag=""):
         """The conv stack of _trunk: activations [B, Ho, Wo, K] of every layer, post bias + rectifier."""
         b = x.shape[0]
         w = self._w if w is None else w
         conv_g, _ = self._layer_geoms(b)
         acts, a = [], x
+        with_bits = self._relu_bits_layers() if self._bits_pass else ()
         for i, (nf, ci, sz, st, pad, ho, wo) in enumerate(self._conv_geom):
             z = self._buffer(("act" + tag, i, b), (b, ho, wo, nf))
+            bits = None
+            if i in with_bits:
+                bits = self._buffer(("act_bits" + tag, i, b), _lib.relu_bits_shape(b * ho * wo, nf), dtype=torch.int32)
+                self._bits[z.data_ptr()] = bits
             if isinstance(a, ObsRows):
-                _lib.conv2d_u8_fwd(a.obs, a.idx, self._scale, w[0], w[1], z, conv_g[0], True)
+                _lib.conv2d_u8_fwd(a.obs, a.idx, self._scale, w[0], w[1], z, conv_g[0], True, y_bits=bits)
             else:
-                _lib.conv2d_fwd(a, w[2 * i], w[2 * i + 1], z, conv_g[i], True, self._conv_ws)
+                _lib.conv2d_fwd(a, w[2 * i], w[2 * i + 1], z, conv_g[i], True, self._conv_ws, y_bits=bits)
             acts.append(z)
             a = z
         return acts
@@ -597,7 +623,12 @@ class AtariCnnPolicy(object):
             # (the caller's grant -- stored_acts_for -- that these rows' forward under the parameters as they stand is
             #  in the rollout's store: gathered instead of computed; A2C's and PPO's one-pass minibatches only)
             store = mb.get("stored_acts") if kind in (KIND_A2C, KIND_PPO) else None
-            acts, hids = self._trunk(x) if store is None else self._trunk_from_store(x, store, idx)
+            self._bits.clear()                          # (a pass's bits belong to that pass's activations alone)
+            self._bits_pass = store is None
+            try:
+                acts, hids = self._trunk(x) if store is None else self._trunk_from_store(x, store, idx)
+            finally:
+                self._bits_pass = False
             g, k_head = self.grads, self._k_head
             hid = self._hid_geom[-1][0]
             dout = self._buffer(("dout", b), (b, self.n_act + 1))
@@ -757,6 +788,7 @@ class AtariCnnPolicy(object):
         if corun is not None:
             _lib.corun_job_run(corun)           # no launch could carry it: on its own, ahead of the step's update
         self._folds.run()
+        self._bits.clear()                      # (the pass that wrote them ends here)
 
     def _layer_grads(self, d, masked, y, rows, channels, k, geom, inp, d_in, corun=None, wt=None, defer=False):
         """One layer's backward: bias and weight gradient (deferred folds) and, with d_in, the data gradient
@@ -772,7 +804,8 @@ class AtariCnnPolicy(object):
                                               self._fold_ws(("dw", k)), dbias=dbias, defer=defer)
         elif d_in is not None:      # data + weight gradient share one launch where that pays (dense layers)
             done = folds.conv2d_bwd_pair(d, self._w[k], inp, d_in, inp, self._g[k], geom, self._fold_ws(("dw", k)),
-                                         dbias=dbias, corun=corun, wt=wt, defer=defer)
+                                         dbias=dbias, corun=corun, wt=wt, defer=defer,
+                                         mask_bits=self._bits.get(inp.data_ptr()))     # (this pass's forward wrote them)
         else:
             done = folds.conv2d_bwd_weight(d, inp, self._g[k], geom, self._fold_ws(("dw", k)), dbias=dbias, defer=defer)
         if not done:                # generic kernels leave the bias sums to the streaming kernel (its mask is idempotent)

@@ -929,6 +929,39 @@ int arl_conv2d_bwd_pair_plan(const float* dy, const float* w, const float* wt_or
                              int32_t* job_taken_or_null, arl_wgrad_plan* plan, void* stream);
 int arl_conv2d_bwd_weight_group(const arl_wgrad_plan* plans, int32_t n, void* stream);
 
+/* Rectifier masks as bits.  A data gradient uses one thing of every value of its f32 mask: whether it is > 0.  For an
+ * activation tensor y f32[rows][C] with C % 32 == 0 (rows in the tensor's own NHWC order) the mask as bits is
+ * u32[rows][C / 32]: bit c % 32 of word c / 32 = (y[row][c] > 0.f) as the device evaluates it on the stored value (NaN and
+ * -0 give 0, as in the f32 comparison) -- 1/32 of the bytes.  The *_bits entry points are their namesakes with one more
+ * pointer; NULL there = the namesake itself, bit for bit and launch for launch.
+ *   y_bits (forward calls): the launch also writes y's mask as bits; y itself is written as ever.  Served on the bf16-split
+ *     routes by the kernels of layers with 32 .. 64 output columns whose k-tiles hold one filter tap (in_c % 32 == 0: the
+ *     learner's conv 2 and conv 3) and by the first convolution from u8 rows with 32 filters (the image-stationary kernel,
+ *     or the tap-gathering split kernel where that one does not run); ARL_E_RANGE -- nothing launched, never ignored -- for
+ *     out_c % 32 != 0, a reduction that the call splits (the fold writes y), the fp32 route, wider or multi-tap layers and
+ *     the generic kernels.
+ *   mask_bits (data gradients): the mask of mask_or_null as bits, from a forward call's y_bits on the same tensor.  It
+ *     comes on top of mask_or_null (ARL_E_ARG without it): the bf16-split launches of 17 .. 64 input channels on the
+ *     k-contiguous weight copy (wt) and the shared launch of arl_conv2d_bwd_pair test the bit and never read the floats;
+ *     every other launch (fp32 route, no wt, 16-wide tiles, generic kernels, the split reduction's fold) compares the
+ *     floats as before.  dx is the same bits either way.  ARL_E_RANGE for in_c % 32 != 0.
+ * Both: ARL_E_ALIGN unless 4-byte aligned.  arl_conv2d_bwd_pair_bits with plan_or_null is arl_conv2d_bwd_pair_plan.
+ * The reference has no counterpart: Theano keeps the rectifier's input for T.grad (pg_cnn.py:47-68).                    */
+int arl_conv2d_fwd_bits(const float* x, const float* w, const float* bias_or_null, float* y, uint32_t* y_bits_or_null,
+                        const arl_conv_geom* geom, int32_t relu, void* workspace, void* stream);
+int arl_conv2d_u8_fwd_bits(const uint8_t* obs, int64_t obs_rows, const int32_t* idx_or_null, float scale,
+                           const float* w, const float* bias_or_null, float* y, uint32_t* y_bits_or_null,
+                           const arl_conv_geom* geom, int32_t relu, void* stream);
+int arl_conv2d_bwd_data_bits(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
+                             const uint32_t* mask_bits_or_null, float* dx, const arl_conv_geom* geom,
+                             const struct arl_corun_job* job_or_null, int32_t* job_taken_or_null, void* stream);
+int arl_conv2d_bwd_pair_bits(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
+                             const uint32_t* mask_bits_or_null, float* dx, const float* x, float* dw,
+                             const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes, arl_fold_item* item,
+                             float* dbias_or_null, arl_fold_item* bias_item_or_null,
+                             const struct arl_corun_job* job_or_null, int32_t* job_taken_or_null,
+                             arl_wgrad_plan* plan_or_null, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Replay memory of the DQN family
  * ------------------------------------------------------------------------- */
