@@ -13,7 +13,7 @@ import torch
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libaccel_rl_hip.so")
 
-ARL_ABI_VERSION = 4
+ARL_ABI_VERSION = 5
 PROMO_NEP50, PROMO_LEGACY, PROMO_ASSOC = 0, 1, 2
 PPO_TIE_THEANO, PPO_TIE_MATH, PPO_TIE_BOTH = 0, 1, 2      # ARL_PPO_TIE_*: whose gradient min() / clip() hand on (accel_rl_hip.h)
 PPG_POLICY, PPG_AUX = 0, 1                                # ARL_PPG_*: arl_ppg_head_loss_parts' phase
@@ -184,42 +184,28 @@ _SIGNATURES = {
     "arl_pg_head_loss_parts": (_i32, [_vp] * 11 + [_i64, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _i32] + [_vp] * 7 +
                                [_vp, _i32, _vp]),
     "arl_conv_workspace_bytes": (_i64, []),
-    "arl_conv2d_fwd": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _i32, _vp, _vp]),
-    "arl_conv2d_bwd_data": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), C.POINTER(ArlCorunJob), C.POINTER(_i32), _vp]),
+    "arl_conv2d_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _i32, _vp, C.POINTER(ArlFoldItem), _vp]),
+    "arl_conv2d_bwd_data": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), C.POINTER(ArlCorunJob),
+                                   C.POINTER(_i32), _vp]),
     "arl_conv2d_dgrad_weights": (_i32, [C.POINTER(ArlDgradWt), _i32, _vp]),
     "arl_conv2d_bwd_weight": (_i32, [_vp, _vp, _vp, C.POINTER(ArlConvGeom), _vp, _vp]),
     "arl_conv2d_bwd_weight_parts": (_i32, [_vp, _vp, _vp, C.POINTER(ArlConvGeom), _vp, _i64, C.POINTER(ArlFoldItem),
-                                           _vp, C.POINTER(ArlFoldItem), _vp]),
+                                           _vp, C.POINTER(ArlFoldItem), C.POINTER(ArlWgradPlan), _vp]),
     "arl_fold_many": (_i32, [C.POINTER(ArlFoldItem), _i32, _vp]),
-    "arl_conv2d_fwd_parts": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _i32, _vp, C.POINTER(ArlFoldItem), _vp]),
     "arl_conv2d_fwd_plan": (_i32, [C.POINTER(ArlConvGeom), C.POINTER(_i32), C.POINTER(_i32)]),
     "arl_serve_conv1_supported": (_i32, [C.POINTER(ArlGame), C.POINTER(ArlConvGeom)]),
     "arl_rollout_begin_conv1": (_i32, [C.POINTER(ArlGame), C.POINTER(ArlEnvState), C.POINTER(ArlRollout),
                                        C.POINTER(ArlServeConv1), _vp]),
     "arl_env_step_served": (_i32, [C.POINTER(ArlGame), C.POINTER(ArlEnvState), C.POINTER(ArlRollout),
                                    C.POINTER(ArlServeHead), C.POINTER(ArlServeConv1), _vp, _i32, _f64, _f64, _i32, _vp]),
-    "arl_conv2d_u8_fwd": (_i32, [_vp, _i64, _vp, _f32, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _i32, _vp]),
+    "arl_conv2d_u8_fwd": (_i32, [_vp, _i64, _vp, _f32, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _i32, _vp]),
     "arl_conv2d_u8_bwd_weight_parts": (_i32, [_vp, _vp, _i64, _vp, _f32, _vp, C.POINTER(ArlConvGeom), _vp, _i64,
-                                              C.POINTER(ArlFoldItem), _vp, C.POINTER(ArlFoldItem), _vp]),
-    "arl_conv2d_bwd_pair": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _vp, _i64,
+                                              C.POINTER(ArlFoldItem), _vp, C.POINTER(ArlFoldItem),
+                                              C.POINTER(ArlWgradPlan), _vp]),
+    "arl_conv2d_bwd_pair": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _vp, _i64,
                                    C.POINTER(ArlFoldItem), _vp, C.POINTER(ArlFoldItem), C.POINTER(ArlCorunJob),
-                                   C.POINTER(_i32), _vp]),
-    "arl_conv2d_bwd_weight_plan": (_i32, [_vp, _vp, _vp, C.POINTER(ArlConvGeom), _vp, _i64, C.POINTER(ArlFoldItem),
-                                          _vp, C.POINTER(ArlFoldItem), C.POINTER(ArlWgradPlan)]),
-    "arl_conv2d_u8_bwd_weight_plan": (_i32, [_vp, _vp, _i64, _vp, _f32, _vp, C.POINTER(ArlConvGeom), _vp, _i64,
-                                             C.POINTER(ArlFoldItem), _vp, C.POINTER(ArlFoldItem),
-                                             C.POINTER(ArlWgradPlan)]),
-    "arl_conv2d_bwd_pair_plan": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _vp, _i64,
-                                        C.POINTER(ArlFoldItem), _vp, C.POINTER(ArlFoldItem), C.POINTER(ArlCorunJob),
-                                        C.POINTER(_i32), C.POINTER(ArlWgradPlan), _vp]),
+                                   C.POINTER(_i32), C.POINTER(ArlWgradPlan), _vp]),
     "arl_conv2d_bwd_weight_group": (_i32, [C.POINTER(ArlWgradPlan), _i32, _vp]),
-    "arl_conv2d_fwd_bits": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _i32, _vp, _vp]),
-    "arl_conv2d_u8_fwd_bits": (_i32, [_vp, _i64, _vp, _f32, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _i32, _vp]),
-    "arl_conv2d_bwd_data_bits": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), C.POINTER(ArlCorunJob),
-                                        C.POINTER(_i32), _vp]),
-    "arl_conv2d_bwd_pair_bits": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ArlConvGeom), _vp, _i64,
-                                        C.POINTER(ArlFoldItem), _vp, C.POINTER(ArlFoldItem), C.POINTER(ArlCorunJob),
-                                        C.POINTER(_i32), C.POINTER(ArlWgradPlan), _vp]),
     "arl_relu_bwd_bias_parts": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, C.POINTER(ArlFoldItem), _vp]),
     "arl_replay_append": (_i32, [C.POINTER(ArlReplay), _vp, _vp, _vp, _vp, _i32, _i32, _f64, _i32, _vp]),
     "arl_replay_extract": (_i32, [C.POINTER(ArlReplay), _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -802,7 +788,7 @@ def conv_workspace(device):
 
 def relu_bits_shape(rows, channels):
     """Shape of the i32 tensor that holds an f32[rows][channels] activation's rectifier mask as bits (32 channels per
-    word, bit c % 32 of word c // 32 = y[row][c] > 0; accel_rl_hip.h: arl_conv2d_fwd_bits)."""
+    word, bit c % 32 of word c // 32 = y[row][c] > 0; accel_rl_hip.h: y_bits_or_null)."""
     assert channels % 32 == 0, "rectifier bits need a multiple of 32 channels"
     return (rows, channels // 32)
 
@@ -815,39 +801,29 @@ def _want_bits(bits, n_values, name):
         assert bits.numel() * 32 >= n_values, name + " size"
 
 
-def conv2d_fwd(x, w, bias, y, geom, relu, workspace, stream=None, y_bits=None):
-    """y[B,Ho,Wo,K] = act(conv(x[B,H,W,C], w[K,kh,kw,C]) + bias); all fp32 contiguous memory.
-    y_bits (i32, relu_bits_shape): the launch also writes y's rectifier mask as bits."""
+def _conv2d_fwd(x, w, bias, y, y_bits, geom, relu, workspace, item, stream):
     for t, n in ((x, "x"), (w, "w"), (y, "y")):
         _want(t, torch.float32, n)
     ho, wo = conv_out_hw(geom)
     assert x.numel() == geom.batch * geom.in_h * geom.in_w * geom.in_c, "x size"
     assert w.numel() == geom.out_c * geom.kh * geom.kw * geom.in_c, "w size"
     assert y.numel() == geom.batch * ho * wo * geom.out_c, "y size"
-    if y_bits is not None:
-        _want_bits(y_bits, y.numel(), "y_bits")
-        _check(load().arl_conv2d_fwd_bits(x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(),
-                                          y.data_ptr(), y_bits.data_ptr(), C.byref(geom), int(bool(relu)),
-                                          ptr(workspace), stream_ptr(stream)), "arl_conv2d_fwd_bits")
-        return
-    _check(load().arl_conv2d_fwd(x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(),
-                                 y.data_ptr(), C.byref(geom), int(bool(relu)), ptr(workspace),
-                                 stream_ptr(stream)), "arl_conv2d_fwd")
+    _want_bits(y_bits, y.numel(), "y_bits")
+    _check(load().arl_conv2d_fwd(x.data_ptr(), w.data_ptr(), ptr(bias), y.data_ptr(), ptr(y_bits), C.byref(geom),
+                                 int(bool(relu)), ptr(workspace), item, stream_ptr(stream)), "arl_conv2d_fwd")
+
+
+def conv2d_fwd(x, w, bias, y, geom, relu, workspace, stream=None, y_bits=None):
+    """y[B,Ho,Wo,K] = act(conv(x[B,H,W,C], w[K,kh,kw,C]) + bias); all fp32 contiguous memory.
+    y_bits (i32, relu_bits_shape): the launch also writes y's rectifier mask as bits."""
+    _conv2d_fwd(x, w, bias, y, y_bits, geom, relu, workspace, None, stream)
 
 
 def conv2d_fwd_parts(x, w, bias, y, geom, relu, workspace, stream=None):
     """conv2d_fwd that leaves a split reduction unfolded: returns the ArlFoldItem describing the partial sums in
     `workspace` (splits == 0: the launch did not split and y is final, bias / rectifier applied)."""
-    for t, n in ((x, "x"), (w, "w"), (y, "y")):
-        _want(t, torch.float32, n)
-    ho, wo = conv_out_hw(geom)
-    assert x.numel() == geom.batch * geom.in_h * geom.in_w * geom.in_c, "x size"
-    assert w.numel() == geom.out_c * geom.kh * geom.kw * geom.in_c, "w size"
-    assert y.numel() == geom.batch * ho * wo * geom.out_c, "y size"
     item = ArlFoldItem()
-    _check(load().arl_conv2d_fwd_parts(x.data_ptr(), w.data_ptr(), None if bias is None else bias.data_ptr(),
-                                       y.data_ptr(), C.byref(geom), int(bool(relu)), ptr(workspace), C.byref(item),
-                                       stream_ptr(stream)), "arl_conv2d_fwd_parts")
+    _conv2d_fwd(x, w, bias, y, None, geom, relu, workspace, C.byref(item), stream)
     return item
 
 
@@ -881,14 +857,9 @@ def conv2d_u8_fwd(obs, idx, scale, w, bias, y, geom, relu, stream=None, y_bits=N
     ho, wo = conv_out_hw(geom)
     assert w.numel() == geom.out_c * geom.kh * geom.kw * geom.in_c, "w size"
     assert y.numel() == geom.batch * ho * wo * geom.out_c, "y size"
-    if y_bits is not None:
-        _want_bits(y_bits, y.numel(), "y_bits")
-        _check(load().arl_conv2d_u8_fwd_bits(obs.data_ptr(), obs.shape[0], ptr(idx), float(scale), w.data_ptr(), ptr(bias),
-                                             y.data_ptr(), y_bits.data_ptr(), C.byref(geom), int(bool(relu)),
-                                             stream_ptr(stream)), "arl_conv2d_u8_fwd_bits")
-        return
+    _want_bits(y_bits, y.numel(), "y_bits")
     _check(load().arl_conv2d_u8_fwd(obs.data_ptr(), obs.shape[0], ptr(idx), float(scale), w.data_ptr(), ptr(bias),
-                                    y.data_ptr(), C.byref(geom), int(bool(relu)), stream_ptr(stream)),
+                                    y.data_ptr(), ptr(y_bits), C.byref(geom), int(bool(relu)), stream_ptr(stream)),
            "arl_conv2d_u8_fwd")
 
 
@@ -913,15 +884,10 @@ def conv2d_bwd_data(dy, w, mask, dx, geom, stream=None, corun=None, wt=None, mas
     assert dx.numel() == geom.batch * geom.in_h * geom.in_w * geom.in_c, "dx size"
     assert mask is None or mask.numel() == dx.numel()
     taken = _i32(0)
-    if mask_bits is not None:
-        _want_bits(mask_bits, dx.numel(), "mask_bits")
-        _check(load().arl_conv2d_bwd_data_bits(dy.data_ptr(), w.data_ptr(), ptr(wt), ptr(mask), mask_bits.data_ptr(),
-                                               dx.data_ptr(), C.byref(geom), None if corun is None else C.byref(corun),
-                                               C.byref(taken), stream_ptr(stream)), "arl_conv2d_bwd_data_bits")
-        return bool(taken.value)
-    _check(load().arl_conv2d_bwd_data(dy.data_ptr(), w.data_ptr(), ptr(wt), None if mask is None else mask.data_ptr(),
-                                      dx.data_ptr(), C.byref(geom), None if corun is None else C.byref(corun),
-                                      C.byref(taken), stream_ptr(stream)), "arl_conv2d_bwd_data")
+    _want_bits(mask_bits, dx.numel(), "mask_bits")
+    _check(load().arl_conv2d_bwd_data(dy.data_ptr(), w.data_ptr(), ptr(wt), ptr(mask), ptr(mask_bits), dx.data_ptr(),
+                                      C.byref(geom), None if corun is None else C.byref(corun), C.byref(taken),
+                                      stream_ptr(stream)), "arl_conv2d_bwd_data")
     return bool(taken.value)
 
 
@@ -990,14 +956,10 @@ class FoldList(object):
         assert dw.numel() == geom.out_c * geom.kh * geom.kw * geom.in_c, "dw size"
         item = self._next()
         pb, ib = self._bias_slot(dbias)
-        if defer:
-            _check(load().arl_conv2d_bwd_weight_plan(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), C.byref(geom),
-                                                     ptr(workspace), workspace.numel() * workspace.element_size(),
-                                                     item, pb, ib, self._next_plan(stream)), "arl_conv2d_bwd_weight_plan")
-            return self._bias_done(dbias)
         _check(load().arl_conv2d_bwd_weight_parts(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), C.byref(geom),
                                                   ptr(workspace), workspace.numel() * workspace.element_size(),
-                                                  item, pb, ib, stream_ptr(stream)), "arl_conv2d_bwd_weight_parts")
+                                                  item, pb, ib, self._next_plan(stream) if defer else None,
+                                                  stream_ptr(stream)), "arl_conv2d_bwd_weight_parts")
         return self._bias_done(dbias)
 
     def conv2d_u8_bwd_weight(self, dy, obs, idx, scale, dw, geom, workspace, dbias=None, stream=None, defer=False):
@@ -1008,16 +970,11 @@ class FoldList(object):
         assert dw.numel() == geom.out_c * geom.kh * geom.kw * geom.in_c, "dw size"
         item = self._next()
         pb, ib = self._bias_slot(dbias)
-        if defer:
-            _check(load().arl_conv2d_u8_bwd_weight_plan(dy.data_ptr(), obs.data_ptr(), obs.shape[0], ptr(idx),
-                                                        float(scale), dw.data_ptr(), C.byref(geom), ptr(workspace),
-                                                        workspace.numel() * workspace.element_size(), item, pb, ib,
-                                                        self._next_plan(stream)), "arl_conv2d_u8_bwd_weight_plan")
-            return self._bias_done(dbias)
         _check(load().arl_conv2d_u8_bwd_weight_parts(dy.data_ptr(), obs.data_ptr(), obs.shape[0], ptr(idx),
                                                      float(scale), dw.data_ptr(), C.byref(geom), ptr(workspace),
                                                      workspace.numel() * workspace.element_size(), item, pb, ib,
-                                                     stream_ptr(stream)), "arl_conv2d_u8_bwd_weight_parts")
+                                                     self._next_plan(stream) if defer else None, stream_ptr(stream)),
+               "arl_conv2d_u8_bwd_weight_parts")
         return self._bias_done(dbias)
 
     def conv2d_bwd_pair(self, dy, w, mask, dx, x, dw, geom, workspace, dbias=None, stream=None, corun=None, wt=None,
@@ -1035,27 +992,13 @@ class FoldList(object):
         slot = self._n - 1
         pb, ib = self._bias_slot(dbias)
         taken = _i32(0)
-        if mask_bits is not None:
-            _want_bits(mask_bits, dx.numel(), "mask_bits")
-            _check(load().arl_conv2d_bwd_pair_bits(dy.data_ptr(), w.data_ptr(), ptr(wt), ptr(mask), mask_bits.data_ptr(),
-                                                   dx.data_ptr(), x.data_ptr(), dw.data_ptr(), C.byref(geom),
-                                                   ptr(workspace), workspace.numel() * workspace.element_size(), item,
-                                                   pb, ib, None if corun is None else C.byref(corun), C.byref(taken),
-                                                   self._next_plan(stream) if defer else None, stream_ptr(stream)),
-                   "arl_conv2d_bwd_pair_bits")
-        elif defer:
-            _check(load().arl_conv2d_bwd_pair_plan(dy.data_ptr(), w.data_ptr(), ptr(wt), ptr(mask), dx.data_ptr(),
-                                                   x.data_ptr(), dw.data_ptr(), C.byref(geom), ptr(workspace),
-                                                   workspace.numel() * workspace.element_size(), item, pb, ib,
-                                                   None if corun is None else C.byref(corun), C.byref(taken),
-                                                   self._next_plan(stream), stream_ptr(stream)),
-                   "arl_conv2d_bwd_pair_plan")
-        else:
-            _check(load().arl_conv2d_bwd_pair(dy.data_ptr(), w.data_ptr(), ptr(wt), ptr(mask), dx.data_ptr(), x.data_ptr(),
-                                              dw.data_ptr(), C.byref(geom), ptr(workspace),
-                                              workspace.numel() * workspace.element_size(), item, pb, ib,
-                                              None if corun is None else C.byref(corun), C.byref(taken),
-                                              stream_ptr(stream)), "arl_conv2d_bwd_pair")
+        _want_bits(mask_bits, dx.numel(), "mask_bits")
+        _check(load().arl_conv2d_bwd_pair(dy.data_ptr(), w.data_ptr(), ptr(wt), ptr(mask), ptr(mask_bits), dx.data_ptr(),
+                                          x.data_ptr(), dw.data_ptr(), C.byref(geom), ptr(workspace),
+                                          workspace.numel() * workspace.element_size(), item, pb, ib,
+                                          None if corun is None else C.byref(corun), C.byref(taken),
+                                          self._next_plan(stream) if defer else None, stream_ptr(stream)),
+               "arl_conv2d_bwd_pair")
         self.corun_taken = bool(taken.value)
         self.last_dw_in_place = self._items[slot].splits == 0      # no split partials: dw is final as written
         return self._bias_done(dbias)
@@ -2087,7 +2030,7 @@ def noisy_noise(state, layers, rows, rows_per_draw, stream=None):
 
 def noisy_dense_combine(w_item, bias, s_item, b_sigma, feout, y, relu, fein_next=None, xs_next=None, state=None,
                         stream=None):
-    """y[rows, units] = relu?(P_w + f(e_out) * P_sigma) from the two arl_conv2d_fwd_parts items (arl_noisy_dense_combine)."""
+    """y[rows, units] = relu?(P_w + f(e_out) * P_sigma) from the two conv2d_fwd_parts items (arl_noisy_dense_combine)."""
     rows, units = y.shape
     assert feout.numel() == y.numel(), "feout size"
     assert fein_next is None or (fein_next.numel() == xs_next.numel() == y.numel()), "fein_next / xs_next size"

@@ -60,7 +60,7 @@ __device__ __forceinline__ float atom_softmax(float x, int lane, int n_atoms) {
 }
 
 // Where a sample's logit block [A (+ 1)][stride] is read from: the finished logits, or (Parts) the output layer's split
-// partial sums as arl_conv2d_fwd_parts left them -- logit = fold_splits_kernel's sum of the partials + bias, operation for
+// partial sums as arl_conv2d_fwd's item has them -- logit = fold_splits_kernel's sum of the partials + bias, operation for
 // operation (its 16 lanes-of-a-group partial sums s_g = 0 + p_g + p_{g+16} + ..., then s_0 + s_1 + ... + s_15, then the bias),
 // so that the loss kernel can take the place of the fold launch without moving a bit.
 struct Plain {

@@ -10,6 +10,10 @@
 //   arl_conv2d_bwd_data    dx = conv^T(dy, w) [* (act > 0)]  implicit GEMM per stride-parity class
 //   arl_conv2d_bwd_weight  dw = sum_m dy[m]^T im2col(x)[m]   split over m, fixed-order fold
 //
+// and, one entry point each (optional operands are _or_null arguments: rectifier bits, an unfolded split, a plan):
+// arl_conv2d_u8_fwd (conv 1 from u8 rows), arl_conv2d_bwd_weight_parts / arl_conv2d_u8_bwd_weight_parts (deferred fold,
+// or planned for arl_conv2d_bwd_weight_group), arl_conv2d_bwd_pair (data + weight gradient in one launch).
+//
 // A dense layer is the 1x1 convolution on a 1x1 image (H = W = kh = kw = 1, C = fan_in).
 // Layouts: activations NHWC fp32, weights (K, kh, kw, C) ("OHWI", correlation kernels),
 // gradients in the same layouts.  All channel counts are multiples of 4 so that every

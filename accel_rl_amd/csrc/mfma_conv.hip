@@ -182,9 +182,9 @@ bool fwd_plan(int M, int N, int K, int* splits, int* per) {
     return small;
 }
 
-// parts: leave a split reduction unfolded and describe it (arl_conv2d_fwd_parts); null = fold here
+// parts: leave a split reduction unfolded and describe it; null = fold here
 int fwd_impl(const float* x, const float* w, const float* bias_or_null, float* y, const arl_conv_geom* geom, int32_t relu,
-             void* workspace, void* stream, arl_fold_item* parts = nullptr, uint32_t* y_bits = nullptr) {
+             void* workspace, void* stream, arl_fold_item* parts, uint32_t* y_bits) {
     Geom g;
     int rc = check_geom(geom, &g);
     if (rc) return rc;
@@ -286,14 +286,6 @@ namespace arlc {
 int fold_wide_from() { return g_fold_wide; }
 }
 
-extern "C" int arl_conv2d_fwd_parts(const float* x, const float* w, const float* bias_or_null, float* y,
-                                    const arl_conv_geom* geom, int32_t relu, void* workspace, arl_fold_item* item,
-                                    void* stream) {
-    ARL_REQUIRE(item, ARL_E_ARG, "null pointer");
-    ARL_ROUTE_SCOPE(geom, nullptr);
-    return fwd_impl(x, w, bias_or_null, y, geom, relu, workspace, stream, item);
-}
-
 extern "C" int arl_conv2d_fwd_plan(const arl_conv_geom* geom, int32_t* splits, int32_t* k_per_split) {
     ARL_REQUIRE(splits && k_per_split, ARL_E_ARG, "null pointer");
     ARL_REQUIRE(split_of(geom) >= 0, ARL_E_ARG, "conv route: ARL_CONV_ROUTE_SPLIT9, _FP32, _SPLIT6 or _BF16");
@@ -310,16 +302,10 @@ extern "C" int arl_conv2d_fwd_plan(const arl_conv_geom* geom, int32_t* splits, i
 }
 
 extern "C" int arl_conv2d_fwd(const float* x, const float* w, const float* bias_or_null, float* y,
-                              const arl_conv_geom* geom, int32_t relu, void* workspace, void* stream) {
+                              uint32_t* y_bits_or_null, const arl_conv_geom* geom, int32_t relu, void* workspace,
+                              arl_fold_item* item_or_null, void* stream) {
     ARL_ROUTE_SCOPE(geom, nullptr);
-    return fwd_impl(x, w, bias_or_null, y, geom, relu, workspace, stream);
-}
-
-extern "C" int arl_conv2d_fwd_bits(const float* x, const float* w, const float* bias_or_null, float* y,
-                                   uint32_t* y_bits_or_null, const arl_conv_geom* geom, int32_t relu, void* workspace,
-                                   void* stream) {
-    ARL_ROUTE_SCOPE(geom, nullptr);
-    return fwd_impl(x, w, bias_or_null, y, geom, relu, workspace, stream, nullptr, y_bits_or_null);
+    return fwd_impl(x, w, bias_or_null, y, geom, relu, workspace, stream, item_or_null, y_bits_or_null);
 }
 
 namespace {
@@ -332,6 +318,7 @@ namespace {
 int dgrad_impl(const float* dy, const float* w, const float* mask_or_null, float* dx, const arl_conv_geom* geom,
                DgradPlan* plan_only, void* stream, void* workspace = nullptr, int64_t workspace_bytes = 0,
                const float* wt = nullptr, const uint32_t* mask_bits = nullptr) {
+    ARL_REQUIRE(geom, ARL_E_ARG, "null pointer");   // (as the pair and the u8 calls report it)
     Geom g;
     int rc = check_geom(geom, &g);
     if (rc) return rc;
@@ -568,14 +555,8 @@ int wgrad_impl(const float* dy, const float* x, float* dw, const arl_conv_geom* 
 }  // namespace
 
 extern "C" int arl_conv2d_bwd_data(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
-                                   float* dx, const arl_conv_geom* geom, const arl_corun_job* job_or_null,
-                                   int32_t* job_taken_or_null, void* stream) {
-    return arl_conv2d_bwd_data_bits(dy, w, wt_or_null, mask_or_null, nullptr, dx, geom, job_or_null, job_taken_or_null, stream);
-}
-
-extern "C" int arl_conv2d_bwd_data_bits(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
-                                        const uint32_t* mask_bits_or_null, float* dx, const arl_conv_geom* geom,
-                                        const arl_corun_job* job_or_null, int32_t* job_taken_or_null, void* stream) {
+                                   const uint32_t* mask_bits_or_null, float* dx, const arl_conv_geom* geom,
+                                   const arl_corun_job* job_or_null, int32_t* job_taken_or_null, void* stream) {
     ARL_ROUTE_SCOPE(geom, job_or_null);
     const int rc = dgrad_impl(dy, w, mask_or_null, dx, geom, nullptr, stream, nullptr, 0, wt_or_null, mask_bits_or_null);
     if (job_taken_or_null) *job_taken_or_null = t_ctx.corun_taken ? 1 : 0;
@@ -600,8 +581,7 @@ void bias_item(arl_fold_item* item, const float* bias_part, float* dbias, int sp
 }
 int wgrad_parts_impl(const float* dy, const float* x, float* dw, const arl_conv_geom* geom,
                      void* workspace, int64_t workspace_bytes, arl_fold_item* item,
-                     float* dbias_or_null, arl_fold_item* bias_item_or_null, void* stream,
-                     WgradPlan* plan_only = nullptr) {
+                     float* dbias_or_null, arl_fold_item* bias_item_or_null, void* stream, WgradPlan* plan_only) {
     ARL_REQUIRE(item && (!dbias_or_null || bias_item_or_null), ARL_E_ARG, "null pointer");
     ARL_REQUIRE(!dbias_or_null || arl::aligned16(dbias_or_null), ARL_E_ALIGN, "16-byte alignment");
     int splits = 1;
@@ -617,23 +597,16 @@ int wgrad_parts_impl(const float* dy, const float* x, float* dw, const arl_conv_
 }
 }  // namespace
 
-extern "C" int arl_conv2d_bwd_weight_parts(const float* dy, const float* x, float* dw, const arl_conv_geom* geom,
-                                           void* workspace, int64_t workspace_bytes, arl_fold_item* item,
-                                           float* dbias_or_null, arl_fold_item* bias_item_or_null, void* stream) {
-    ARL_ROUTE_SCOPE(geom, nullptr);
-    return wgrad_parts_impl(dy, x, dw, geom, workspace, workspace_bytes, item, dbias_or_null, bias_item_or_null, stream);
-}
-
 static_assert(sizeof(WgradPlan) <= sizeof(arl_wgrad_plan), "arl_wgrad_plan too small");
 
-extern "C" int arl_conv2d_bwd_weight_plan(const float* dy, const float* x, float* dw, const arl_conv_geom* geom,
-                                          void* workspace, int64_t workspace_bytes, arl_fold_item* item,
-                                          float* dbias_or_null, arl_fold_item* bias_item_or_null, arl_wgrad_plan* plan) {
-    ARL_REQUIRE(plan, ARL_E_ARG, "null pointer");
-    *plan = arl_wgrad_plan{};
+extern "C" int arl_conv2d_bwd_weight_parts(const float* dy, const float* x, float* dw, const arl_conv_geom* geom,
+                                           void* workspace, int64_t workspace_bytes, arl_fold_item* item,
+                                           float* dbias_or_null, arl_fold_item* bias_item_or_null,
+                                           arl_wgrad_plan* plan_or_null, void* stream) {
+    if (plan_or_null) *plan_or_null = arl_wgrad_plan{};             // (kind 0: nothing left to launch)
     ARL_ROUTE_SCOPE(geom, nullptr);
-    return wgrad_parts_impl(dy, x, dw, geom, workspace, workspace_bytes, item, dbias_or_null, bias_item_or_null, nullptr,
-                            reinterpret_cast<WgradPlan*>(plan));
+    return wgrad_parts_impl(dy, x, dw, geom, workspace, workspace_bytes, item, dbias_or_null, bias_item_or_null, stream,
+                            reinterpret_cast<WgradPlan*>(plan_or_null));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -671,14 +644,8 @@ void fill_u8(GatherDesc* d, const uint8_t* obs, int64_t obs_rows, const int32_t*
 }  // namespace
 
 extern "C" int arl_conv2d_u8_fwd(const uint8_t* obs, int64_t obs_rows, const int32_t* idx_or_null, float scale,
-                                 const float* w, const float* bias_or_null, float* y, const arl_conv_geom* geom,
-                                 int32_t relu, void* stream) {
-    return arl_conv2d_u8_fwd_bits(obs, obs_rows, idx_or_null, scale, w, bias_or_null, y, nullptr, geom, relu, stream);
-}
-
-extern "C" int arl_conv2d_u8_fwd_bits(const uint8_t* obs, int64_t obs_rows, const int32_t* idx_or_null, float scale,
-                                      const float* w, const float* bias_or_null, float* y, uint32_t* y_bits_or_null,
-                                      const arl_conv_geom* geom, int32_t relu, void* stream) {
+                                 const float* w, const float* bias_or_null, float* y, uint32_t* y_bits_or_null,
+                                 const arl_conv_geom* geom, int32_t relu, void* stream) {
     launch_log_clear();                             // (the scope opens only after the geometry checks)
     ARL_REQUIRE(w && y, ARL_E_ARG, "null pointer");
     U8Geom g;
@@ -789,29 +756,19 @@ extern "C" int arl_conv2d_u8_bwd_weight_parts(const float* dy, const uint8_t* ob
                                               const int32_t* idx_or_null, float scale, float* dw,
                                               const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes,
                                               arl_fold_item* item, float* dbias_or_null,
-                                              arl_fold_item* bias_item_or_null, void* stream) {
+                                              arl_fold_item* bias_item_or_null, arl_wgrad_plan* plan_or_null,
+                                              void* stream) {
+    if (plan_or_null) *plan_or_null = arl_wgrad_plan{};
     return wgrad_u8_impl(dy, obs, obs_rows, idx_or_null, scale, dw, geom, workspace, workspace_bytes, item, dbias_or_null,
-                         bias_item_or_null, nullptr, stream);
+                         bias_item_or_null, reinterpret_cast<WgradPlan*>(plan_or_null), stream);
 }
-
-extern "C" int arl_conv2d_u8_bwd_weight_plan(const float* dy, const uint8_t* obs, int64_t obs_rows,
-                                             const int32_t* idx_or_null, float scale, float* dw,
-                                             const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes,
-                                             arl_fold_item* item, float* dbias_or_null,
-                                             arl_fold_item* bias_item_or_null, arl_wgrad_plan* plan) {
-    ARL_REQUIRE(plan, ARL_E_ARG, "null pointer");
-    *plan = arl_wgrad_plan{};
-    return wgrad_u8_impl(dy, obs, obs_rows, idx_or_null, scale, dw, geom, workspace, workspace_bytes, item, dbias_or_null,
-                         bias_item_or_null, reinterpret_cast<WgradPlan*>(plan), nullptr);
-}
-
 
 namespace {
 // defer: the weight gradient of a layer that does not pair is planned into *defer instead of launched
 int pair_impl(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null, float* dx, const float* x,
               float* dw, const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes, arl_fold_item* item,
               float* dbias_or_null, arl_fold_item* bias_item_or_null, const arl_corun_job* job_or_null,
-              int32_t* job_taken_or_null, WgradPlan* defer, void* stream, const uint32_t* mask_bits = nullptr) {
+              int32_t* job_taken_or_null, WgradPlan* defer, void* stream, const uint32_t* mask_bits) {
     ARL_REQUIRE(item && geom && (!dbias_or_null || bias_item_or_null), ARL_E_ARG, "null pointer");
     if (job_taken_or_null) *job_taken_or_null = 0;
     ARL_ROUTE_SCOPE(geom, job_or_null);
@@ -862,36 +819,15 @@ int pair_impl(const float* dy, const float* w, const float* wt_or_null, const fl
 }  // namespace
 
 extern "C" int arl_conv2d_bwd_pair(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
-                                   float* dx, const float* x, float* dw, const arl_conv_geom* geom, void* workspace,
-                                   int64_t workspace_bytes, arl_fold_item* item, float* dbias_or_null,
-                                   arl_fold_item* bias_item_or_null, const arl_corun_job* job_or_null,
-                                   int32_t* job_taken_or_null, void* stream) {
-    return pair_impl(dy, w, wt_or_null, mask_or_null, dx, x, dw, geom, workspace, workspace_bytes, item, dbias_or_null,
-                     bias_item_or_null, job_or_null, job_taken_or_null, nullptr, stream);
-}
-
-// plan_or_null: as arl_conv2d_bwd_pair_plan (null: as arl_conv2d_bwd_pair)
-extern "C" int arl_conv2d_bwd_pair_bits(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
-                                        const uint32_t* mask_bits_or_null, float* dx, const float* x, float* dw,
-                                        const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes,
-                                        arl_fold_item* item, float* dbias_or_null, arl_fold_item* bias_item_or_null,
-                                        const arl_corun_job* job_or_null, int32_t* job_taken_or_null,
-                                        arl_wgrad_plan* plan_or_null, void* stream) {
-    if (plan_or_null) *plan_or_null = arl_wgrad_plan{};
+                                   const uint32_t* mask_bits_or_null, float* dx, const float* x, float* dw,
+                                   const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes,
+                                   arl_fold_item* item, float* dbias_or_null, arl_fold_item* bias_item_or_null,
+                                   const arl_corun_job* job_or_null, int32_t* job_taken_or_null,
+                                   arl_wgrad_plan* plan_or_null, void* stream) {
+    if (plan_or_null) *plan_or_null = arl_wgrad_plan{};             // (kind 0: nothing left to launch)
     return pair_impl(dy, w, wt_or_null, mask_or_null, dx, x, dw, geom, workspace, workspace_bytes, item, dbias_or_null,
                      bias_item_or_null, job_or_null, job_taken_or_null, reinterpret_cast<WgradPlan*>(plan_or_null), stream,
                      mask_bits_or_null);
-}
-
-extern "C" int arl_conv2d_bwd_pair_plan(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
-                                        float* dx, const float* x, float* dw, const arl_conv_geom* geom, void* workspace,
-                                        int64_t workspace_bytes, arl_fold_item* item, float* dbias_or_null,
-                                        arl_fold_item* bias_item_or_null, const arl_corun_job* job_or_null,
-                                        int32_t* job_taken_or_null, arl_wgrad_plan* plan, void* stream) {
-    ARL_REQUIRE(plan, ARL_E_ARG, "null pointer");
-    *plan = arl_wgrad_plan{};                       // (kind 0: nothing left to launch)
-    return pair_impl(dy, w, wt_or_null, mask_or_null, dx, x, dw, geom, workspace, workspace_bytes, item, dbias_or_null,
-                     bias_item_or_null, job_or_null, job_taken_or_null, reinterpret_cast<WgradPlan*>(plan), stream);
 }
 
 // The planned weight gradients of a backward pass: the group-eligible ones (a bf16-split route, one of

@@ -314,8 +314,8 @@ inline int check_geom(const arl_conv_geom* g, Geom* o) {
     return 0;
 }
 
-// A rectifier mask as bits (arl_conv2d_*_bits): u32[rows][channels / 32], bit c % 32 of word c / 32 = (y[row][c] > 0).
-// Null = not asked for; anything the kernels cannot serve is refused, never ignored.
+// A rectifier mask as bits (y_bits_or_null, mask_bits_or_null): u32[rows][channels / 32], bit c % 32 of word c / 32 =
+// (y[row][c] > 0).  Null = not asked for; anything the kernels cannot serve is refused, never ignored.
 inline int check_relu_bits(const void* bits, int channels) {
     if (!bits) return 0;
     ARL_REQUIRE(channels % 32 == 0, ARL_E_RANGE, "rectifier bits: the channel count must be a multiple of 32");

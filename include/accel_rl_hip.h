@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ARL_ABI_VERSION 4
+#define ARL_ABI_VERSION 5
 
 #define ARL_E_ARG      (-1)   /* null pointer / non-positive size                 */
 #define ARL_E_RANGE    (-2)   /* size outside what the kernels support             */
@@ -736,26 +736,75 @@ typedef struct arl_conv_geom {
 /* Scratch for the split reductions below (fixed; the caller allocates once). */
 int64_t arl_conv_workspace_bytes(void);
 
+/* One entry point per operation; an optional operand is an `_or_null` argument, and NULL there changes nothing about what
+ * the others do (bit for bit and launch for launch).
+ *
+ * Rectifier masks as bits (y_bits_or_null, mask_bits_or_null below).  A data gradient uses one thing of every value of
+ * its f32 mask: whether it is > 0.  For an activation tensor y f32[rows][C] with C % 32 == 0 (rows in the tensor's own NHWC
+ * order) the mask as bits is u32[rows][C / 32]: bit c % 32 of word c / 32 = (y[row][c] > 0.f) as the device evaluates it on
+ * the stored value (NaN and -0 give 0, as in the f32 comparison) -- 1/32 of the bytes.  ARL_E_ALIGN unless 4-byte aligned.
+ * The reference has no counterpart: Theano keeps the rectifier's input for T.grad (pg_cnn.py:47-68).                    */
+
 /* y = conv(x, w) + bias, then max(., 0) if relu.  Replaces the forward of Lasagne's
  * Conv2DLayer / DenseLayer as used by PgCnn (accel_rl/policies/pg/networks/pg_cnn.py:47-68,
  * policies/layers.py:22-41; the reference's flipped filters are stored pre-flipped).
- * Deterministic: fp32 MFMA accumulation in k order, split-K folded in a fixed order. */
-int arl_conv2d_fwd(const float* x, const float* w, const float* bias_or_null, float* y,
-                   const arl_conv_geom* geom, int32_t relu, void* workspace, void* stream);
+ * Deterministic: fp32 MFMA accumulation in k order, split-K folded in a fixed order.
+ * y_bits_or_null: the launch also writes y's mask as bits; y itself is written as ever.  Served on the bf16-split routes by
+ *   the kernels of layers with 32 .. 64 output columns whose k-tiles hold one filter tap (in_c % 32 == 0: the learner's
+ *   conv 2 and conv 3); ARL_E_RANGE -- nothing launched, never ignored -- for out_c % 32 != 0, a reduction that the call
+ *   splits (the fold writes y; with item_or_null too), the fp32 route, wider or multi-tap layers and the generic kernels.
+ * item_or_null: non-NULL leaves a split reduction unfolded and describes it, NULL folds here.  When the launch split its
+ *   reduction the partial sums stay in `workspace` and *item describes them (part f32[splits][rows * out_c], total = rows
+ *   * out_c; bias and rectifier NOT applied: they belong to whoever folds -- arl_env_step_served below does, per env,
+ *   inside its launch); item->splits == 0: the launch did not split, y is final (bias and rectifier applied).  The
+ *   workspace stays live until the consumer has run.                                                                  */
+int arl_conv2d_fwd(const float* x, const float* w, const float* bias_or_null, float* y, uint32_t* y_bits_or_null,
+                   const arl_conv_geom* geom, int32_t relu, void* workspace, arl_fold_item* item_or_null, void* stream);
+/* How arl_conv2d_fwd walks this geometry's reduction (host-side, nothing launched): *splits = the number of
+ * partial sums per output (1: not split) and *k_per_split = the reduction indices of one.  Two geometries of one layer
+ * that differ only in `batch` give every row the same bits when both numbers agree and the route is one of the
+ * bf16-split ones (ARL_CONV_ROUTE_SPLIT9 / _SPLIT6): their kernels issue the same piece products in the same k order
+ * whatever the tile shape the launch's size picks, and the fold's order depends on the split count alone.  A caller
+ * that wants to reuse rows computed at another batch size (the rollout's activations in the learner) asks here.
+ * NULL pointers, a bad geometry or route: as arl_conv2d_fwd.                                                        */
+int arl_conv2d_fwd_plan(const arl_conv_geom* geom, int32_t* splits, int32_t* k_per_split);
+
+/* Convolution 1 read straight from the sampler's observations (no f32 copy of the input):
+ * obs u8[obs_rows][in_c][in_h][in_w] (the layout of samples_buf.observations,
+ * accel_rl/sampler/act_server/buffers.py:7-38), row b of the batch = obs[idx ? idx[b] : b]
+ * (the minibatch indices of optimizers/util.py:8-18), x = float(byte) * scale
+ * (atari_cnn_policy.py:88-91: the network input is obs * (1 / 255)).  Weights and their gradient are
+ * f32[out_c][in_c][kh][kw] (correlation kernels).  geom->batch = rows of the batch; in_c any count >= 1.
+ * Requires pad 0, stride % 4 == 0, in_w % 4 == 0, (in_h * in_w) % 4 == 0, kw in {4, 8, 16},
+ * kh % (16 / kw) == 0, out_c % 4 == 0 and <= 32 (else ARL_E_RANGE: use arl_gather_scale_obs_nhwc +
+ * arl_conv2d_fwd).  The sums run over the exact integer pixels, plane by plane, and `scale` multiplies the
+ * finished sum once (a convolution is linear in its input: y = scale * conv(byte, w) + bias) -- equal to the
+ * gather + scale route up to f32 round-off, not bit for bit.
+ * y_bits_or_null: as arl_conv2d_fwd's.  Served on the bf16-split routes with 32 filters (the image-stationary kernel, or
+ *   the tap-gathering split kernel where that one does not run); ARL_E_RANGE, nothing launched, anywhere else.  */
+int arl_conv2d_u8_fwd(const uint8_t* obs, int64_t obs_rows, const int32_t* idx_or_null, float scale,
+                      const float* w, const float* bias_or_null, float* y, uint32_t* y_bits_or_null,
+                      const arl_conv_geom* geom, int32_t relu, void* stream);
 
 /* dx = gradient of the layer input given dy (every element of dx is written).
  * If mask is given (same shape as dx): dx = 0 where mask <= 0 -- the rectifier
  * backward of the previous layer.  Requires kh % stride == 0 and kw % stride == 0.
- * Replaces the T.grad of the same layers (optimizers/single/ppo_optimizer.py:38-40). */
-/* job (optional): an optimiser job (arl_corun_job, below) that this call's launch may carry in extra workgroups;
- * *job_taken = 1 if it did (only the scalar-addressed data-gradient launches of layers with > 16 input channels
- * can), else 0 and the caller runs the job itself (arl_corun_job_run). */
+ * Replaces the T.grad of the same layers (optimizers/single/ppo_optimizer.py:38-40).
+ * wt_or_null: arl_conv2d_dgrad_weights' copy of w (below).
+ * mask_bits_or_null: the mask of mask_or_null as bits, from a forward call's y_bits on the same tensor.  It comes on top of
+ *   mask_or_null (ARL_E_ARG without it): the bf16-split launches of 17 .. 64 input channels on the k-contiguous weight
+ *   copy (wt) and the shared launch of arl_conv2d_bwd_pair test the bit and never read the floats; every other launch
+ *   (fp32 route, no wt, 16-wide tiles, generic kernels, the split reduction's fold) compares the floats as before.  dx
+ *   is the same bits either way.  ARL_E_RANGE for in_c % 32 != 0.
+ * job (optional): an optimiser job (arl_corun_job, below) that this call's launch may carry in extra workgroups;
+ *   *job_taken = 1 if it did (only the scalar-addressed data-gradient launches of layers with > 16 input channels
+ *   can), else 0 and the caller runs the job itself (arl_corun_job_run). */
 struct arl_corun_job;
-int arl_conv2d_bwd_data(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null, float* dx,
-                        const arl_conv_geom* geom, const struct arl_corun_job* job_or_null,
-                        int32_t* job_taken_or_null, void* stream);
+int arl_conv2d_bwd_data(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
+                        const uint32_t* mask_bits_or_null, float* dx, const arl_conv_geom* geom,
+                        const struct arl_corun_job* job_or_null, int32_t* job_taken_or_null, void* stream);
 
-/* The data gradient's own copy of a layer's weights (ABI 4): per input-pixel parity class (ph, pw) of the stride a matrix
+/* The data gradient's own copy of a layer's weights: per input-pixel parity class (ph, pw) of the stride a matrix
  * wt[ph * stride + pw][in_c][(ty * kw / stride + tx) * out_c + k] = w[k][i0 + stride ty][j0 + stride tx][c], (i0, j0) =
  * ((ph + pad_h) % stride, (pw + pad_w) % stride) -- the reduction index of dx = conv^T(dy, w) contiguous, as a forward pass
  * finds its weights.  Same size as w; one launch converts up to ARL_DGRAD_WT_MAX layers (after every parameter update,
@@ -777,31 +826,57 @@ int arl_conv2d_dgrad_weights(const arl_dgrad_wt* items, int32_t n, void* stream)
 int arl_conv2d_bwd_weight(const float* dy, const float* x, float* dw, const arl_conv_geom* geom,
                           void* workspace, void* stream);
 
-/* Deferred-fold variant (arl_fold_item above). */
-/* dbias (optional): the kernel also leaves per-split column sums of dy (the bias gradient of a layer
- * whose dy is already masked by its rectifier) behind the weight partials and describes their fold in
- * *bias_item; bias_item->splits == -1 means "not produced" (the generic kernels ran): use
- * arl_relu_bwd_bias_grad / _parts instead. */
+/* A weight gradient described instead of launched (plan_or_null below; run by arl_conv2d_bwd_weight_group). */
+typedef struct arl_wgrad_plan { int64_t opaque[32]; } arl_wgrad_plan;
+
+/* Deferred-fold variant (arl_fold_item above; arl_fold_many folds).
+ * dbias (optional): the kernel also leaves per-split column sums of dy (the bias gradient of a layer
+ *   whose dy is already masked by its rectifier) behind the weight partials and describes their fold in
+ *   *bias_item; bias_item->splits == -1 means "not produced" (the generic kernels ran): use
+ *   arl_relu_bwd_bias_grad / _parts instead.
+ * plan_or_null: non-NULL plans only -- the call validates, plans the row split and fills the fold item(s) exactly as
+ *   with NULL (same workspace, same split count, same partial layout, same bias partials), describes its launch in
+ *   *plan and launches nothing; `stream` is not used. */
 int arl_conv2d_bwd_weight_parts(const float* dy, const float* x, float* dw, const arl_conv_geom* geom,
                                 void* workspace, int64_t workspace_bytes, arl_fold_item* item,
-                                float* dbias_or_null, arl_fold_item* bias_item_or_null, void* stream);
+                                float* dbias_or_null, arl_fold_item* bias_item_or_null, arl_wgrad_plan* plan_or_null,
+                                void* stream);
+/* The same for arl_conv2d_u8_fwd's layer. */
+int arl_conv2d_u8_bwd_weight_parts(const float* dy, const uint8_t* obs, int64_t obs_rows,
+                                   const int32_t* idx_or_null, float scale, float* dw,
+                                   const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes,
+                                   arl_fold_item* item, float* dbias_or_null,
+                                   arl_fold_item* bias_item_or_null, arl_wgrad_plan* plan_or_null, void* stream);
 int arl_fold_many(const arl_fold_item* items, int32_t n, void* stream);
 
-/* Forward with the split reduction left unfolded: as arl_conv2d_fwd, but when the launch split its reduction the partial
- * sums stay in `workspace` and *item describes them (part f32[splits][rows * out_c], total = rows * out_c; bias and
- * rectifier NOT applied: they belong to whoever folds -- arl_env_step_served below does, per env, inside its launch);
- * item->splits == 0: the launch did not split, y is final (bias and rectifier applied).  The workspace stays live until
- * the consumer has run.  Replaces the same Lasagne DenseLayer forward as arl_conv2d_fwd (pg_cnn.py:57-68).          */
-int arl_conv2d_fwd_parts(const float* x, const float* w, const float* bias_or_null, float* y,
-                         const arl_conv_geom* geom, int32_t relu, void* workspace, arl_fold_item* item, void* stream);
-/* How arl_conv2d_fwd / _parts walk this geometry's reduction (host-side, nothing launched): *splits = the number of
- * partial sums per output (1: not split) and *k_per_split = the reduction indices of one.  Two geometries of one layer
- * that differ only in `batch` give every row the same bits when both numbers agree and the route is one of the
- * bf16-split ones (ARL_CONV_ROUTE_SPLIT9 / _SPLIT6): their kernels issue the same piece products in the same k order
- * whatever the tile shape the launch's size picks, and the fold's order depends on the split count alone.  A caller
- * that wants to reuse rows computed at another batch size (the rollout's activations in the learner) asks here.
- * NULL pointers, a bad geometry or route: as arl_conv2d_fwd.                                                        */
-int arl_conv2d_fwd_plan(const arl_conv_geom* geom, int32_t* splits, int32_t* k_per_split);
+/* A layer's data gradient and weight gradient (deferred fold) as ONE launch: the two are independent
+ * and both read dy, so their workgroups share a grid -- one ramp-up and one tail instead of two, and
+ * the second problem's workgroups fill the CUs the first one's last wave leaves idle.  Same results as
+ * arl_conv2d_bwd_data + arl_conv2d_bwd_weight_parts (which it falls back to when either side is not
+ * on the scalar-addressed fast path); wt_or_null, mask_bits_or_null, the job and dbias as there.
+ * plan_or_null: non-NULL leaves the weight gradient of a layer that does not pair to the group -- the data gradient is
+ *   launched now (and carries the job), the weight gradient is planned into *plan; a layer that pairs runs its shared
+ *   launch now and leaves *plan empty (the group skips it). */
+int arl_conv2d_bwd_pair(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
+                        const uint32_t* mask_bits_or_null, float* dx, const float* x, float* dw,
+                        const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes, arl_fold_item* item,
+                        float* dbias_or_null, arl_fold_item* bias_item_or_null,
+                        const struct arl_corun_job* job_or_null, int32_t* job_taken_or_null,
+                        arl_wgrad_plan* plan_or_null, void* stream);
+
+/* Several layers' weight gradients as ONE launch.  The weight gradients of a backward pass do not depend on one another
+ * (each reads its own layer's dy and input), so the caller walks the data gradients first and has every weight gradient
+ * planned (plan_or_null above, a caller-owned arl_wgrad_plan per layer).  arl_conv2d_bwd_weight_group then
+ * runs up to ARL_WGRAD_GROUP_MAX plans: those on a bf16-split route whose kernel is one of the 64-filter f32 tile or the
+ * two u8 tiles share one grid -- every workgroup finds its layer from its block index and does what its layer's own
+ * launch would have had it do, writing where it would have written (bit-identical partials; no synchronisation between
+ * workgroups) -- one ramp and one tail instead of three, and the L1-bound u8 workgroups resident beside matrix-bound
+ * ones.  Every other plan (fp32 route, generic kernels, <= 16 filters, other tiles, a trace buffer set) is launched on
+ * its own first, as the planning call would have with plan_or_null = NULL; so is a single eligible plan.  The plans'
+ * buffers must stay untouched between the planning call and the group's launch.
+ * Replaces the same T.grad nodes as arl_conv2d_bwd_weight (optimizers/single/ppo_optimizer.py:38-40).               */
+#define ARL_WGRAD_GROUP_MAX 4
+int arl_conv2d_bwd_weight_group(const arl_wgrad_plan* plans, int32_t n, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * One agent step of action serving in ONE launch
@@ -809,7 +884,7 @@ int arl_conv2d_fwd_plan(const arl_conv_geom* geom, int32_t* splits, int32_t* k_p
 
 /* The policy's output layers as arl_env_step_served evaluates them for every env (row e of each array = env e). */
 typedef struct arl_serve_head {
-    arl_fold_item hidden;       /* the last hidden layer as arl_conv2d_fwd_parts left it: total = n_env * hid;
+    arl_fold_item hidden;       /* the last hidden layer as arl_conv2d_fwd's item has it:   total = n_env * hid;
                                  * splits > 0: part f32[splits][n_env][hid] partial sums (folded in arl_fold_many's order);
                                  * splits == 0: part f32[n_env][hid] finished activations.  `out` is not used.          */
     const float* hidden_bias;   /* f32[hid] or NULL: added after the fold (splits > 0 only)                             */
@@ -861,106 +936,6 @@ int arl_env_step_served(const arl_game* game, const arl_env_state* st, const arl
                         const arl_serve_head* head, const arl_serve_conv1* conv1_or_null,
                         const double* uniforms, int32_t step, double max_path_length, double discount,
                         int32_t max_start_noops, void* stream);
-
-/* A layer's data gradient and weight gradient (deferred fold) as ONE launch: the two are independent
- * and both read dy, so their workgroups share a grid -- one ramp-up and one tail instead of two, and
- * the second problem's workgroups fill the CUs the first one's last wave leaves idle.  Same results as
- * arl_conv2d_bwd_data + arl_conv2d_bwd_weight_parts (which it falls back to when either side is not
- * on the scalar-addressed fast path).  wt_or_null: arl_conv2d_dgrad_weights' copy of w for the data gradient. */
-int arl_conv2d_bwd_pair(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null, float* dx,
-                        const float* x, float* dw, const arl_conv_geom* geom, void* workspace,
-                        int64_t workspace_bytes, arl_fold_item* item, float* dbias_or_null,
-                        arl_fold_item* bias_item_or_null, const struct arl_corun_job* job_or_null,
-                        int32_t* job_taken_or_null, void* stream);
-
-/* Convolution 1 read straight from the sampler's observations (no f32 copy of the input):
- * obs u8[obs_rows][in_c][in_h][in_w] (the layout of samples_buf.observations,
- * accel_rl/sampler/act_server/buffers.py:7-38), row b of the batch = obs[idx ? idx[b] : b]
- * (the minibatch indices of optimizers/util.py:8-18), x = float(byte) * scale
- * (atari_cnn_policy.py:88-91: the network input is obs * (1 / 255)).  Weights and their gradient are
- * f32[out_c][in_c][kh][kw] (correlation kernels).  geom->batch = rows of the batch; in_c any count >= 1.
- * Requires pad 0, stride % 4 == 0, in_w % 4 == 0, (in_h * in_w) % 4 == 0, kw in {4, 8, 16},
- * kh % (16 / kw) == 0, out_c % 4 == 0 and <= 32 (else ARL_E_RANGE: use arl_gather_scale_obs_nhwc +
- * arl_conv2d_fwd).  The sums run over the exact integer pixels, plane by plane, and `scale` multiplies the
- * finished sum once (a convolution is linear in its input: y = scale * conv(byte, w) + bias) -- equal to the
- * gather + scale route up to f32 round-off, not bit for bit.  */
-int arl_conv2d_u8_fwd(const uint8_t* obs, int64_t obs_rows, const int32_t* idx_or_null, float scale,
-                      const float* w, const float* bias_or_null, float* y, const arl_conv_geom* geom,
-                      int32_t relu, void* stream);
-/* Its weight gradient (deferred fold, optional bias-gradient partials: as arl_conv2d_bwd_weight_parts). */
-int arl_conv2d_u8_bwd_weight_parts(const float* dy, const uint8_t* obs, int64_t obs_rows,
-                                   const int32_t* idx_or_null, float scale, float* dw,
-                                   const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes,
-                                   arl_fold_item* item, float* dbias_or_null,
-                                   arl_fold_item* bias_item_or_null, void* stream);
-
-/* Several layers' weight gradients as ONE launch.  The weight gradients of a backward pass do not depend on one another
- * (each reads its own layer's dy and input), so the caller walks the data gradients first and has every weight gradient
- * described instead of launched: a caller-owned arl_wgrad_plan per layer, filled by the *_plan calls below, which
- * validate, plan the row split and fill the fold item(s) exactly as their launching counterparts do (same workspace,
- * same split count, same partial layout, same bias partials) and launch nothing.  arl_conv2d_bwd_weight_group then
- * runs up to ARL_WGRAD_GROUP_MAX plans: those on a bf16-split route whose kernel is one of the 64-filter f32 tile or the
- * two u8 tiles share one grid -- every workgroup finds its layer from its block index and does what its layer's own
- * launch would have had it do, writing where it would have written (bit-identical partials; no synchronisation between
- * workgroups) -- one ramp and one tail instead of three, and the L1-bound u8 workgroups resident beside matrix-bound
- * ones.  Every other plan (fp32 route, generic kernels, <= 16 filters, other tiles, a trace buffer set) is launched on
- * its own first, as arl_conv2d_bwd_weight_parts / arl_conv2d_u8_bwd_weight_parts would have; so is a single eligible
- * plan.  The plans' buffers must stay untouched between the *_plan call and the group's launch.
- * Replaces the same T.grad nodes as arl_conv2d_bwd_weight (optimizers/single/ppo_optimizer.py:38-40).               */
-#define ARL_WGRAD_GROUP_MAX 4
-typedef struct arl_wgrad_plan { int64_t opaque[32]; } arl_wgrad_plan;
-/* arl_conv2d_bwd_weight_parts without its launch. */
-int arl_conv2d_bwd_weight_plan(const float* dy, const float* x, float* dw, const arl_conv_geom* geom,
-                               void* workspace, int64_t workspace_bytes, arl_fold_item* item,
-                               float* dbias_or_null, arl_fold_item* bias_item_or_null, arl_wgrad_plan* plan);
-/* arl_conv2d_u8_bwd_weight_parts without its launch. */
-int arl_conv2d_u8_bwd_weight_plan(const float* dy, const uint8_t* obs, int64_t obs_rows,
-                                  const int32_t* idx_or_null, float scale, float* dw,
-                                  const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes,
-                                  arl_fold_item* item, float* dbias_or_null,
-                                  arl_fold_item* bias_item_or_null, arl_wgrad_plan* plan);
-/* arl_conv2d_bwd_pair with the weight gradient of a layer that does not pair left to the group: the data gradient is
- * launched now (and carries the job, as there); a layer that pairs runs its shared launch now and leaves *plan empty
- * (the group skips it). */
-int arl_conv2d_bwd_pair_plan(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
-                             float* dx, const float* x, float* dw, const arl_conv_geom* geom, void* workspace,
-                             int64_t workspace_bytes, arl_fold_item* item, float* dbias_or_null,
-                             arl_fold_item* bias_item_or_null, const struct arl_corun_job* job_or_null,
-                             int32_t* job_taken_or_null, arl_wgrad_plan* plan, void* stream);
-int arl_conv2d_bwd_weight_group(const arl_wgrad_plan* plans, int32_t n, void* stream);
-
-/* Rectifier masks as bits.  A data gradient uses one thing of every value of its f32 mask: whether it is > 0.  For an
- * activation tensor y f32[rows][C] with C % 32 == 0 (rows in the tensor's own NHWC order) the mask as bits is
- * u32[rows][C / 32]: bit c % 32 of word c / 32 = (y[row][c] > 0.f) as the device evaluates it on the stored value (NaN and
- * -0 give 0, as in the f32 comparison) -- 1/32 of the bytes.  The *_bits entry points are their namesakes with one more
- * pointer; NULL there = the namesake itself, bit for bit and launch for launch.
- *   y_bits (forward calls): the launch also writes y's mask as bits; y itself is written as ever.  Served on the bf16-split
- *     routes by the kernels of layers with 32 .. 64 output columns whose k-tiles hold one filter tap (in_c % 32 == 0: the
- *     learner's conv 2 and conv 3) and by the first convolution from u8 rows with 32 filters (the image-stationary kernel,
- *     or the tap-gathering split kernel where that one does not run); ARL_E_RANGE -- nothing launched, never ignored -- for
- *     out_c % 32 != 0, a reduction that the call splits (the fold writes y), the fp32 route, wider or multi-tap layers and
- *     the generic kernels.
- *   mask_bits (data gradients): the mask of mask_or_null as bits, from a forward call's y_bits on the same tensor.  It
- *     comes on top of mask_or_null (ARL_E_ARG without it): the bf16-split launches of 17 .. 64 input channels on the
- *     k-contiguous weight copy (wt) and the shared launch of arl_conv2d_bwd_pair test the bit and never read the floats;
- *     every other launch (fp32 route, no wt, 16-wide tiles, generic kernels, the split reduction's fold) compares the
- *     floats as before.  dx is the same bits either way.  ARL_E_RANGE for in_c % 32 != 0.
- * Both: ARL_E_ALIGN unless 4-byte aligned.  arl_conv2d_bwd_pair_bits with plan_or_null is arl_conv2d_bwd_pair_plan.
- * The reference has no counterpart: Theano keeps the rectifier's input for T.grad (pg_cnn.py:47-68).                    */
-int arl_conv2d_fwd_bits(const float* x, const float* w, const float* bias_or_null, float* y, uint32_t* y_bits_or_null,
-                        const arl_conv_geom* geom, int32_t relu, void* workspace, void* stream);
-int arl_conv2d_u8_fwd_bits(const uint8_t* obs, int64_t obs_rows, const int32_t* idx_or_null, float scale,
-                           const float* w, const float* bias_or_null, float* y, uint32_t* y_bits_or_null,
-                           const arl_conv_geom* geom, int32_t relu, void* stream);
-int arl_conv2d_bwd_data_bits(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
-                             const uint32_t* mask_bits_or_null, float* dx, const arl_conv_geom* geom,
-                             const struct arl_corun_job* job_or_null, int32_t* job_taken_or_null, void* stream);
-int arl_conv2d_bwd_pair_bits(const float* dy, const float* w, const float* wt_or_null, const float* mask_or_null,
-                             const uint32_t* mask_bits_or_null, float* dx, const float* x, float* dw,
-                             const arl_conv_geom* geom, void* workspace, int64_t workspace_bytes, arl_fold_item* item,
-                             float* dbias_or_null, arl_fold_item* bias_item_or_null,
-                             const struct arl_corun_job* job_or_null, int32_t* job_taken_or_null,
-                             arl_wgrad_plan* plan_or_null, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * Replay memory of the DQN family
@@ -1116,7 +1091,7 @@ int arl_catdqn_loss(const float* pred_logits, const float* tgt_next_logits, cons
                     int32_t atom_stride, int32_t dueling, float v_min, float v_max, float gamma_n,
                     float* dlogits, float* loss_rows, float* kl, void* stream);
 
-/* The same loss reading its three logit blocks as the output layer's SPLIT PARTIAL SUMS (arl_conv2d_fwd_parts on the
+/* The same loss reading its three logit blocks as the output layer's SPLIT PARTIAL SUMS (arl_conv2d_fwd's item on the
  * "action_atoms" dense layer, catdqn_cnn.py:69-76): at the reference's minibatch of 32 (accel_rl/algos/dqn/dqn.py:18) an
  * update is a chain of launch latencies, and the two launches that only fold the output layers' partials are taken
  * over by the loss kernel -- logit = (the partials summed in arl_fold_many's order) + bias, operation for operation, so
@@ -2007,7 +1982,7 @@ typedef struct arl_noisy_layer {
 int arl_noisy_noise(const int64_t* state, const arl_noisy_layer* layers, int32_t n_layers, int64_t rows,
                     int32_t rows_per_draw, void* stream);
 
-/* The layer's output from its two products as arl_conv2d_fwd_parts left them (relu 0; W product with bias b, W_sigma
+/* The layer's output from its two products as arl_conv2d_fwd's items have them (relu 0; W product with bias b, W_sigma
  * product with bias b_sigma: splits == 0 means finished, bias applied; splits > 0: folded here in arl_fold_many's order,
  * then the bias): y = relu?(P_w + f(e_out) * P_sigma), f32[rows][units] (noisy_layer.py:120-147, a hidden layer's
  * rectifier: noisy_net_dqn_cnn.py:64-76).  fein_next / xs_next (both or neither): xs_next = y * fein_next, the next
@@ -2089,7 +2064,7 @@ int arl_noisy_duel_bwd_prep(const float* g, const float* feout, int64_t rows, in
 int arl_noisy_duel_bwd_dx(const float* dx_w, const float* dx_sigma_lo, const float* fein_lo, const float* dx_sigma_hi,
                           const float* fein_hi, int64_t rows, int32_t fan_in, float* dx, void* stream);
 
-/* A noisy output layer's logits as its two arl_conv2d_fwd_parts products left them, from the source's first row on
+/* A noisy output layer's logits as the items of its two arl_conv2d_fwd products have them, from the source's first row on
  * (row = (n_actions + dueling) atom_stride floats): logit = [x W + b] + f(e_out) ([x f(e_in) W_sigma] + b_sigma). */
 typedef struct arl_noisy_logit_src {
     const float* w_part;        /* x W: f32[w_splits][..] partial sums, or (w_splits == 0) finished values (bias in) */

@@ -52,7 +52,7 @@ def test_the_boundary_header_keeps_no_state():
 
 
 def test_abi_version_and_arg_errors(lib):
-    assert lib.arl_abi_version() == 4
+    assert lib.arl_abi_version() == 5
     # null pointers / bad sizes are rejected before any HIP call is made
     assert lib.arl_gae_scan(None, None, None, None, 0.99, 0.95, 4, 5, 0, None, None, None) == -1
     assert b"null" in lib.arl_last_error()
@@ -63,7 +63,17 @@ def test_abi_version_and_arg_errors(lib):
     assert lib.arl_standardize_workspace_bytes() >= 3 * 8
     assert lib.arl_env_step_served(None, None, None, None, None, None, 0, 1.0, 0.99, 0, None) == -1
     assert lib.arl_serve_conv1_supported(None, None) == 0
-    assert lib.arl_conv2d_fwd_parts(None, None, None, None, None, 1, None, None, None) == -1
+    assert lib.arl_conv2d_fwd(None, None, None, None, None, None, 1, None, None, None) == -1
+    # the other conv entry points that take their optional operands as NULL-able arguments
+    for call in (lambda: lib.arl_conv2d_u8_fwd(None, 0, None, 1.0, None, None, None, None, None, 1, None),
+                 lambda: lib.arl_conv2d_bwd_data(None, None, None, None, None, None, None, None, None, None),
+                 lambda: lib.arl_conv2d_bwd_weight_parts(None, None, None, None, None, 0, None, None, None, None, None),
+                 lambda: lib.arl_conv2d_u8_bwd_weight_parts(None, None, 0, None, 1.0, None, None, None, 0, None, None, None,
+                                                            None, None),
+                 lambda: lib.arl_conv2d_bwd_pair(None, None, None, None, None, None, None, None, None, None, 0, None, None,
+                                                 None, None, None, None, None)):
+        assert call() == -1
+        assert b"null" in lib.arl_last_error()
 
 
 def test_struct_layouts_match_header(lib):

@@ -120,7 +120,7 @@ def test_binding_and_arg_errors():
     from accel_rl_amd import _build, _lib
     _build.build_extension()
     lib = _lib.load()
-    assert "acer.hip" in _build.SOURCES and lib.arl_abi_version() == 4
+    assert "acer.hip" in _build.SOURCES and lib.arl_abi_version() == 5
     for name in ("arl_acer_retrace_scan", "arl_acer_loss", "arl_acer_avg_step", "arl_gather_segments"):
         assert name in _lib.EXPORTED_SYMBOLS and callable(getattr(_lib, name[4:]))
         assert getattr(lib, name).restype is ctypes.c_int32

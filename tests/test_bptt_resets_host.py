@@ -33,7 +33,7 @@ def test_header_binding_and_library_agree_on_the_new_names(lib):
         assert getattr(raw, name) is not None
     for wrapper in ("seq_handover", "lstm_cell_bwd_reset", "gru_cell_bwd_reset", "rnn_cell_bwd_reset"):
         assert callable(getattr(_lib, wrapper))
-    assert lib.arl_abi_version() == 4 == _lib.ARL_ABI_VERSION
+    assert lib.arl_abi_version() == 5 == _lib.ARL_ABI_VERSION
 
 
 def test_new_entry_points_report_argument_errors_without_a_device(lib):

@@ -527,7 +527,8 @@ def test_data_gradient_refusals_launch_nothing():
     assert len(_log()) == 1                                              # (so that an empty log below is the refusal's)
     for bad, code, word in ((_lib.conv_geom(2, 7, 8, 8, 32, 3, 3, 2, 0, 0), -2, b"stride"),      # kernel 3, stride 2
                             (_lib.conv_geom(2, 7, 8, 6, 32, 2, 2, 2, 0, 0), -2, b"multiples of 4")):
-        rc = lib.arl_conv2d_bwd_data(t.data_ptr(), t.data_ptr(), None, None, t.data_ptr(), _lib.C.byref(bad), None, None, None)
+        rc = lib.arl_conv2d_bwd_data(t.data_ptr(), t.data_ptr(), None, None, None, t.data_ptr(), _lib.C.byref(bad), None, None,
+                                     None)
         assert rc == code and word in lib.arl_last_error() and _log() == []
         _lib.conv2d_bwd_data(t[:2 * 2 * 2 * 32], t[:32 * 2 * 2 * 8], None, t[2048:2048 + 2 * 4 * 4 * 8], ok)
         assert len(_log()) == 1
@@ -775,13 +776,14 @@ def test_u8_conv1_refuses_36_filters_and_launches_nothing():
     assert len(_log()) == 1
     bad = _lib.conv_geom(5, 8, 16, 2, 36, 8, 8, 4, 0, 0)
     w36 = torch.zeros(36, 2, 8, 8, device=DEV)
-    assert lib.arl_conv2d_u8_fwd(obs.data_ptr(), 5, None, SCALE, w36.data_ptr(), None, y.data_ptr(), _lib.C.byref(bad), 1, None) == -2
+    assert lib.arl_conv2d_u8_fwd(obs.data_ptr(), 5, None, SCALE, w36.data_ptr(), None, y.data_ptr(), None, _lib.C.byref(bad), 1,
+                                 None) == -2
     assert b"<= 32 filters" in lib.arl_last_error() and _log() == []
     assert torch.isnan(y).all()
     item, bitem = _lib.ArlFoldItem(), _lib.ArlFoldItem()
     ws = _lib.conv_workspace(DEV)
     rc = lib.arl_conv2d_u8_bwd_weight_parts(y.data_ptr(), obs.data_ptr(), 5, None, SCALE, w36.data_ptr(), _lib.C.byref(bad),
-                                            ws.data_ptr(), ws.numel() * 4, _lib.C.byref(item), None, None, None)
+                                            ws.data_ptr(), ws.numel() * 4, _lib.C.byref(item), None, None, None, None)
     assert rc == -2 and _log() == []
 
 

@@ -128,7 +128,7 @@ def test_the_library_exports_the_entry_points_and_refuses_bad_arguments(lib):
         assert name in _lib.EXPORTED_SYMBOLS and getattr(lib, name) is not None
     for fn in ("fqf_fractions", "fqf_act", "fqf_loss"):
         assert callable(getattr(_lib, fn))
-    assert lib.arl_abi_version() == 4
+    assert lib.arl_abi_version() == 5
     p = 4096                                                    # any aligned non-null address (never dereferenced)
 
     def frac(lg=p, b=1, n=8, s=8, tau=p, hat=p):

@@ -114,7 +114,7 @@ def test_the_library_exports_the_entry_points_and_refuses_bad_arguments(lib):
         assert name in _lib.EXPORTED_SYMBOLS and getattr(lib, name) is not None
     for fn in ("iqn_embed", "iqn_merge_fwd", "iqn_merge_bwd", "iqn_act", "iqn_loss"):
         assert callable(getattr(_lib, fn))
-    assert lib.arl_abi_version() == 4
+    assert lib.arl_abi_version() == 5
     # refused before any HIP call is made (no device here): nulls, then sizes (the pointers are never dereferenced)
     assert lib.arl_iqn_embed(None, None, 0, 0, 1, 1, None, None, None) == -1 and b"null" in lib.arl_last_error()
     assert lib.arl_iqn_merge_fwd(None, None, 1, 1, 4, None, None) == -1

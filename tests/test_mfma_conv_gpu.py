@@ -220,10 +220,11 @@ def test_argument_errors():
     y = torch.empty(2, 12, 9, 64, device=DEV)
     bad = _lib.conv_geom(2, 12, 9, 6, 64, 3, 3, 1, 1, 1)        # channels not a multiple of 4
     with pytest.raises(RuntimeError):
-        _lib.load().arl_conv2d_fwd(x.data_ptr(), wt.data_ptr(), None, y.data_ptr(), _lib.C.byref(bad), 0,
-                                   ws.data_ptr(), None) and (_ for _ in ()).throw(RuntimeError("rc"))
+        _lib.load().arl_conv2d_fwd(x.data_ptr(), wt.data_ptr(), None, y.data_ptr(), None, _lib.C.byref(bad), 0,
+                                   ws.data_ptr(), None, None) and (_ for _ in ()).throw(RuntimeError("rc"))
     odd = _lib.conv_geom(2, 13, 9, 64, 64, 3, 3, 2, 1, 1)       # kernel 3, stride 2: unsupported data gradient
-    rc = _lib.load().arl_conv2d_bwd_data(y.data_ptr(), wt.data_ptr(), None, None, x.data_ptr(), _lib.C.byref(odd), None, None, None)
+    rc = _lib.load().arl_conv2d_bwd_data(y.data_ptr(), wt.data_ptr(), None, None, None, x.data_ptr(), _lib.C.byref(odd), None, None,
+                                         None)
     assert rc == -2 and b"stride" in _lib.load().arl_last_error()
     with pytest.raises(RuntimeError):
         _lib.conv2d_fwd(x.cpu(), wt, None, y, geom, False, ws) if False else _lib.ptr(x.cpu())

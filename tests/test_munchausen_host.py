@@ -109,7 +109,7 @@ def test_the_library_exports_the_entry_points_and_refuses_bad_arguments(lib):
     for name in ("arl_mdqn_loss", "arl_miqn_loss"):
         assert name in _lib.EXPORTED_SYMBOLS and getattr(lib, name) is not None
     assert callable(_lib.mdqn_loss) and callable(_lib.miqn_loss)
-    assert lib.arl_abi_version() == 4
+    assert lib.arl_abi_version() == 5
     # refused before any HIP call is made (no device here): nulls, then sizes and constants (nothing is dereferenced)
     assert lib.arl_mdqn_loss(None, None, None, None, None, None, None, 1, 4, 4, 0, 0.99, 1.0, 0.03, 0.9, -1.0, None, None,
                              None, None) == -1 and b"null" in lib.arl_last_error()

@@ -29,7 +29,7 @@ def _buf(nbytes, offset=0):
 
 def test_argument_errors_come_back_before_any_launch(lib):
     from accel_rl_amd import _lib
-    assert _lib.ARL_ABI_VERSION == 4 and lib.arl_abi_version() == 4
+    assert _lib.ARL_ABI_VERSION == 5 and lib.arl_abi_version() == 5
     assert (_lib.POPART_MAX_ROWS, _lib.POPART_MAX_HID) == (1 << 22, 65536)
     assert "arl_popart_denorm" in _lib.EXPORTED_SYMBOLS and "arl_popart_step" in _lib.EXPORTED_SYMBOLS
     keep, p = _buf(4096)

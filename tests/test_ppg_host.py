@@ -155,7 +155,7 @@ def test_entry_is_declared_and_bound_with_matching_arguments():
     from accel_rl_amd import _build, _lib
     _build.build_extension()
     lib = _lib.load()
-    assert lib.arl_abi_version() == 4 and _lib.ARL_ABI_VERSION == 4
+    assert lib.arl_abi_version() == 5 and _lib.ARL_ABI_VERSION == 5
     text = open(os.path.join(ROOT, "include", "accel_rl_hip.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     (decl,) = re.findall(r"\bint\s+arl_ppg_head_loss_parts\s*\(([^)]*)\)\s*;", text)

@@ -79,7 +79,7 @@ def test_the_library_exports_both_entry_points(lib):
     for name in ("arl_qrdqn_act", "arl_qrdqn_loss"):
         assert name in _lib.EXPORTED_SYMBOLS and getattr(lib, name) is not None
     assert callable(_lib.qrdqn_act) and callable(_lib.qrdqn_loss)
-    assert lib.arl_abi_version() == 4
+    assert lib.arl_abi_version() == 5
     # null pointers are refused before any HIP call is made
     assert lib.arl_qrdqn_act(None, None, 1, 4, 8, 8, 0, None, None, None) == -1
     assert b"null" in lib.arl_last_error()

@@ -1,4 +1,4 @@
-"""Rectifier masks as bits (arl_conv2d_*_bits, AtariCnnPolicy._relu_bits_layers, ARL_RELU_BITS): the forward kernels of the
+"""Rectifier masks as bits (y_bits_or_null / mask_bits_or_null of the arl_conv2d_* calls, AtariCnnPolicy._relu_bits_layers, ARL_RELU_BITS): the forward kernels of the
 learner's conv layers also write `y > 0` as one bit per value, u32[rows][C / 32], and the data gradients read those
 words instead of the f32 activations.  Nothing is computed differently -- only where a comparison's outcome is read from
 changes -- so everything here is exact: the words against numpy's packing of the same launch's f32 output, dx with bits
@@ -396,8 +396,8 @@ def test_bits_that_cannot_be_served_are_refused():
     # forward: 48 filters (C % 32 != 0), a misaligned pointer
     g48 = _lib.conv_geom(2, 12, 9, 64, 48, 3, 3, 1, 1, 1)
     x, w48, y48 = randn((2, 12, 9, 64), 1), randn((48, 3, 3, 64), 2), torch.full((2 * 108, 48), 5.0, device=DEV)
-    fwd = lambda g, w, y, p: lib.arl_conv2d_fwd_bits(x.data_ptr(), w.data_ptr(), None, y.data_ptr(), p, C.byref(g), 1,  # noqa: E731
-                                                     ws.data_ptr(), sp)
+    fwd = lambda g, w, y, p: lib.arl_conv2d_fwd(x.data_ptr(), w.data_ptr(), None, y.data_ptr(), p, C.byref(g), 1,  # noqa: E731
+                                                ws.data_ptr(), None, sp)
     assert fwd(g48, w48, y48, bits.data_ptr()) == E_RANGE
     g64 = geom_of(CONV3, 2)
     w64, y64 = randn((64, 3, 3, 64), 3), torch.full((2 * 108, 64), 5.0, device=DEV)
@@ -409,22 +409,22 @@ def test_bits_that_cannot_be_served_are_refused():
     gd = _lib.dense_geom(4, 6912, 512)
     xd, wd, yd = randn((4, 6912), 4), randn((512, 6912), 5), torch.full((4, 512), 5.0, device=DEV)
     assert _lib.conv2d_fwd_plan(gd)[0] > 1
-    assert lib.arl_conv2d_fwd_bits(xd.data_ptr(), wd.data_ptr(), None, yd.data_ptr(), bits.data_ptr(), C.byref(gd), 1,
-                                   ws.data_ptr(), sp) == E_RANGE
+    assert lib.arl_conv2d_fwd(xd.data_ptr(), wd.data_ptr(), None, yd.data_ptr(), bits.data_ptr(), C.byref(gd), 1,
+                              ws.data_ptr(), None, sp) == E_RANGE
     # u8 forward: 16 filters
     g16 = _lib.conv_geom(1, 104, 80, 4, 16, 8, 8, 4, 0, 0)
     obs = torch.zeros((1, 4, 104, 80), dtype=torch.uint8, device=DEV)
     w16, y16 = randn((16, 4, 8, 8), 6), torch.full((475, 16), 5.0, device=DEV)
-    u8 = lambda g, w, y, p: lib.arl_conv2d_u8_fwd_bits(obs.data_ptr(), 1, None, 1.0, w.data_ptr(), None, y.data_ptr(), p,  # noqa: E731
-                                                       C.byref(g), 1, sp)
+    u8 = lambda g, w, y, p: lib.arl_conv2d_u8_fwd(obs.data_ptr(), 1, None, 1.0, w.data_ptr(), None, y.data_ptr(), p,  # noqa: E731
+                                                  C.byref(g), 1, sp)
     assert u8(g16, w16, y16, bits.data_ptr()) == E_RANGE
     w32, y32 = randn((32, 4, 8, 8), 7), torch.full((475, 32), 5.0, device=DEV)
     assert u8(geom_of(CONV1, 1), w32, y32, bits.data_ptr() + 2) == E_ALIGN
     # data gradient: 48 input channels, a misaligned pointer, bits without the mask
     g48i = _lib.conv_geom(2, 12, 9, 48, 64, 3, 3, 1, 1, 1)
     dy, wi, m48, dx48 = randn((2, 12, 9, 64), 8), randn((64, 3, 3, 48), 9), randn((216, 48), 10), torch.full((216, 48), 5.0, device=DEV)
-    bwd = lambda g, w, m, dx, p: lib.arl_conv2d_bwd_data_bits(dy.data_ptr(), w.data_ptr(), None, m, p, dx.data_ptr(),  # noqa: E731
-                                                              C.byref(g), None, None, sp)
+    bwd = lambda g, w, m, dx, p: lib.arl_conv2d_bwd_data(dy.data_ptr(), w.data_ptr(), None, m, p, dx.data_ptr(),  # noqa: E731
+                                                         C.byref(g), None, None, sp)
     assert bwd(g48i, wi, m48.data_ptr(), dx48, bits.data_ptr()) == E_RANGE
     m64, dx64 = randn((216, 64), 11), torch.full((216, 64), 5.0, device=DEV)
     assert bwd(g64, w64, m64.data_ptr(), dx64, bits.data_ptr() + 2) == E_ALIGN
@@ -432,9 +432,9 @@ def test_bits_that_cannot_be_served_are_refused():
     # the pair
     item, plan = _lib.ArlFoldItem(), _lib.ArlWgradPlan()
     dw = torch.zeros_like(w64)
-    pair = lambda p: lib.arl_conv2d_bwd_pair_bits(dy.data_ptr(), w64.data_ptr(), None, m64.data_ptr(), p, dx64.data_ptr(),  # noqa: E731
-                                                  m64.data_ptr(), dw.data_ptr(), C.byref(g64), ws.data_ptr(),
-                                                  ws.numel() * 4, C.byref(item), None, None, None, None, C.byref(plan), sp)
+    pair = lambda p: lib.arl_conv2d_bwd_pair(dy.data_ptr(), w64.data_ptr(), None, m64.data_ptr(), p, dx64.data_ptr(),  # noqa: E731
+                                             m64.data_ptr(), dw.data_ptr(), C.byref(g64), ws.data_ptr(),
+                                             ws.numel() * 4, C.byref(item), None, None, None, None, C.byref(plan), sp)
     assert pair(bits.data_ptr() + 2) == E_ALIGN
     assert b"rectifier bits" in lib.arl_last_error()
     torch.cuda.synchronize()
@@ -444,3 +444,41 @@ def test_bits_that_cannot_be_served_are_refused():
     # and the Python wrappers pass the library's refusal on
     with pytest.raises(RuntimeError, match="rectifier bits"):
         _lib.conv2d_fwd(x, w48, None, y48, g48, True, ws, y_bits=bits)
+
+
+@gpu
+def test_forward_with_an_item_and_bits():
+    """arl_conv2d_fwd given both item_or_null and y_bits_or_null (bf16-split route).  A layer that does not split (2 x 9 x
+    9 x 32, 64 filters of 4 x 4, stride 2: 18 rows) reports splits == 0 and writes the y and the words of the call without
+    an item; a split reduction (64 x 6912 -> 512) is refused with ARL_E_RANGE and nothing is launched."""
+    from accel_rl_amd import _lib
+    lib = _lib.load()
+    sp, ws = _lib.stream_ptr(), workspace()
+    rows, ch = 18, 64
+    g = _lib.conv_geom(2, 9, 9, 32, ch, 4, 4, 2, 0, 0, route=_lib.ROUTE_SPLIT9)
+    x, w, bias = randn((2, 9, 9, 32), 41), randn((ch, 4, 4, 32), 42, 0.05), randn((ch,), 43, 0.1)
+
+    def run(item):
+        y = torch.full((rows, ch), -7.0, device=DEV)
+        buf, bits = guarded(rows * ch // 32)
+        assert lib.arl_conv2d_fwd(x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), bits.data_ptr(), C.byref(g), 1,
+                                  ws.data_ptr(), item, sp) == 0
+        return y, buf, bits
+    item = _lib.ArlFoldItem(splits=-5)
+    y1, buf1, bits1 = run(C.byref(item))
+    assert item.splits == 0
+    assert len(_lib.conv_launch_log()) == 1
+    y0, _, bits0 = run(None)
+    torch.cuda.synchronize()
+    assert torch.equal(y0, y1) and torch.equal(bits0, bits1)
+    check_words(buf1, bits1, y1, ch)
+    # a reduction that splits: the fold would have to write the bits
+    gd = _lib.dense_geom(64, 6912, 512, route=_lib.ROUTE_SPLIT9)
+    assert _lib.conv2d_fwd_plan(gd)[0] > 1
+    xd, wd, yd = randn((64, 6912), 44), randn((512, 6912), 45, 0.02), torch.full((64, 512), 5.0, device=DEV)
+    buf, bits = guarded(64 * 512 // 32)
+    assert lib.arl_conv2d_fwd(xd.data_ptr(), wd.data_ptr(), None, yd.data_ptr(), bits.data_ptr(), C.byref(gd), 1,
+                              ws.data_ptr(), C.byref(item), sp) == -2
+    assert b"rectifier bits" in lib.arl_last_error() and _lib.conv_launch_log() == []
+    torch.cuda.synchronize()
+    assert bool((yd == 5.0).all()) and bool((buf == FILL).all())

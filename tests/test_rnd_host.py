@@ -234,7 +234,7 @@ def _buf(nbytes, offset=0):
 
 def test_argument_errors_come_back_before_any_launch(lib):
     from accel_rl_amd import _lib
-    assert _lib.ARL_ABI_VERSION == 4 and lib.arl_abi_version() == 4
+    assert _lib.ARL_ABI_VERSION == 5 and lib.arl_abi_version() == 5
     keep, p = _buf(64)
     _, odd = _buf(64, 4)
     ws_bytes = lib.arl_rnd_obs_stats_workspace_bytes

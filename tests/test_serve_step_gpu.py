@@ -207,7 +207,7 @@ def test_served_step_matches_the_oracle_sampler_port(game, n_parallel, envs_per)
 
 
 def test_forward_parts_describe_the_fold():
-    """arl_conv2d_fwd_parts: the partial sums it leaves, folded by arl_fold_many's rule with bias and rectifier, are
+    """arl_conv2d_fwd with an item: the partial sums it leaves, folded by arl_fold_many's rule with bias and rectifier, are
     arl_conv2d_fwd's output bit for bit (dense layer at the rollout's shape: 256 x 6912 -> 512, 24 splits)."""
     from accel_rl_amd import _lib
     torch.manual_seed(3)

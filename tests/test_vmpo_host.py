@@ -182,7 +182,7 @@ def test_entries_are_declared_and_bound_with_matching_arguments():
     from accel_rl_amd import _build, _lib
     _build.build_extension()
     lib = _lib.load()
-    assert lib.arl_abi_version() == 4 and _lib.ARL_ABI_VERSION == 4
+    assert lib.arl_abi_version() == 5 and _lib.ARL_ABI_VERSION == 5
     text = open(os.path.join(ROOT, "include", "accel_rl_hip.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     kinds = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "float": ctypes.c_float, "double": ctypes.c_double}

@@ -1,6 +1,6 @@
-"""The conv stack's weight gradients as one launch (arl_conv2d_bwd_weight_group over arl_conv2d_bwd_weight_plan /
-arl_conv2d_u8_bwd_weight_plan, csrc/mfma_wgrad.h wgrad_group_kernel) against the separate launches it replaces
-(arl_conv2d_bwd_weight_parts / arl_conv2d_u8_bwd_weight_parts): the same workgroups doing the same products in the same
+"""The conv stack's weight gradients as one launch (arl_conv2d_bwd_weight_group over the plans of
+arl_conv2d_bwd_weight_parts / arl_conv2d_u8_bwd_weight_parts, csrc/mfma_wgrad.h wgrad_group_kernel) against the separate
+launches it replaces (the same two calls with plan_or_null = NULL): the same workgroups doing the same products in the same
 order, so EVERYTHING is bit-identical -- dw and dbias after the folds and the raw partial workspaces.
 
 Shapes: the spec-1 layers (conv 1 u8 4 -> 32 8x8 / 4, conv 2 32 -> 64 4x4 / 2 pad 1, conv 3 64 -> 64 3x3 pad 1) at
