@@ -8,8 +8,8 @@ and refuses every other class.  This sampler is the other half of the boundary: 
 MuJoCo env, BASELINE config 1's "CPU sampler" form -- stepped by pinned worker processes, with everything the
 learner touches in the SAME place and layout as under `GpuVecSampler`:
 
-  * observations travel host -> device once per (step, group) out of a shared, page-locked step buffer
-    (the reference's `step_buf.obs`), and are scattered on the device into the env-major rollout buffer;
+  * observations travel host -> device once per (step, group) out of a shared step buffer (the reference's
+    `step_buf.obs`) through a page-locked twin of it, and are scattered on the device into the env-major rollout buffer;
   * actions are sampled ON the device from the policy's probabilities (`arl_sample_categorical`: the
     reference's `weighted_sample_n`, rllab/misc/special.py:22-27, with the master's `np.random.rand(B)` per
     (step, group) as its uniforms -- the same variates in the same order) and travel back as B bytes;
@@ -236,7 +236,7 @@ class HostEnvSampler(BaseMbSampler):
         self._total_n_envs = 2 * n_parallel * envs_per
         self.device = device
         self.workers = []
-        self._registered = []
+        self._pinned = {}
 
     # ------------------------------------------------------------------ API
     def initialize(self, seed, affinities=None, discount=1, need_extra_obs=False):
@@ -320,7 +320,6 @@ class HostEnvSampler(BaseMbSampler):
         self.step_obs = batch_buffer(self._examples["observations"], n, dev)
         if self.eval_envs_per:
             self.eval_step_obs = batch_buffer(self._examples["observations"], 2 * half_e, dev)
-        self._pin_shared()
         return self.env_spec, self.sample_size, self.horizon, self.mid_batch_reset
 
     def policy_init(self, policy):
@@ -406,7 +405,7 @@ class HostEnvSampler(BaseMbSampler):
                     self._acquire(j, "obs_ready")
                     step = self._steps[j]
                     obs_dev = self.step_obs[lo:lo + half]
-                    obs_dev.copy_(step.obs, non_blocking=True)
+                    self._upload(obs_dev, step.obs)
                     if self._recurrent and bool(step.reset.any()):     # policy.reset_one for the group's flagged envs
                         self._reset_host.zero_()                       # (sampler.py:135-138)
                         self._reset_host[lo:lo + half].copy_(step.reset.to(torch.uint8))
@@ -417,11 +416,13 @@ class HostEnvSampler(BaseMbSampler):
                     if self.mid_batch_reset or s == 0:
                         live = None
                     else:
-                        self._live_dev.copy_(step.live, non_blocking=True)
+                        self._upload(self._live_dev, step.live)
                         live = self._live_dev
-                    step.act.copy_(act_dev.to(self._act_dtype) if self._act_dtype != torch.uint8 else act_dev,
+                    act_host = self._staging(step.act)
+                    act_host.copy_(act_dev.to(self._act_dtype) if self._act_dtype != torch.uint8 else act_dev,
                                    non_blocking=True)
-                    stream.synchronize()                  # the actions are in the step buffer
+                    stream.synchronize()
+                    step.act.copy_(act_host)              # the actions are in the step buffer
                     step.reset.zero_()
                     for g in self._gates[j]:
                         g.act_ready.release()
@@ -440,11 +441,11 @@ class HostEnvSampler(BaseMbSampler):
             for j in range(2):
                 self._acquire(j, "obs_ready")
                 if self.need_extra_obs:
-                    buf.extra_observations[j * half:(j + 1) * half].copy_(self._steps[j].obs, non_blocking=True)
-            buf.rewards.copy_(self._batch.rewards, non_blocking=True)
-            buf.dones.copy_(self._batch.dones, non_blocking=True)
+                    self._upload(buf.extra_observations[j * half:(j + 1) * half], self._steps[j].obs)
+            self._upload(buf.rewards, self._batch.rewards)
+            self._upload(buf.dones, self._batch.dones)
             for k, v in self._batch.env_infos.items():
-                buf.env_infos[k].copy_(v, non_blocking=True)
+                self._upload(buf.env_infos[k], v)
             stream.synchronize()                          # everything the workers own has been read ...
         return self.samples_buf, self._finish_round()
 
@@ -476,10 +477,7 @@ class HostEnvSampler(BaseMbSampler):
         for p in self.workers:
             p.join(max(0.0, deadline - time.time()))
         self.kill_workers()
-        rt = torch.cuda.cudart()
-        for ptr in self._registered:
-            rt.cudaHostUnregister(ptr)
-        self._registered = []
+        self._pinned = {}
 
     def kill_workers(self):
         """Failure paths (a runner leaving through os._exit): end the simulation processes now."""
@@ -496,24 +494,19 @@ class HostEnvSampler(BaseMbSampler):
         return True
 
     # -------------------------------------------------------------- internals
-    def _pin_shared(self):
-        """Page-lock the shared step / batch arrays (hipHostRegister): host <-> device copies then run as plain DMA
-        without a staging copy.  A refusal is not an error: the copies still work, through pageable memory."""
-        rt = torch.cuda.cudart()
-        tensors = [self._batch.rewards, self._batch.dones] + list(self._batch.env_infos.values())
-        for st in self._steps:
-            tensors += [st.obs, st.act, st.live]
-        for st in self._eval_steps:
-            tensors += [st.obs, st.act]
-        for tns in tensors:
-            if tns.numel() == 0:
-                continue
-            err = rt.cudaHostRegister(tns.data_ptr(), tns.numel() * tns.element_size(), 0)
-            if int(err) == 0:
-                self._registered.append(tns.data_ptr())
-            else:
-                logger.log("HostEnvSampler: page-locking a shared buffer failed (%s); copies go through pageable memory" % err)
-                break
+    def _staging(self, shared):
+        """The page-locked twin of a shared step / batch array.  The workers are forked before this process allocates
+        anything page-locked and could not see such memory anyway, so what they share stays pageable; it crosses to and
+        from the device through this twin, as plain DMA.  A twin is reused only after the stream has been synchronised
+        (once per (step, group), once per batch)."""
+        if shared not in self._pinned:                    # (tensors hash by identity)
+            self._pinned[shared] = torch.empty_like(shared).pin_memory()
+        return self._pinned[shared]
+
+    def _upload(self, dst, shared):
+        host = self._staging(shared)
+        host.copy_(shared)
+        dst.copy_(host, non_blocking=True)
 
     def _alive(self):
         dead = [i for i, p in enumerate(self.workers) if p.exitcode is not None]
@@ -562,12 +555,14 @@ class HostEnvEvalSampler(HostEnvSampler):
                     self._acquire(j, "obs_ready")
                     step = self._eval_steps[j]
                     obs_dev = self.eval_step_obs[lo:lo + half_e]
-                    obs_dev.copy_(step.obs, non_blocking=True)
+                    self._upload(obs_dev, step.obs)
                     self._serve(obs_dev, s, lo, ne, half_e)
                     act_dev = self._act_dev[:half_e]
-                    step.act.copy_(act_dev.to(self._act_dtype) if self._act_dtype != torch.uint8 else act_dev,
+                    act_host = self._staging(step.act)
+                    act_host.copy_(act_dev.to(self._act_dtype) if self._act_dtype != torch.uint8 else act_dev,
                                    non_blocking=True)
                     stream.synchronize()
+                    step.act.copy_(act_host)
                     for g in self._gates[j]:
                         g.act_ready.release()
             for j in range(2):
