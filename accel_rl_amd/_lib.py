@@ -20,6 +20,7 @@ PPG_POLICY, PPG_AUX = 0, 1                                # ARL_PPG_*: arl_ppg_h
 OPT_ADAM, OPT_RMSPROP = 0, 1
 VMPO_MAX_ROWS = 65536                                     # ARL_VMPO_MAX_ROWS: rows of one arl_vmpo_weights launch
 RND_MAX_ROWS, RND_MIX_MAX_ENVS, RND_MIX_MAX_ROWS = 1 << 24, 1 << 20, 1 << 22   # ARL_RND_MAX_ROWS, ARL_RND_MIX_MAX_*
+EPI_MAX_WIDTH, EPI_MAX_MEMORY, EPI_MAX_K, EPI_MAX_ENVS = 128, 4096, 16, 65535   # ARL_EPI_MAX_*; arl_epi_knn's grid
 POPART_MAX_ROWS, POPART_MAX_HID = 1 << 22, 1 << 16        # ARL_POPART_MAX_ROWS, ARL_POPART_MAX_HID
 MAX_ACTIONS = 18
 REPLAY_MAX_HORIZON = 16
@@ -278,6 +279,12 @@ _SIGNATURES = {
     "arl_rnd_obs_prepare": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "arl_rnd_error": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "arl_rnd_reward_mix": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _f64, _f64, _f64, _vp, _vp, _vp, _vp]),
+    "arl_epi_knn": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "arl_invdyn_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "arl_invdyn_loss_parts": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _vp]),
+    "arl_epi_mix": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _vp, _vp,
+                           _vp]),
     "arl_popart_denorm": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "arl_popart_step": (_i32, [_vp, _vp, _vp, _i64, _f64, _f64, _f64, _vp, _vp, _vp, _i32, _vp, _vp]),
     "arl_acer_retrace_scan": (_i32, [_vp] * 4 + [_i32, _vp, _vp, _vp, _vp, _f64, _f64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
@@ -1066,6 +1073,13 @@ class FoldList(object):
             "arl_vmpo_head_loss_parts")
         self._n += 3                # (a refused call leaves no items behind)
 
+    def invdyn_loss(self, e, w1, b1, w2, b2, actions, weight, de, dw1, db1, dw2, db2, loss2, workspace, stream=None):
+        """NGU's inverse-dynamics head (arl_invdyn_loss_parts) with its five folds (dw1, db1, dw2, db2, loss2) left to
+        run().  e f32[2B, E]: pair b = rows 2b, 2b + 1.  workspace: invdyn_workspace()."""
+        invdyn_loss(e, w1, b1, w2, b2, actions, weight, de, dw1, db1, dw2, db2, loss2, workspace, stream,
+                    C.byref(self._items[self._n]), FOLD_MAX_ITEMS - self._n)
+        self._n += 5                # (a refused call leaves no items behind)
+
     def ln_relu_bwd(self, dy, y, z, stats, gamma, dy_masked, dz, dgamma, dbeta, workspace, stream=None):
         """ln_relu_bwd with its two column-sum folds (dgamma, dbeta) left to run()."""
         rows, width = _ln_rows(z, gamma, (dy, y, dz), stats)
@@ -1670,6 +1684,70 @@ def rnd_reward_mix(err, r_ext, n_env, horizon, rho, moments, gamma_int, c_ext, c
     _check(load().arl_rnd_reward_mix(ptr(err), ptr(r_ext), n_env, horizon, ptr(rho), ptr(moments), float(gamma_int),
                                      float(c_ext), float(c_int), ptr(r_mix), ptr(diag2), ptr(workspace),
                                      stream_ptr(stream)), "arl_rnd_reward_mix")
+
+
+# ---------------------------------------------------------------------------
+# NGU's episodic bonus: k-nearest-neighbour search in the episode's memory, kernel + modulator + mix (csrc/episodic.hip)
+# ---------------------------------------------------------------------------
+
+def invdyn_workspace(width, hidden, n_actions, device):
+    return torch.empty(max(load().arl_invdyn_workspace_bytes(width, hidden, n_actions) // 4, 4), dtype=torch.float32,
+                       device=device)
+
+
+def invdyn_loss(e, w1, b1, w2, b2, actions, weight, de, dw1, db1, dw2, db2, loss2, workspace, stream=None, items=None,
+                room=5):
+    """loss2 = (weighted mean cross-entropy, weighted accuracy) of the head relu(x w1 + b1) w2 + b2 on pairs x_b = (e[2b],
+    e[2b + 1]), and de, dw1, db1, dw2, db2; folded at once (items None) or left to a FoldList."""
+    for t, n in ((e, "e"), (w1, "w1"), (b1, "b1"), (w2, "w2"), (b2, "b2"), (weight, "weight"), (de, "de"), (dw1, "dw1"),
+                 (db1, "db1"), (dw2, "dw2"), (db2, "db2"), (loss2, "loss2"), (workspace, "workspace")):
+        _want(t, torch.float32, n)
+    _want(actions, torch.uint8, "actions")
+    batch, width = e.shape[0] // 2, e.shape[1]
+    hidden, n_act = b1.numel(), b2.numel()
+    assert e.shape[0] == 2 * batch and de.numel() == e.numel() and actions.numel() == weight.numel() == batch and \
+        w1.numel() == dw1.numel() == 2 * width * hidden and w2.numel() == dw2.numel() == hidden * n_act and \
+        db1.numel() == hidden and db2.numel() == n_act and loss2.numel() >= 2 and room >= 5, "invdyn_loss sizes"
+    assert workspace.numel() * 4 >= load().arl_invdyn_workspace_bytes(width, hidden, n_act), "workspace too small"
+    _check(load().arl_invdyn_loss_parts(ptr(e), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(actions), ptr(weight), batch, width,
+                                        hidden, n_act, ptr(de), ptr(dw1), ptr(db1), ptr(dw2), ptr(db2), ptr(loss2),
+                                        ptr(workspace), items, stream_ptr(stream)), "arl_invdyn_loss_parts")
+
+
+def epi_knn(emb, dones, n_env, horizon, mem, n_ins, k, knn, m, stream=None):
+    """knn f64[rows, k], m i32[rows]: every row's m smallest squared distances to its episode's memory (ascending, the
+    rest +inf); then mem f32[n_env, M, E] and n_ins i32[n_env] become the state after the rollout."""
+    _want(emb, torch.float32, "emb")
+    _want(mem, torch.float32, "mem")
+    _want(dones, torch.uint8, "dones")
+    _want(n_ins, torch.int32, "n_ins")
+    _want(m, torch.int32, "m")
+    _want(knn, torch.float64, "knn")
+    rows, width = n_env * horizon, emb.shape[-1]
+    assert mem.dim() == 3 and mem.shape[0] == n_env and mem.shape[2] == width, "mem [n_env, M, E]"
+    assert emb.numel() == rows * width and dones.numel() == rows and n_ins.numel() == n_env and m.numel() == rows and \
+        knn.numel() == rows * k, "epi_knn sizes"
+    _check(load().arl_epi_knn(ptr(emb), ptr(dones), n_env, horizon, width, mem.shape[1], int(k), ptr(mem), ptr(n_ins),
+                              ptr(knn), ptr(m), stream_ptr(stream)), "arl_epi_knn")
+
+
+def epi_mix(knn, m, err, r_ext, dist_mean, err_moments, eps, c, xi, s_max, mod_clip, c_ext, c_int, r_mix, diag3,
+            stream=None):
+    """r_mix = c_ext r_ext + c_int r_epi mod: the distances' running mean, NGU's kernel, the clipped modulator from RND's
+    error (err None: 1), in one launch.  diag3 = (mean r_epi, mean mod, the running mean distance)."""
+    _want(knn, torch.float64, "knn")
+    _want(m, torch.int32, "m")
+    for t, n in ((r_ext, "r_ext"), (r_mix, "r_mix"), (diag3, "diag3")) + (() if err is None else ((err, "err"),)):
+        _want(t, torch.float32, n)
+    for t, n in ((dist_mean, "dist_mean"), (err_moments, "err_moments")):
+        _want(t, torch.float64, n)
+    rows = m.numel()
+    k = knn.numel() // rows
+    assert knn.numel() == rows * k and r_ext.numel() == r_mix.numel() == rows and (err is None or err.numel() == rows) and \
+        dist_mean.numel() == 2 and err_moments.numel() == 3 and diag3.numel() >= 3, "epi_mix sizes"
+    _check(load().arl_epi_mix(ptr(knn), ptr(m), ptr(err), ptr(r_ext), rows, k, ptr(dist_mean), ptr(err_moments),
+                              float(eps), float(c), float(xi), float(s_max), float(mod_clip), float(c_ext), float(c_int),
+                              ptr(r_mix), ptr(diag3), stream_ptr(stream)), "arl_epi_mix")
 
 
 # ---------------------------------------------------------------------------

@@ -652,6 +652,101 @@ int arl_rnd_reward_mix(const float* err, const float* r_ext, int64_t n_env, int3
                        double gamma_int, double c_ext, double c_int, float* r_mix, float* diag2, void* workspace,
                        void* stream);
 
+/* The episodic novelty bonus of NGU ("Never Give Up", Badia et al. 2020; csrc/episodic.hip): a k-nearest-neighbour
+ * search of every rollout row's embedding against the memory of its own episode, and the stage that turns the distances
+ * into the mixed reward.  float64 on the promoted inputs, every output rounded once, no float atomics, no process-wide
+ * state, nothing contracted into an fma: tests/ngu_ref.py restates both entry points in NumPy, bit for bit.
+ *
+ * arl_epi_knn: search, then append (two launches on `stream`).
+ *   Carried across calls, zero-initialised by the caller: mem f32[n_env][memory_size][width] and n_ins i32[n_env], the
+ *   number of embeddings inserted in env n's current episode; entry i lives in slot i mod memory_size.  (Past 2^30 the
+ *   append folds n_ins to memory_size + n_ins mod memory_size: the same slots, the ring still full.)
+ *   emb f32[n_env][horizon][width]: row (n, t) is the embedding of the newest plane of that transition's NEXT observation
+ *   (arl_rnd_reward_mix's row order); dones u8[n_env][horizon].
+ *   The episode sequence of env n is the carried entries followed by this rollout's rows.  A row with done != 0 starts a
+ *   new episode: its embedding is entry 0 of that episode (the next observation after a done is the new episode's first
+ *   frame) and it has no candidates.  Any other row's candidates are the min(memory_size, p) most recent entries of its
+ *   own episode that precede it, p = the entries of the current episode before the row (the carried n_ins when no done
+ *   came earlier in the rollout, plus the rollout's rows since the last done, the done row included): a ring that is
+ *   overwritten in the middle of the rollout is modelled exactly.
+ *   distance(a, b) = sum_e ((double) a_e - (double) b_e)^2, e ascending from 0.0 -- the differences, not |a|^2 + |b|^2 -
+ *   2ab, which cancels on the near-duplicates the bonus is decided on (hence the vector ALU, not MFMA).
+ *   knn f64[rows][k]: the m = min(k, candidates) smallest distances of the row, ascending; slots m .. k - 1 hold
+ *   +infinity.  m i32[rows].  Equal distances need no rule: they give equal values.
+ *   Append: after the search mem and n_ins are the state after the rollout.  With a done in the rollout, the last at row
+ *   L: every slot is 0 except those of entries 0 .. horizon - 1 - L (rows L .. horizon - 1), n_ins = horizon - L;
+ *   without one, rows 0 .. horizon - 1 become entries n_ins .. n_ins + horizon - 1.  Only the last memory_size entries
+ *   are written, each slot once.
+ *   Work split: grid (ceil(horizon / 4), n_env), four waves, one row per wave, the row's embedding in registers; the
+ *   candidates (the ring by age, then the rollout's earlier rows) pass through LDS 64 at a time, once for the four rows,
+ *   row stride width + 1 words; a lane keeps the 16 smallest distances it has seen sorted in registers and the wave takes
+ *   k times the smallest head of its 64 lists.
+ *   Limits (ARL_E_RANGE): width a multiple of 4 in 4 .. ARL_EPI_MAX_WIDTH, 1 <= memory_size <= ARL_EPI_MAX_MEMORY,
+ *   1 <= k <= ARL_EPI_MAX_K, 1 <= n_env <= 65535, 1 <= horizon <= ARL_RND_MAX_HORIZON, n_env * horizon <=
+ *   ARL_RND_MAX_ROWS.  A NULL pointer: ARL_E_ARG.  emb or mem not 16-byte, knn not 8-byte, n_ins or m not 4-byte aligned:
+ *   ARL_E_ALIGN.  A refused call launches nothing and writes nothing.
+ *
+ * arl_epi_mix: one workgroup of 1 024 threads, like arl_rnd_reward_mix.  Carried: dist_mean f64[2] = (count, mean) of
+ *   all valid distances seen, err_moments f64[3] = (count, mean, m2) of err; both start as zeros.
+ *   1. S = the sum of knn[j][i], i < m_j (thread t adds rows t, t + 1024, ... in ascending order, each row's values
+ *      ascending; then arl_rnd_reward_mix's workgroup sum), n = their number.  With n > 0: w = n / (count + n), mean <-
+ *      mean + (S / n - mean) w, count <- count + n -- BEFORE use.
+ *   2. row j with m_j > 0: dn_i = max(knn[j][i] / max(mean, 1e-8) - xi, 0), K_i = eps / (dn_i + eps), s = sqrt(sum_i K_i)
+ *      + c (i ascending from 0.0), r_epi = s > s_max ? 0 : 1 / s.  Rows with m_j = 0 -- done rows, and the very first row
+ *      of a run -- get r_epi = 0: a choice (nothing to compare with says nothing about novelty).
+ *   3. err_or_null given (RND's per-row error f32[rows]): its batch mean and m2 (two passes, float64) are merged into
+ *      err_moments by Chan's rule BEFORE use, as arl_rnd_reward_mix merges; alpha = 1 + ((double) err_j - mean) /
+ *      sqrt(m2 / count + 1e-8), mod = min(max(alpha, 1), mod_clip).  NULL: mod = 1, err_moments untouched.
+ *   4. a = c_ext (double) r_ext_j, b = c_int (r_epi mod), r_mix_j = (float)(b == 0 ? a : a + b): c_int = 0 returns
+ *      c_ext r_ext, for c_ext = 1 r_ext's bits.  diag3 = (mean r_epi, mean mod, the distances' running mean) over rows.
+ *   Limits: 1 <= rows <= ARL_RND_MIX_MAX_ROWS, 1 <= k <= ARL_EPI_MAX_K (ARL_E_RANGE); a NULL pointer other than
+ *   err_or_null, eps <= 0, c < 0, xi < 0, s_max <= 0, mod_clip < 1, any of them or c_ext / c_int not finite, r_mix equal
+ *   to an input (ARL_E_ARG); knn, dist_mean, err_moments not 8-byte, another pointer not 4-byte aligned (ARL_E_ALIGN).
+ *   m values above k are read as k.                                                                                  */
+#define ARL_EPI_MAX_WIDTH  128
+#define ARL_EPI_MAX_MEMORY 4096
+#define ARL_EPI_MAX_K      16
+int arl_epi_knn(const float* emb, const uint8_t* dones, int64_t n_env, int32_t horizon, int32_t width, int32_t memory_size,
+                int32_t k, float* mem, int32_t* n_ins, double* knn, int32_t* m, void* stream);
+int arl_epi_mix(const double* knn, const int32_t* m, const float* err_or_null, const float* r_ext, int64_t rows, int32_t k,
+                double* dist_mean, double* err_moments, double eps, double c, double xi, double s_max, double mod_clip,
+                double c_ext, double c_int, float* r_mix, float* diag3, void* stream);
+
+/* arl_invdyn_loss_parts: NGU's inverse-dynamics head (csrc/episodic.hip), which trains the embedding: forward, loss and
+ * every gradient in one launch, plus the fold.  Plain fp32.
+ *   e f32[2 batch][width]: rows 2b and 2b + 1 are the embeddings of the frame before and after the action of pair b; read
+ *   as x f32[batch][2 width] that is their concatenation.  w1 f32[2 width][hidden], b1 f32[hidden], w2
+ *   f32[hidden][n_actions], b2 f32[n_actions]; actions u8[batch] (a value >= n_actions is read as n_actions - 1); weight
+ *   f32[batch], 1 or 0.
+ *   hid = max(x w1 + b1, 0), l = hid w2 + b2, CE_b = log(sum_a exp(l_a - max l)) + max l - l_action (expf / logf of the
+ *   device library, a ascending), D = max(sum_b weight_b, 1) (float64, the same order in every workgroup).
+ *   loss2[0] = sum_b weight_b CE_b / D, loss2[1] = sum_b weight_b [argmax_a l_a == action_b] / D (the first maximum);
+ *   d l = (weight_b / D)(softmax(l) - onehot), exactly 0 where weight_b is 0, and from it de f32[2 batch][width], dw1, db1,
+ *   dw2, db2 in the parameters' shapes.  An all-masked batch gives loss 0 and zero gradients, never NaN.
+ *   Work split: min(ceil(batch / ARL_INVDYN_TILE), ARL_INVDYN_MAX_PARTS) workgroups of four waves, workgroup g takes the
+ *   tiles g, g + grid, ... of 32 pairs; w1 and w2 stay in LDS for the life of the workgroup; the six products (hidden
+ *   layer, logits, hidden gradient, de, dw1, dw2) run on v_mfma_f32_32x32x2_f32, k ascending; the weight gradients stay in
+ *   a wave's accumulators across its tiles.  Each workgroup writes one partial of dw1, db1, dw2, db2 and (loss, accuracy)
+ *   to workspace (>= arl_invdyn_workspace_bytes(width, hidden, n_actions) bytes, 0 for refused sizes; 16-byte aligned);
+ *   arl_fold_many adds the workgroups' partials in its fixed order -- at once (items5_or_null NULL: a second launch here)
+ *   or later (five arl_fold_item are filled in; the workspace stays live until the caller's arl_fold_many).  No atomics;
+ *   bit-identical run to run.  de is written by the launch itself.
+ *   Limits (ARL_E_RANGE): width a multiple of 4 in 4 .. ARL_EPI_MAX_WIDTH, hidden a multiple of 4 in 4 ..
+ *   ARL_INVDYN_MAX_HIDDEN, 2 <= n_actions <= ARL_INVDYN_MAX_ACTIONS, 1 <= batch <= ARL_RND_MAX_ROWS, and -- the weights
+ *   resident in LDS, dw1 resident in accumulators -- ceil(2 width / 32) ceil(hidden / 32) <= 16 (width 128 goes with
+ *   hidden <= 64, hidden 256 with width <= 32) with at most 159 KiB of LDS in all.  A NULL pointer other than
+ *   items5_or_null: ARL_E_ARG.  e, de, the gradients, loss2 or workspace not 16-byte, another float pointer not 4-byte
+ *   aligned: ARL_E_ALIGN.  A refused call launches nothing and writes nothing.                                        */
+#define ARL_INVDYN_TILE        32
+#define ARL_INVDYN_MAX_PARTS   64
+#define ARL_INVDYN_MAX_HIDDEN  256
+#define ARL_INVDYN_MAX_ACTIONS 64
+int64_t arl_invdyn_workspace_bytes(int32_t width, int32_t hidden, int32_t n_actions);
+int arl_invdyn_loss_parts(const float* e, const float* w1, const float* b1, const float* w2, const float* b2,
+                          const uint8_t* actions, const float* weight, int64_t batch, int32_t width, int32_t hidden,
+                          int32_t n_actions, float* de, float* dw1, float* db1, float* dw2, float* db2, float* loss2,
+                          void* workspace, struct arl_fold_item* items5_or_null, void* stream);
+
 /* PopArt (adaptive value normalisation, single task; csrc/popart.hip): what an actor-critic whose value output is a
  * NORMALISED value n adds between its rollout and its optimiser step.  The unnormalised value of a state is sigma n + mu.
  * float64 on the promoted inputs, every output rounded once, no float atomics, no process-wide state; nothing
