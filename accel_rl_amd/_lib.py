@@ -283,6 +283,8 @@ _SIGNATURES = {
     "arl_invdyn_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "arl_invdyn_loss_parts": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _vp]),
+    "arl_curl_workspace_bytes": (_i64, [_i32]),
+    "arl_curl_loss_parts": (_i32, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "arl_epi_mix": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _vp, _vp,
                            _vp]),
     "arl_popart_denorm": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
@@ -1080,6 +1082,13 @@ class FoldList(object):
                     C.byref(self._items[self._n]), FOLD_MAX_ITEMS - self._n)
         self._n += 5                # (a refused call leaves no items behind)
 
+    def curl_loss(self, zq, zk, w, coef, dzq, dw, loss2, workspace, stream=None):
+        """CURL's contrastive loss (arl_curl_loss_parts) with its two folds (dw, loss2) left to run().  workspace:
+        curl_workspace()."""
+        curl_loss(zq, zk, w, coef, dzq, dw, loss2, workspace, stream, C.byref(self._items[self._n]),
+                  FOLD_MAX_ITEMS - self._n)
+        self._n += 2                # (a refused call leaves no items behind)
+
     def ln_relu_bwd(self, dy, y, z, stats, gamma, dy_masked, dz, dgamma, dbeta, workspace, stream=None):
         """ln_relu_bwd with its two column-sum folds (dgamma, dbeta) left to run()."""
         rows, width = _ln_rows(z, gamma, (dy, y, dz), stats)
@@ -1712,6 +1721,27 @@ def invdyn_loss(e, w1, b1, w2, b2, actions, weight, de, dw1, db1, dw2, db2, loss
     _check(load().arl_invdyn_loss_parts(ptr(e), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(actions), ptr(weight), batch, width,
                                         hidden, n_act, ptr(de), ptr(dw1), ptr(db1), ptr(dw2), ptr(db2), ptr(loss2),
                                         ptr(workspace), items, stream_ptr(stream)), "arl_invdyn_loss_parts")
+
+
+# ---------------------------------------------------------------------------
+# CURL's contrastive loss: InfoNCE with a bilinear similarity over one minibatch (csrc/curl.hip)
+# ---------------------------------------------------------------------------
+
+def curl_workspace(width, device):
+    return torch.empty(max(load().arl_curl_workspace_bytes(width) // 4, 4), dtype=torch.float32, device=device)
+
+
+def curl_loss(zq, zk, w, coef, dzq, dw, loss2, workspace, stream=None, items=None, room=2):
+    """loss2 = (coef * mean_i (logsumexp_j S_ij - S_ii), share of rows whose arg-max is the diagonal) for S = zq w zk^T,
+    and dzq, dw (zk is a constant); folded at once (items None) or left to a FoldList."""
+    for t, n in ((zq, "zq"), (zk, "zk"), (w, "w"), (dzq, "dzq"), (dw, "dw"), (loss2, "loss2"), (workspace, "workspace")):
+        _want(t, torch.float32, n)
+    batch, width = zq.shape
+    assert tuple(zk.shape) == (batch, width) and dzq.numel() == zq.numel() and w.numel() == dw.numel() == width * width \
+        and loss2.numel() >= 2 and room >= 2, "curl_loss sizes"
+    assert workspace.numel() * 4 >= load().arl_curl_workspace_bytes(width), "workspace too small"
+    _check(load().arl_curl_loss_parts(ptr(zq), ptr(zk), ptr(w), batch, width, float(coef), ptr(dzq), ptr(dw), ptr(loss2),
+                                      ptr(workspace), items, stream_ptr(stream)), "arl_curl_loss_parts")
 
 
 def epi_knn(emb, dones, n_env, horizon, mem, n_ins, k, knn, m, stream=None):

@@ -1,0 +1,1 @@
+from accel_rl_amd.algos.dqn.curl import CURL  # noqa: F401

@@ -159,6 +159,31 @@ class FqfOptimizer(DqnOptimizer):
         _lib.opt_step(self._frac_state, self._frac_method.kernel_id, self._frac_learning_rate, avg_factor, 0.0, b1, b2, eps)
 
 
+class CurlOptimizer(DqnOptimizer):
+    """DqnOptimizer for a policy with a momentum encoder (AtariCurlDqnPolicy): the whole bucket -- conv stack, dense
+    layers, output layer, projection, bilinear form -- takes DqnOptimizer's one update with one state; then the momentum
+    encoder moves by momentum_tau towards the updated online encoder (policy.momentum_step: arl_acer_avg_step), inside
+    the same captured graph."""
+
+    def __init__(self, learning_rate, update_method, update_method_args=None, grad_norm_clip=None,
+                 scale_conv_grads=False, use_graph=True, momentum_tau=0.001):
+        if not (np.isfinite(momentum_tau) and 0 <= momentum_tau <= 1):
+            raise ValueError("momentum_tau must lie in [0, 1]")
+        super().__init__(learning_rate, update_method, update_method_args=update_method_args,
+                         grad_norm_clip=grad_norm_clip, scale_conv_grads=scale_conv_grads, use_graph=use_graph)
+        self._momentum_tau = float(momentum_tau)
+
+    def _setup_bucket(self, target, lr_mult, givens=None):
+        if not hasattr(target, "momentum_step"):
+            raise TypeError("CurlOptimizer updates a policy with a momentum encoder (AtariCurlDqnPolicy), got %s" %
+                            type(target).__name__)
+        super()._setup_bucket(target, lr_mult, givens)
+
+    def _apply_update(self, avg_factor=1.0):
+        super()._apply_update(avg_factor)
+        self._target.momentum_step(self._momentum_tau)
+
+
 class SacOptimizer(DqnOptimizer):
     """DqnOptimizer for AtariSacDiscretePolicy: four ranges -- the actor's bucket, the two critics' buckets and log_alpha
     -- each with its own ArlOptState, slots, step count and norm log, each updated by one arl_opt_step inside the

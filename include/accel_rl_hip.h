@@ -747,6 +747,37 @@ int arl_invdyn_loss_parts(const float* e, const float* w1, const float* b1, cons
                           int32_t n_actions, float* de, float* dw1, float* db1, float* dw2, float* db2, float* loss2,
                           void* workspace, struct arl_fold_item* items5_or_null, void* stream);
 
+/* arl_curl_loss_parts: the contrastive (InfoNCE) loss of CURL (Srinivas, Laskin, Abbeel 2020; csrc/curl.hip) with a
+ * bilinear similarity, over one minibatch whose other rows are the negatives: forward, loss and every gradient in one
+ * launch, plus the fold.  Plain fp32.
+ *   zq f32[batch][width]: the queries; zk f32[batch][width]: the keys, constants (no gradient); w f32[width][width].
+ *   P = zq w, S = P zk^T (batch x batch), L_i = log(sum_j exp(S_ij - max_j S_ij)) + max_j S_ij - S_ii (expf / logf of the
+ *   device library; the sum over key tiles of 32 in ascending order, rescaled as the running maximum grows).
+ *   loss2[0] = coef / batch sum_i L_i, loss2[1] = #{i: the first arg-max of S_i. is i} / batch;
+ *   G = coef / batch (softmax_row(S) - I), dP = G zk, dzq f32[batch][width] = dP w^T, dw f32[width][width] = zq^T dP.
+ *   coef = 0 gives loss 0 and gradients that are exactly 0.
+ *   Work split: min(ceil(batch / ARL_CURL_TILE), ARL_CURL_MAX_PARTS) workgroups of four waves, workgroup g takes the query
+ *   tiles g, g + grid, ... of 32 rows; w stays in LDS for the life of the workgroup; the keys stream through LDS in tiles
+ *   of 32 rows twice (pass 1: the online soft-max, one lane per query row; pass 2: S again, G, dP), so S never exists in
+ *   memory; the five products run on v_mfma_f32_32x32x2_f32; the blocks of dw stay in a wave's accumulators across its
+ *   tiles.  Each workgroup writes one partial of dw and of (loss, accuracy) to workspace (>=
+ *   arl_curl_workspace_bytes(width) bytes, 0 for a refused width; 16-byte aligned); arl_fold_many adds the workgroups'
+ *   partials in its fixed order -- at once (items2_or_null NULL: a second launch here) or later (two arl_fold_item are
+ *   filled in; the workspace stays live until the caller's arl_fold_many).  No atomics; bit-identical run to run.  dzq is
+ *   written by the launch itself.
+ *   Limits (ARL_E_RANGE): width a multiple of 4 in 4 .. ARL_CURL_MAX_WIDTH (146 KiB of LDS at 128), 1 <= batch <=
+ *   ARL_CURL_MAX_ROWS.  A NULL pointer other than items2_or_null, a coef that is not finite: ARL_E_ARG.  zq, zk, dzq, dw,
+ *   loss2 or workspace not 16-byte, w not 4-byte aligned: ARL_E_ALIGN.  A refused call launches nothing and writes
+ *   nothing.                                                                                                          */
+#define ARL_CURL_TILE      32
+#define ARL_CURL_MAX_PARTS 64
+#define ARL_CURL_MAX_WIDTH 128
+#define ARL_CURL_MAX_ROWS  4096
+int64_t arl_curl_workspace_bytes(int32_t width);
+int arl_curl_loss_parts(const float* zq, const float* zk, const float* w, int64_t batch, int32_t width, float coef,
+                        float* dzq, float* dw, float* loss2, void* workspace, struct arl_fold_item* items2_or_null,
+                        void* stream);
+
 /* PopArt (adaptive value normalisation, single task; csrc/popart.hip): what an actor-critic whose value output is a
  * NORMALISED value n adds between its rollout and its optimiser step.  The unnormalised value of a state is sigma n + mu.
  * float64 on the promoted inputs, every output rounded once, no float atomics, no process-wide state; nothing
