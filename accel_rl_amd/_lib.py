@@ -257,6 +257,10 @@ _SIGNATURES = {
     "arl_maxpool3s2_fwd": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "arl_maxpool3s2_bwd": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "arl_add_relu": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "arl_attn_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _vp]),
+    "arl_attn_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _vp]),
+    "arl_entity_coords_fwd": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "arl_entity_coords_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "arl_gather_scale_obs_nhwc_any": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp]),
     "arl_mdqn_loss": (_i32, [_vp] * 7 + [_i64, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "arl_sacd_act": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
@@ -1993,6 +1997,85 @@ def add_relu(a, b, out, relu=None, stream=None):
         _want(t, torch.float32, "add_relu tensors")
         assert t.numel() == a.numel(), "sizes"
     _check(load().arl_add_relu(ptr(a), ptr(b), a.numel(), ptr(out), ptr(relu), stream_ptr(stream)), "arl_add_relu")
+
+
+# ---------------------------------------------------------------------------
+# Multi-head self-attention over the positions of a feature map and its coordinate channels (csrc/attention.hip)
+# ---------------------------------------------------------------------------
+
+ATTN_MAX_POS, ATTN_MAX_HEAD_DIM, ATTN_MAX_WIDTH, ATTN_MAX_GRID = 64, 64, 256, 1024      # ARL_ATTN_MAX_*
+
+
+def attn_shape_ok(n_pos, n_heads, head_dim):
+    """What arl_attn_fwd / arl_attn_bwd take (accel_rl_hip.h); needs no device."""
+    return (1 <= n_pos <= ATTN_MAX_POS and 4 <= head_dim <= ATTN_MAX_HEAD_DIM and head_dim % 4 == 0 and n_heads >= 1 and
+            n_heads * head_dim <= ATTN_MAX_WIDTH)
+
+
+def _attn_dims(qkv, out, lse):
+    """(batch, n_pos, n_heads, head_dim) of qkv [B, N, 3, H, d], after the shape checks of out [B, N, H * d] and lse
+    [B, H, N] (may be None)."""
+    if qkv.dim() != 5 or qkv.shape[2] != 3:
+        raise ValueError("qkv must be [batch, n_pos, 3, n_heads, head_dim], got %s" % (tuple(qkv.shape),))
+    b, n, _, h, d = qkv.shape
+    _want(qkv, torch.float32, "qkv")
+    _want(out, torch.float32, "out")
+    if out.numel() != b * n * h * d or out.shape[0] != b:
+        raise ValueError("out must hold [%d, %d, %d] floats, got %s" % (b, n, h * d, tuple(out.shape)))
+    if lse is not None:
+        _want(lse, torch.float32, "lse")
+        if tuple(lse.shape) != (b, h, n):
+            raise ValueError("lse must be [%d, %d, %d], got %s" % (b, h, n, tuple(lse.shape)))
+    return b, n, h, d
+
+
+def attn_fwd(qkv, out, lse=None, scale=None, stream=None):
+    """out [B, N, H * d] = softmax_j(scale Q K^T) V per sample and head of qkv [B, N, 3, H, d]; lse [B, H, N] (training:
+    attn_bwd's input) = logsumexp_j of the scaled scores.  scale: 1 / sqrt(d) unless given."""
+    b, n, h, d = _attn_dims(qkv, out, lse)
+    scale = d ** -0.5 if scale is None else scale
+    _check(load().arl_attn_fwd(ptr(qkv), ptr(out), ptr(lse), b, n, h, d, float(scale), stream_ptr(stream)), "arl_attn_fwd")
+
+
+def attn_bwd(qkv, out, lse, dout, dqkv, scale=None, stream=None):
+    """dqkv (qkv's layout) = the gradient of attn_fwd's input given dout, the gradient of its output."""
+    b, n, h, d = _attn_dims(qkv, out, lse)
+    if lse is None:
+        raise ValueError("attn_bwd needs the forward's lse")
+    _want(dout, torch.float32, "dout")
+    _want(dqkv, torch.float32, "dqkv")
+    if dout.numel() != out.numel() or dqkv.numel() != qkv.numel():
+        raise ValueError("dout / dqkv must have the sizes of out / qkv")
+    scale = d ** -0.5 if scale is None else scale
+    _check(load().arl_attn_bwd(ptr(qkv), ptr(out), ptr(lse), ptr(dout), ptr(dqkv), b, n, h, d, float(scale),
+                               stream_ptr(stream)), "arl_attn_bwd")
+
+
+def _coords_dims(x, y):
+    """(batch, h, w, channels) of x [B, h, w, C] next to y [B, h, w, C + 4]."""
+    if x.dim() != 4 or tuple(y.shape) != tuple(x.shape[:3]) + (x.shape[3] + 4,):
+        raise ValueError("entity coords: x [B, h, w, C] and y [B, h, w, C + 4], got %s and %s" %
+                         (tuple(x.shape), tuple(y.shape)))
+    _want(x, torch.float32, "x")
+    _want(y, torch.float32, "y")
+    return tuple(x.shape)
+
+
+def entity_coords_fwd(x, y, stream=None):
+    """y [B, h, w, C + 4] = x [B, h, w, C] with the column and row coordinate in -1 .. 1 and two zero channels appended."""
+    b, h, w, c = _coords_dims(x, y)
+    _check(load().arl_entity_coords_fwd(ptr(x), b, h, w, c, ptr(y), stream_ptr(stream)), "arl_entity_coords_fwd")
+
+
+def entity_coords_bwd(g, d_y, mask, g_in, stream=None):
+    """g_in = g + d_y[..., :C] (+0 where mask <= 0, with a mask); g_in may be g."""
+    b, h, w, c = _coords_dims(g, d_y)
+    for t, name in ((g_in, "g_in"),) + (() if mask is None else ((mask, "mask"),)):
+        _want(t, torch.float32, name)
+        if tuple(t.shape) != tuple(g.shape):
+            raise ValueError("entity coords: %s must have g's shape" % name)
+    _check(load().arl_entity_coords_bwd(ptr(g), ptr(d_y), ptr(mask), b, h, w, c, ptr(g_in), stream_ptr(stream)),
+           "arl_entity_coords_bwd")
 
 
 # ---------------------------------------------------------------------------

@@ -1,0 +1,421 @@
+// Multi-head self-attention over the positions of one feature map, forward and backward, for gfx950: the core of the
+// relational policy (Zambaldi et al. 2018; policies/atari_relational_policy.py), and the two streaming kernels that
+// append and strip its coordinate channels.
+//
+//   arl_attn_fwd            S = scale Q K^T, P = softmax_j(S), O = P V per sample and head [, lse = logsumexp_j S]
+//   arl_attn_bwd            S again (the forward's instructions), P = exp(S - lse), D_i = sum_e dO_ie O_ie,
+//                           dV = P^T dO, dP = dO V^T, dS = scale P o (dP - D), dQ = dS K, dK = dS^T Q
+//   arl_entity_coords_fwd   y = [x, (2 j - (w - 1)) / (w - 1), (2 i - (h - 1)) / (h - 1), 0, 0] along the channels
+//   arl_entity_coords_bwd   g_in = g + d_y[..., :C] [, +0 where mask <= 0]
+//
+// Attention.  One work item is one (sample, head); a workgroup of four waves walks the items grid-stride (item g,
+// g + grid, ...), and an item's whole attention lives in the LDS of its compute unit: Q, K, V (and dO) as [64][d + 1]
+// tiles, S / P (and dS) as [64][65].  Every row stride is odd, so an operand read down a column (P^T, dS^T, K^T, V^T)
+// is as conflict-free as one along a row.  Rows from N up are zeros in every tile and in P and dS, and the reductions
+// over positions stop at N.  All six products run on v_mfma_f32_32x32x2_f32, operands as they are: S, dP and dS are
+// 2 x 2 blocks of 32 x 32, one per wave; a [64][d] product (O, dV, dQ, dK) is 2 x 2 blocks too where d > 32, and where
+// d <= 32 its two blocks deal the reduction out in halves (positions 0 .. 31 and 32 .. 63) to two waves each: the
+// second half's partial goes through a tile that is free at that point and is added to the first's.  The soft-max and
+// D_i take four threads per row, each walking every fourth column (every fourth float4) in ascending order, the four
+// partial sums added as ((p0 + p1) + p2) + p3.  Every output element has one writer: plain vector stores, no atomics,
+// no partial sums in global memory; nothing depends on the grid, and two runs give the same bits.  P never leaves LDS.
+// The streaming kernels are csrc/resnet.hip's kind: one float4 per thread and step, no LDS.
+// Compiled with -ffp-contract=off and without packed fp32 instructions.
+#include "arl_common.h"
+
+#include <math.h>
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int AT_THREADS = 256;
+constexpr int AT_POS = ARL_ATTN_MAX_POS;        // rows of every tile
+constexpr int AT_LS = AT_POS + 1;               // row stride of S / P / dS
+constexpr int AT_SBLK = AT_POS * AT_LS;
+
+// D[i][j] += sum_k a(i, k) b(k, j) over kb <= k < ke (operands from ke on read as 0); i, j = 0 .. 31
+template <class FA, class FB>
+__device__ __forceinline__ f32x16 mm32(f32x16 acc, int kb, int ke, int lane, FA a, FB b) {
+    const int l31 = lane & 31, half = lane >> 5;
+    for (int k0 = kb; k0 < ke; k0 += 2) {
+        const int k = k0 + half;
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(k < ke ? a(l31, k) : 0.f, k < ke ? b(k, l31) : 0.f, acc, 0, 0, 0);
+    }
+    return acc;
+}
+__device__ __forceinline__ int acc_row(int v, int lane) { return (v & 3) + 8 * (v >> 2) + 4 * (lane >> 5); }
+
+// rows 0 .. 63 of a tile from src (row n at src + n * row_stride, d floats, 16-byte aligned); rows from N up are zeros
+__device__ __forceinline__ void load_tile(float* dst, const float* __restrict__ src, int64_t row_stride, int N, int d,
+                                          int ld, int tid) {
+    const int d4 = d >> 2;
+    for (int i = tid; i < AT_POS * d4; i += AT_THREADS) {
+        const int r = i / d4, c = (i - r * d4) * 4;
+        float4 v = {0.f, 0.f, 0.f, 0.f};
+        if (r < N) v = *reinterpret_cast<const float4*>(src + r * row_stride + c);
+        float* o = dst + r * ld + c;
+        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+    }
+}
+
+// this wave's 32 x 32 block (rb, cb) of Q K^T, not yet scaled: the one instruction sequence of both passes
+__device__ __forceinline__ f32x16 qk_block(const float* sQ, const float* sK, int ld, int d, int rb, int cb, int lane) {
+    f32x16 acc = {};
+    return mm32(acc, 0, d, lane, [&](int i, int k) { return sQ[(rb + i) * ld + k]; },
+                [&](int k, int j) { return sK[(cb + j) * ld + k]; });
+}
+
+// C[64][d] = A B over the positions k < kn: a(row, k), b(k, col) with row in 0 .. 63 and col in 0 .. 63 (b answers 0 for
+// col >= d); emit(row, col, value) once per element with col < d.  d > 32: block (wave / 2, wave % 2).  d <= 32: row
+// block wave % 2, positions [32 (wave / 2), 32 (wave / 2) + 32): waves 2 and 3 leave their partial in `part` ([64][ld],
+// free at this point), waves 0 and 1 add it to theirs -- first half + second half -- and emit.  All four waves call.
+template <class FA, class FB, class FE>
+__device__ __forceinline__ void pos_product(int d, int kn, float* part, int ld, int wave, int lane, FA a, FB b, FE emit) {
+    const int l31 = lane & 31;
+    f32x16 acc = {};
+    if (d > 32) {
+        const int rb = (wave >> 1) * 32, cb = (wave & 1) * 32;
+        acc = mm32(acc, 0, kn, lane, [&](int i, int k) { return a(rb + i, k); }, [&](int k, int j) { return b(k, cb + j); });
+        if (cb + l31 < d) {
+#pragma unroll
+            for (int v = 0; v < 16; ++v) emit(rb + acc_row(v, lane), cb + l31, acc[v]);
+        }
+        return;
+    }
+    const int rb = (wave & 1) * 32, half = wave >> 1;
+    const int kb = half * 32, ke = kn < kb + 32 ? kn : kb + 32;         // (an empty half leaves zeros)
+    acc = mm32(acc, kb, ke, lane, [&](int i, int k) { return a(rb + i, k); }, [&](int k, int j) { return b(k, j); });
+    if (half == 1 && l31 < d) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v) part[(rb + acc_row(v, lane)) * ld + l31] = acc[v];
+    }
+    __syncthreads();
+    if (half == 0 && l31 < d) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            const int r = rb + acc_row(v, lane);
+            emit(r, l31, acc[v] + part[r * ld + l31]);
+        }
+    }
+}
+
+// ((p0 + p1) + p2) + p3 of the four threads of a row (lanes 4 r .. 4 r + 3)
+__device__ __forceinline__ float row_sum4(float p, int lane) {
+    const int base = lane & ~3;
+    const float p0 = __shfl(p, base, 64), p1 = __shfl(p, base + 1, 64), p2 = __shfl(p, base + 2, 64),
+                p3 = __shfl(p, base + 3, 64);
+    return ((p0 + p1) + p2) + p3;
+}
+
+__global__ __launch_bounds__(AT_THREADS, 2) void attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out,
+                                                              float* __restrict__ lse, int64_t items, int N, int H, int d,
+                                                              float scale) {
+    extern __shared__ float lds[];
+    const int ld = d + 1, tile = AT_POS * ld;
+    float* sQ = lds;                            // [64][d + 1]; after S: the second halves' partial of O
+    float* sK = sQ + tile;
+    float* sV = sK + tile;
+    float* sS = sV + tile;                      // [64][65]  S, then exp(S - max)
+    float* sInv = sS + AT_SBLK;                 // [64]      1 / sum_j exp(S_ij - max_i)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31;
+    const int64_t HD = (int64_t)H * d;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / H;
+        const int h = (int)(item - b * H);
+        const float* base = qkv + b * N * 3 * HD + (int64_t)h * d;
+        __syncthreads();                        // the item before has been read
+        load_tile(sQ, base, 3 * HD, N, d, ld, tid);
+        load_tile(sK, base + HD, 3 * HD, N, d, ld, tid);
+        load_tile(sV, base + 2 * HD, 3 * HD, N, d, ld, tid);
+        __syncthreads();
+        {
+            const int rb = (wave >> 1) * 32, cb = (wave & 1) * 32;
+            const f32x16 acc = qk_block(sQ, sK, ld, d, rb, cb, lane);
+#pragma unroll
+            for (int v = 0; v < 16; ++v) sS[(rb + acc_row(v, lane)) * AT_LS + cb + l31] = scale * acc[v];
+        }
+        __syncthreads();
+        {                                       // soft-max: row tid / 4, columns tid % 4, + 4, ..
+            const int i = tid >> 2, q = tid & 3;
+            float* s = sS + i * AT_LS;
+            float m = -INFINITY, p = 0.f;
+            if (i < N) {
+                for (int j = q; j < N; j += 4) m = fmaxf(m, s[j]);
+            }
+            m = fmaxf(m, __shfl_xor(m, 1, 64));
+            m = fmaxf(m, __shfl_xor(m, 2, 64));
+            if (i < N) {
+                for (int j = q; j < N; j += 4) {
+                    const float e = expf(s[j] - m);
+                    s[j] = e;
+                    p += e;
+                }
+                for (int j = N + q; j < AT_POS; j += 4) s[j] = 0.f;
+            } else {
+                for (int j = q; j < AT_POS; j += 4) s[j] = 0.f;
+            }
+            const float l = row_sum4(p, lane);
+            if (q == 0) {
+                sInv[i] = i < N ? 1.f / l : 0.f;
+                if (lse && i < N) lse[item * N + i] = m + logf(l);
+            }
+        }
+        __syncthreads();
+        float* o = out + b * N * HD + (int64_t)h * d;
+        pos_product(d, N, sQ, ld, wave, lane, [&](int i, int k) { return sS[i * AT_LS + k]; },
+                    [&](int k, int e) { return e < d ? sV[k * ld + e] : 0.f; },
+                    [&](int i, int e, float v) { if (i < N) o[i * HD + e] = v * sInv[i]; });
+    }
+}
+
+__global__ __launch_bounds__(AT_THREADS, 2) void attn_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ out,
+                                                              const float* __restrict__ lse, const float* __restrict__ dout,
+                                                              float* __restrict__ dqkv, int64_t items, int N, int H, int d,
+                                                              float scale) {
+    extern __shared__ float lds[];
+    const int ld = d + 1, tile = AT_POS * ld;
+    float* sQ = lds;
+    float* sK = sQ + tile;
+    float* sV = sK + tile;                      // after dP: the second halves' partial of dK
+    float* sG = sV + tile;                      // dO; after dP: the second halves' partial of dQ
+    float* sP = sG + tile;                      // [64][65]
+    float* sdS = sP + AT_SBLK;                  // [64][65]; before dS: the second halves' partial of dV
+    float* sLse = sdS + AT_SBLK;                // [64]
+    float* sD = sLse + AT_POS;                  // [64]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31;
+    const int rb = (wave >> 1) * 32, cb = (wave & 1) * 32;      // this wave's block of S, dP and dS
+    const int64_t HD = (int64_t)H * d;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / H;
+        const int h = (int)(item - b * H);
+        const int64_t off = b * N * 3 * HD + (int64_t)h * d;
+        __syncthreads();                        // the item before has been read
+        load_tile(sQ, qkv + off, 3 * HD, N, d, ld, tid);
+        load_tile(sK, qkv + off + HD, 3 * HD, N, d, ld, tid);
+        load_tile(sV, qkv + off + 2 * HD, 3 * HD, N, d, ld, tid);
+        load_tile(sG, dout + b * N * HD + (int64_t)h * d, HD, N, d, ld, tid);
+        if (tid < AT_POS) sLse[tid] = tid < N ? lse[item * N + tid] : 0.f;
+        __syncthreads();
+        {                                       // D_i: row tid / 4, float4s tid % 4, + 4, ..; the products added one by one
+            const int i = tid >> 2, q = tid & 3;
+            float p = 0.f;
+            if (i < N) {
+                const float* o = out + (b * N + i) * HD + (int64_t)h * d;
+                const float* g = sG + i * ld;
+                for (int c = 4 * q; c < d; c += 16) {
+                    const float4 ov = *reinterpret_cast<const float4*>(o + c);
+                    p += g[c] * ov.x;
+                    p += g[c + 1] * ov.y;
+                    p += g[c + 2] * ov.z;
+                    p += g[c + 3] * ov.w;
+                }
+            }
+            const float s = row_sum4(p, lane);
+            if (q == 0) sD[i] = s;
+        }
+        {                                       // P = exp(S - lse), zeros from N on
+            const f32x16 acc = qk_block(sQ, sK, ld, d, rb, cb, lane);
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int i = rb + acc_row(v, lane), j = cb + l31;
+                sP[i * AT_LS + j] = (i < N && j < N) ? expf(scale * acc[v] - sLse[i]) : 0.f;
+            }
+        }
+        __syncthreads();
+        float* dq = dqkv + off;
+        float* dk = dq + HD;
+        float* dv = dk + HD;
+        // dV = P^T dO
+        pos_product(d, N, sdS, ld, wave, lane, [&](int j, int i) { return sP[i * AT_LS + j]; },
+                    [&](int i, int e) { return e < d ? sG[i * ld + e] : 0.f; },
+                    [&](int j, int e, float v) { if (j < N) dv[j * 3 * HD + e] = v; });
+        __syncthreads();                        // dV's partial has been read
+        {                                       // dP = dO V^T, dS = scale (P (dP - D))
+            f32x16 acc = {};
+            acc = mm32(acc, 0, d, lane, [&](int i, int e) { return sG[(rb + i) * ld + e]; },
+                       [&](int e, int j) { return sV[(cb + j) * ld + e]; });
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int i = rb + acc_row(v, lane), j = cb + l31;
+                sdS[i * AT_LS + j] = scale * (sP[i * AT_LS + j] * (acc[v] - sD[i]));
+            }
+        }
+        __syncthreads();                        // dS is whole; dO and V have been read
+        // dQ = dS K
+        pos_product(d, N, sG, ld, wave, lane, [&](int i, int j) { return sdS[i * AT_LS + j]; },
+                    [&](int j, int e) { return e < d ? sK[j * ld + e] : 0.f; },
+                    [&](int i, int e, float v) { if (i < N) dq[i * 3 * HD + e] = v; });
+        // dK = dS^T Q
+        pos_product(d, N, sV, ld, wave, lane, [&](int j, int i) { return sdS[i * AT_LS + j]; },
+                    [&](int i, int e) { return e < d ? sQ[i * ld + e] : 0.f; },
+                    [&](int j, int e, float v) { if (j < N) dk[j * 3 * HD + e] = v; });
+    }
+}
+
+// ---- the coordinate channels -------------------------------------------------------------------------------------------
+
+constexpr int EC_MAX_CHANNELS = 1024, EC_MAX_SIDE = 1 << 16, EC_MAX_BATCH = 1 << 20;
+
+__device__ __forceinline__ void split_index(int64_t t, int d, int64_t& q, int& r) {
+    if ((uint64_t)t <= 0xffffffffull) {
+        const uint32_t tt = (uint32_t)t, dd = (uint32_t)d;
+        q = (int64_t)(tt / dd);
+        r = (int)(tt % dd);
+    } else {
+        q = t / d;
+        r = (int)(t % d);
+    }
+}
+
+__device__ __forceinline__ float coord(int pos, int side) {
+    return side > 1 ? (float)(2 * pos - (side - 1)) / (float)(side - 1) : 0.f;
+}
+
+__global__ __launch_bounds__(AT_THREADS) void entity_coords_fwd_kernel(const float4* __restrict__ x, int h, int w, int c4,
+                                                                       int64_t total, float4* __restrict__ y) {
+    const int64_t step = (int64_t)gridDim.x * AT_THREADS;
+    for (int64_t t = (int64_t)blockIdx.x * AT_THREADS + threadIdx.x; t < total; t += step) {
+        int64_t p, q, b;
+        int c, j, i;
+        split_index(t, c4 + 1, p, c);
+        if (c < c4) {
+            y[t] = x[p * c4 + c];
+        } else {
+            split_index(p, w, q, j);
+            split_index(q, h, b, i);
+            y[t] = make_float4(coord(j, w), coord(i, h), 0.f, 0.f);
+        }
+    }
+}
+
+// g and g_in may be one buffer: a thread reads its own float4 before it writes it and touches no other
+__global__ __launch_bounds__(AT_THREADS) void entity_coords_bwd_kernel(const float4* g, const float4* __restrict__ dy,
+                                                                       const float4* __restrict__ mask, int c4,
+                                                                       int64_t total, float4* g_in) {
+    const int64_t step = (int64_t)gridDim.x * AT_THREADS;
+    for (int64_t t = (int64_t)blockIdx.x * AT_THREADS + threadIdx.x; t < total; t += step) {
+        int64_t p;
+        int c;
+        split_index(t, c4, p, c);
+        const float4 u = g[t], v = dy[p * (c4 + 1) + c];
+        float4 s = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
+        if (mask) {
+            const float4 m = mask[t];
+            s = make_float4(m.x > 0.f ? s.x : 0.f, m.y > 0.f ? s.y : 0.f, m.z > 0.f ? s.z : 0.f, m.w > 0.f ? s.w : 0.f);
+        }
+        g_in[t] = s;
+    }
+}
+
+int check_attn(int64_t batch, int32_t n_pos, int32_t n_heads, int32_t head_dim) {
+    if (batch < 1 || batch > ARL_ATTN_MAX_BATCH || n_pos < 1 || n_pos > ARL_ATTN_MAX_POS || head_dim < 4 ||
+        head_dim > ARL_ATTN_MAX_HEAD_DIM || (head_dim & 3) || n_heads < 1 ||
+        (int64_t)n_heads * head_dim > ARL_ATTN_MAX_WIDTH) {
+        arl::set_error("attention: need 1 <= batch <= 2^24, 1 <= n_pos <= 64, head_dim a multiple of 4 in 4 .. 64, "
+                       "n_heads >= 1 and n_heads * head_dim <= 256");
+        return ARL_E_RANGE;
+    }
+    return 0;
+}
+
+size_t attn_lds_bytes(int d, bool bwd) {
+    return ((size_t)(bwd ? 4 : 3) * AT_POS * (d + 1) + (bwd ? 2 : 1) * AT_SBLK + (bwd ? 2 : 1) * AT_POS) * sizeof(float);
+}
+
+int raise_lds(const void* kernel, size_t lds, const char* what) {
+    if (lds <= 65536) return 0;                 // per launch: the attribute belongs to the current device's copy
+    hipError_t err = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (err != hipSuccess) {
+        arl::set_error("hipFuncSetAttribute(%s): %s", what, hipGetErrorString(err));
+        return (int)err;
+    }
+    return 0;
+}
+
+int check_coords(int64_t batch, int32_t h, int32_t w, int32_t channels) {
+    if (batch < 1 || batch > EC_MAX_BATCH || h < 1 || h > EC_MAX_SIDE || w < 1 || w > EC_MAX_SIDE || channels < 4 ||
+        channels > EC_MAX_CHANNELS || (channels & 3)) {
+        arl::set_error("entity_coords: need 1 <= batch <= 2^20, 1 <= h, w <= 2^16 and channels a multiple of 4 in 4 .. 1024");
+        return ARL_E_RANGE;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int arl_attn_fwd(const float* qkv, float* out, float* lse_or_null, int64_t batch, int32_t n_pos, int32_t n_heads,
+                            int32_t head_dim, float scale, void* stream) {
+    ARL_REQUIRE(qkv && out, ARL_E_ARG, "null pointer");
+    ARL_REQUIRE(std::isfinite(scale), ARL_E_ARG, "scale must be finite");
+    int rc = check_attn(batch, n_pos, n_heads, head_dim);
+    if (rc) return rc;
+    const int64_t items = batch * n_heads, n_out = batch * n_pos * n_heads * head_dim;
+    const arl::Span in[1] = {{qkv, 3 * n_out * 4}};
+    const arl::Span outs[2] = {{out, n_out * 4}, {lse_or_null, items * n_pos * 4}};
+    if (!arl::check_disjoint("arl_attn_fwd", in, 1, outs, 2)) return ARL_E_ARG;
+    ARL_REQUIRE(arl::aligned16(qkv) && arl::aligned16(out) && arl::aligned4(lse_or_null), ARL_E_ALIGN,
+                "qkv and out 16-byte, lse 4-byte aligned");
+    const size_t lds = attn_lds_bytes(head_dim, false);
+    rc = raise_lds(reinterpret_cast<const void*>(attn_fwd_kernel), lds, "attn_fwd_kernel");
+    if (rc) return rc;
+    const unsigned grid = (unsigned)(items < ARL_ATTN_MAX_GRID ? items : ARL_ATTN_MAX_GRID);
+    hipLaunchKernelGGL(attn_fwd_kernel, dim3(grid), dim3(AT_THREADS), lds, (hipStream_t)stream, qkv, out, lse_or_null,
+                       items, (int)n_pos, (int)n_heads, (int)head_dim, scale);
+    return arl::check_launch("attn_fwd_kernel");
+}
+
+extern "C" int arl_attn_bwd(const float* qkv, const float* out, const float* lse, const float* dout, float* dqkv,
+                            int64_t batch, int32_t n_pos, int32_t n_heads, int32_t head_dim, float scale, void* stream) {
+    ARL_REQUIRE(qkv && out && lse && dout && dqkv, ARL_E_ARG, "null pointer");
+    ARL_REQUIRE(std::isfinite(scale), ARL_E_ARG, "scale must be finite");
+    int rc = check_attn(batch, n_pos, n_heads, head_dim);
+    if (rc) return rc;
+    const int64_t items = batch * n_heads, n_out = batch * n_pos * n_heads * head_dim;
+    const arl::Span in[4] = {{qkv, 3 * n_out * 4}, {out, n_out * 4}, {lse, items * n_pos * 4}, {dout, n_out * 4}};
+    const arl::Span outs[1] = {{dqkv, 3 * n_out * 4}};
+    if (!arl::check_disjoint("arl_attn_bwd", in, 4, outs, 1)) return ARL_E_ARG;
+    ARL_REQUIRE(arl::aligned16(qkv) && arl::aligned16(out) && arl::aligned16(dout) && arl::aligned16(dqkv) &&
+                    arl::aligned4(lse), ARL_E_ALIGN, "qkv, out, dout and dqkv 16-byte, lse 4-byte aligned");
+    const size_t lds = attn_lds_bytes(head_dim, true);
+    rc = raise_lds(reinterpret_cast<const void*>(attn_bwd_kernel), lds, "attn_bwd_kernel");
+    if (rc) return rc;
+    const unsigned grid = (unsigned)(items < ARL_ATTN_MAX_GRID ? items : ARL_ATTN_MAX_GRID);
+    hipLaunchKernelGGL(attn_bwd_kernel, dim3(grid), dim3(AT_THREADS), lds, (hipStream_t)stream, qkv, out, lse, dout, dqkv,
+                       items, (int)n_pos, (int)n_heads, (int)head_dim, scale);
+    return arl::check_launch("attn_bwd_kernel");
+}
+
+extern "C" int arl_entity_coords_fwd(const float* x, int64_t batch, int32_t h, int32_t w, int32_t channels, float* y,
+                                     void* stream) {
+    ARL_REQUIRE(x && y, ARL_E_ARG, "null pointer");
+    int rc = check_coords(batch, h, w, channels);
+    if (rc) return rc;
+    const int64_t pixels = batch * h * w;
+    ARL_REQUIRE(!arl::overlap(x, pixels * channels * 4, y, pixels * (channels + 4) * 4), ARL_E_ARG, "y must not overlap x");
+    ARL_REQUIRE(arl::aligned16(x) && arl::aligned16(y), ARL_E_ALIGN, "16-byte alignment");
+    const int c4 = channels >> 2;
+    const int64_t total = pixels * (c4 + 1);
+    hipLaunchKernelGGL(entity_coords_fwd_kernel, dim3(arl::stream_grid(total, AT_THREADS)), dim3(AT_THREADS), 0,
+                       (hipStream_t)stream, (const float4*)x, (int)h, (int)w, c4, total, (float4*)y);
+    return arl::check_launch("entity_coords_fwd_kernel");
+}
+
+extern "C" int arl_entity_coords_bwd(const float* g, const float* d_y, const float* mask_or_null, int64_t batch, int32_t h,
+                                     int32_t w, int32_t channels, float* g_in, void* stream) {
+    ARL_REQUIRE(g && d_y && g_in, ARL_E_ARG, "null pointer");
+    int rc = check_coords(batch, h, w, channels);
+    if (rc) return rc;
+    const int64_t pixels = batch * h * w, n = pixels * channels * 4;
+    ARL_REQUIRE(!arl::overlap(g_in, n, d_y, pixels * (channels + 4) * 4) &&
+                    !(mask_or_null && arl::overlap(g_in, n, mask_or_null, n)) &&
+                    (g_in == g || !arl::overlap(g_in, n, g, n)),
+                ARL_E_ARG, "g_in must not overlap d_y or mask, and g only as the same buffer");
+    ARL_REQUIRE(arl::aligned16(g) && arl::aligned16(d_y) && arl::aligned16(mask_or_null) && arl::aligned16(g_in),
+                ARL_E_ALIGN, "16-byte alignment");
+    const int c4 = channels >> 2;
+    const int64_t total = pixels * c4;
+    hipLaunchKernelGGL(entity_coords_bwd_kernel, dim3(arl::stream_grid(total, AT_THREADS)), dim3(AT_THREADS), 0,
+                       (hipStream_t)stream, (const float4*)g, (const float4*)d_y, (const float4*)mask_or_null, c4, total,
+                       (float4*)g_in);
+    return arl::check_launch("entity_coords_bwd_kernel");
+}

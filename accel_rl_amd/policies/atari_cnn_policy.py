@@ -122,10 +122,10 @@ class AtariCnnPolicy(object):
             # (the u8 path takes any plane count)
             ci = c if (self._u8 and not self._conv_geom) else (c + 3) // 4 * 4
             self._conv_geom.append((nf, ci, sz, st, tuple(pad), h, w))
-            c = nf
+            c = self._next_conv_input_channels(len(self._conv_geom) - 1, nf)
             h, w = self._next_conv_input_hw(len(self._conv_geom) - 1, h, w)
-        self._conv_out = (c, h, w)
-        fan = c * h * w
+        self._conv_out = (self.conv_filters[-1], h, w)
+        fan = self.conv_filters[-1] * h * w
         hid_ref, hid_names, fan = self._hidden_reference_init(fan)
         self._n_hidden_tensors = len(hid_ref)
         head_ref, head_names = self._head_reference_init(fan, n_act)
@@ -206,6 +206,11 @@ class AtariCnnPolicy(object):
         """Height and width of what the conv layer after layer i reads, given layer i's output: the output itself, for
         a plain stack (a policy with a pooling layer behind some of its conv layers says otherwise)."""
         return ho, wo
+
+    def _next_conv_input_channels(self, i, nf):
+        """Channels of what the conv layer after layer i reads, given layer i's nf filters: its output, for a plain stack
+        (a policy that puts channels between two of its conv layers, or reshapes there, says otherwise)."""
+        return nf
 
     def _bucket_order(self, n):
         """The tensors' order in the flat bucket's memory: the order of `_shapes`, for every policy whose conv layers own
@@ -354,14 +359,15 @@ class AtariCnnPolicy(object):
                      (self._u8 and sz in (8, 16) and sz % (8 // (sz >> 2)) == 0 if i == 0 else ci % 32 == 0) and
                      (tuple(pad) == (0, 0) or sz * sz <= 32))
 
-    def _convs(self, x, w=None, tag=""):
-        """The conv stack of _trunk: activations [B, Ho, Wo, K] of every layer, post bias + rectifier."""
+    def _convs(self, x, w=None, tag="", upto=None):
+        """The conv stack of _trunk: activations [B, Ho, Wo, K] of every layer, post bias + rectifier (upto: of the
+        first `upto` layers only, for a policy whose later conv layers are no part of the chain)."""
         b = x.shape[0]
         w = self._w if w is None else w
         conv_g, _ = self._layer_geoms(b)
         acts, a = [], x
         with_bits = self._relu_bits_layers() if self._bits_pass else ()
-        for i, (nf, ci, sz, st, pad, ho, wo) in enumerate(self._conv_geom):
+        for i, (nf, ci, sz, st, pad, ho, wo) in enumerate(self._conv_geom[:upto]):
             z = self._buffer(("act" + tag, i, b), (b, ho, wo, nf))
             bits = None
             if i in with_bits:
@@ -761,10 +767,10 @@ class AtariCnnPolicy(object):
         conv_g, _ = self._layer_geoms(b)
         return [(self._w[2 * i], wt, conv_g[i]) for i, wt in sorted(self._wt.items())]
 
-    def _backward_convs(self, x, acts, d_act, masked=False, corun=None):
+    def _backward_convs(self, x, acts, d_act, masked=False, corun=None, upto=None):
         """Conv layers, last to first; d_act = NHWC gradient of the last conv output (masked: already
         multiplied by its rectifier mask); corun: an optimiser job (_lib.corun_job) for the first data-gradient launch
-        that can carry it."""
+        that can carry it; upto: the chain is the first `upto` layers (_convs)."""
         b = x.shape[0]
         conv_g, _ = self._layer_geoms(b)
         if not getattr(self, "_wt_fresh", False):          # (else: written by the head's launch of this pass)
@@ -774,7 +780,7 @@ class AtariCnnPolicy(object):
         # the data gradients first: the layers' weight gradients, independent of one another, are only planned and then
         # share one launch (arl_conv2d_bwd_weight_group); ARL_WGRAD_GROUP=0: each right behind its data gradient (A/B switch)
         group = os.environ.get("ARL_WGRAD_GROUP", "1") != "0"
-        for i in range(self._n_conv - 1, -1, -1):
+        for i in range((self._n_conv if upto is None else upto) - 1, -1, -1):
             nf, ci, sz, st, pad, ho, wo = self._conv_geom[i]
             d_in = self._buffer(("dx_conv", i, b), tuple(acts[i - 1].shape)) if i > 0 else None
             d_act, masked = self._through_activation(i, d_act, masked, acts[i])
@@ -790,11 +796,13 @@ class AtariCnnPolicy(object):
         self._folds.run()
         self._bits.clear()                      # (the pass that wrote them ends here)
 
-    def _layer_grads(self, d, masked, y, rows, channels, k, geom, inp, d_in, corun=None, wt=None, defer=False):
+    def _layer_grads(self, d, masked, y, rows, channels, k, geom, inp, d_in, corun=None, wt=None, defer=False,
+                     inp_rectified=True):
         """One layer's backward: bias and weight gradient (deferred folds) and, with d_in, the data gradient
         already multiplied by the rectifier mask of `inp` (the layer below's output), so that the layer below
         gets its pre-activation gradient without another pass.  Not `masked`: d still needs this layer's own
-        mask, applied in place by the streaming kernel that also sums the bias gradient."""
+        mask, applied in place by the streaming kernel that also sums the bias gradient.  inp_rectified False: `inp` is
+        no rectifier's output, d_in comes unmasked."""
         folds, g = self._folds, self.grads
         if not masked:
             folds.relu_bwd_bias_grad(d, y, rows, channels, g[k + 1], self._fold_ws(("db", k)))
@@ -803,8 +811,8 @@ class AtariCnnPolicy(object):
             done = folds.conv2d_u8_bwd_weight(d, inp.obs, inp.idx, self._scale, self._g[k], geom,
                                               self._fold_ws(("dw", k)), dbias=dbias, defer=defer)
         elif d_in is not None:      # data + weight gradient share one launch where that pays (dense layers)
-            done = folds.conv2d_bwd_pair(d, self._w[k], inp, d_in, inp, self._g[k], geom, self._fold_ws(("dw", k)),
-                                         dbias=dbias, corun=corun, wt=wt, defer=defer,
+            done = folds.conv2d_bwd_pair(d, self._w[k], inp if inp_rectified else None, d_in, inp, self._g[k], geom,
+                                         self._fold_ws(("dw", k)), dbias=dbias, corun=corun, wt=wt, defer=defer,
                                          mask_bits=self._bits.get(inp.data_ptr()))     # (this pass's forward wrote them)
         else:
             done = folds.conv2d_bwd_weight(d, inp, self._g[k], geom, self._fold_ws(("dw", k)), dbias=dbias, defer=defer)

@@ -1830,6 +1830,59 @@ int arl_gather_scale_obs_nhwc_any(const uint8_t* obs, const int32_t* idx_or_null
                                   int32_t plane_bytes, float scale, float* out, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Multi-head self-attention over the positions of a feature map (the relational policy; csrc/attention.hip)
+ * ------------------------------------------------------------------------- */
+
+/* Tensors, all f32 and contiguous: qkv [batch][n_pos][3][n_heads][head_dim] (what a 1 x 1 convolution of
+ * 3 n_heads head_dim channels writes: channel (which n_heads + h) head_dim + e, which = 0 / 1 / 2 for Q / K / V),
+ * out and dout [batch][n_pos][n_heads head_dim], lse [batch][n_heads][n_pos], dqkv as qkv.
+ * Per sample b and head h, with Q, K, V the [n_pos][head_dim] slices of qkv and i, j < n_pos:
+ *   forward   s_ij = scale * (sum_e Q_ie K_je)           the sum on the fp32 MFMA chain (below), then one multiplication
+ *             m_i = max_j s_ij;  x_ij = expf(s_ij - m_i);  l_i = ((p0 + p1) + p2) + p3, p_q = the sum of x_ij over
+ *             j = q, q + 4, .. in ascending order from 0.f
+ *             out_ie = (sum_j x_ij V_je) * (1.f / l_i);   lse_i = m_i + logf(l_i)   (lse_or_null NULL: not written)
+ *   backward  s_ij as above (the same instructions on the same operands: the same bits), P_ij = expf(s_ij - lse_i)
+ *             D_i = ((p0 + p1) + p2) + p3, p_q = dout_ie * out_ie added one by one from 0.f over e = 4 c .. 4 c + 3,
+ *             c = q, q + 4, ..
+ *             dV_je = sum_i P_ij dout_ie;  dP_ij = sum_e dout_ie V_je;  dS_ij = scale * (P_ij * (dP_ij - D_i))
+ *             dQ_ie = sum_j dS_ij K_je;    dK_je = sum_i dS_ij Q_ie     -> dqkv, every element written once
+ * Every sum over e or over positions is a chain of v_mfma_f32_32x32x2_f32 on 32 x 32 output blocks, operands as they
+ * are, fp32 accumulation from 0, the reduction index ascending in steps of two; a sum over positions stops at n_pos.
+ * Where head_dim <= 32 a sum over positions is taken as (positions 0 .. 31) + (positions 32 .. 63), two chains and one
+ * addition.  P exists in LDS only.  Work split: min(batch n_heads, ARL_ATTN_MAX_GRID) workgroups of four waves,
+ * workgroup g takes the (sample, head) pairs g, g + grid, ..; one writer per output element, no atomics, nothing
+ * depends on the grid: two launches give the same bits.  LDS per workgroup: (3 * 64 * (head_dim + 1) + 64 * 65 + 64) * 4
+ * bytes forward, (4 * 64 * (head_dim + 1) + 2 * 64 * 65 + 128) * 4 backward (100 352 at head_dim 64).
+ * Refused before any HIP call, nothing written: a NULL pointer other than lse_or_null, a scale that is not finite, an
+ * output that overlaps an input or another output (ARL_E_ARG); batch outside 1 .. ARL_ATTN_MAX_BATCH, n_pos outside
+ * 1 .. ARL_ATTN_MAX_POS, head_dim outside 4 .. ARL_ATTN_MAX_HEAD_DIM or not a multiple of 4, n_heads < 1 or
+ * n_heads head_dim > ARL_ATTN_MAX_WIDTH (ARL_E_RANGE); qkv, out, dout or dqkv not 16-byte, lse not 4-byte aligned
+ * (ARL_E_ALIGN).                                                                                                      */
+#define ARL_ATTN_MAX_POS      64
+#define ARL_ATTN_MAX_HEAD_DIM 64
+#define ARL_ATTN_MAX_WIDTH    256
+#define ARL_ATTN_MAX_BATCH    (1 << 24)
+#define ARL_ATTN_MAX_GRID     1024
+int arl_attn_fwd(const float* qkv, float* out, float* lse_or_null, int64_t batch, int32_t n_pos, int32_t n_heads,
+                 int32_t head_dim, float scale, void* stream);
+int arl_attn_bwd(const float* qkv, const float* out, const float* lse, const float* dout, float* dqkv, int64_t batch,
+                 int32_t n_pos, int32_t n_heads, int32_t head_dim, float scale, void* stream);
+
+/* The coordinate channels of the relational policy, on NHWC activations; one float4 per thread, no LDS, 64-bit indexing.
+ * arl_entity_coords_fwd: x f32[batch][h][w][channels] -> y f32[batch][h][w][channels + 4]: y[b][i][j][c] = x[b][i][j][c]
+ *   for c < channels; channel `channels` = (float)(2 j - (w - 1)) / (float)(w - 1) (integer numerator and denominator
+ *   converted, one fp32 division), +0 when w = 1; channel channels + 1 the same in i and h; channels + 2 and + 3 are +0.
+ * arl_entity_coords_bwd: g, mask_or_null, g_in f32[batch][h][w][channels], d_y f32[batch][h][w][channels + 4]:
+ *   g_in = g + d_y[..][c < channels] (one fp32 addition); with mask, +0 wherever mask <= 0.  g_in may be g itself (a
+ *   thread reads its own elements before it writes them).
+ * Refused before any HIP call, nothing written: a NULL pointer other than mask_or_null, y overlapping x, g_in overlapping
+ *   d_y or mask, or g other than as the same buffer (ARL_E_ARG); batch outside 1 .. 2^20, h or w outside 1 .. 2^16,
+ *   channels outside 4 .. 1024 or not a multiple of 4 (ARL_E_RANGE); a pointer not 16-byte aligned (ARL_E_ALIGN).     */
+int arl_entity_coords_fwd(const float* x, int64_t batch, int32_t h, int32_t w, int32_t channels, float* y, void* stream);
+int arl_entity_coords_bwd(const float* g, const float* d_y, const float* mask_or_null, int64_t batch, int32_t h, int32_t w,
+                          int32_t channels, float* g_in, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * LSTM cell of the recurrent policies
  * ------------------------------------------------------------------------- */
 
