@@ -259,6 +259,8 @@ _SIGNATURES = {
     "arl_add_relu": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "arl_attn_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _vp]),
     "arl_attn_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _vp]),
+    "arl_attn_tiled_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _vp]),
+    "arl_attn_tiled_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _vp]),
     "arl_entity_coords_fwd": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "arl_entity_coords_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "arl_gather_scale_obs_nhwc_any": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp]),
@@ -2049,6 +2051,36 @@ def attn_bwd(qkv, out, lse, dout, dqkv, scale=None, stream=None):
     scale = d ** -0.5 if scale is None else scale
     _check(load().arl_attn_bwd(ptr(qkv), ptr(out), ptr(lse), ptr(dout), ptr(dqkv), b, n, h, d, float(scale),
                                stream_ptr(stream)), "arl_attn_bwd")
+
+
+ATTN_TILED_MAX_POS = 256                                # ARL_ATTN_TILED_MAX_POS
+
+
+def attn_tiled_shape_ok(n_pos, n_heads, head_dim):
+    """What arl_attn_tiled_fwd / arl_attn_tiled_bwd take (accel_rl_hip.h); needs no device."""
+    return 1 <= n_pos <= ATTN_TILED_MAX_POS and attn_shape_ok(1, n_heads, head_dim)
+
+
+def attn_tiled_fwd(qkv, out, lse=None, scale=None, stream=None):
+    """attn_fwd for up to ATTN_TILED_MAX_POS positions: key tiles of 64 streamed around an online soft-max."""
+    b, n, h, d = _attn_dims(qkv, out, lse)
+    scale = d ** -0.5 if scale is None else scale
+    _check(load().arl_attn_tiled_fwd(ptr(qkv), ptr(out), ptr(lse), b, n, h, d, float(scale), stream_ptr(stream)),
+           "arl_attn_tiled_fwd")
+
+
+def attn_tiled_bwd(qkv, out, lse, dout, dqkv, scale=None, stream=None):
+    """attn_bwd for up to ATTN_TILED_MAX_POS positions, given attn_tiled_fwd's out and lse."""
+    b, n, h, d = _attn_dims(qkv, out, lse)
+    if lse is None:
+        raise ValueError("attn_tiled_bwd needs the forward's lse")
+    _want(dout, torch.float32, "dout")
+    _want(dqkv, torch.float32, "dqkv")
+    if dout.numel() != out.numel() or dqkv.numel() != qkv.numel():
+        raise ValueError("dout / dqkv must have the sizes of out / qkv")
+    scale = d ** -0.5 if scale is None else scale
+    _check(load().arl_attn_tiled_bwd(ptr(qkv), ptr(out), ptr(lse), ptr(dout), ptr(dqkv), b, n, h, d, float(scale),
+                                     stream_ptr(stream)), "arl_attn_tiled_bwd")
 
 
 def _coords_dims(x, y):

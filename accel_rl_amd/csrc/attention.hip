@@ -5,6 +5,7 @@
 //   arl_attn_fwd            S = scale Q K^T, P = softmax_j(S), O = P V per sample and head [, lse = logsumexp_j S]
 //   arl_attn_bwd            S again (the forward's instructions), P = exp(S - lse), D_i = sum_e dO_ie O_ie,
 //                           dV = P^T dO, dP = dO V^T, dS = scale P o (dP - D), dQ = dS K, dK = dS^T Q
+//   arl_attn_tiled_fwd/_bwd the same for 65 .. 256 positions: 64-row tiles around an online soft-max (further down)
 //   arl_entity_coords_fwd   y = [x, (2 j - (w - 1)) / (w - 1), (2 i - (h - 1)) / (h - 1), 0, 0] along the channels
 //   arl_entity_coords_bwd   g_in = g + d_y[..., :C] [, +0 where mask <= 0]
 //
@@ -252,6 +253,251 @@ __global__ __launch_bounds__(AT_THREADS, 2) void attn_bwd_kernel(const float* __
     }
 }
 
+// ---- more than 64 positions: 64-row tiles streamed around an online soft-max ---------------------------------------------
+//
+// The same tiles, products and thread layouts as above, with N up to ARL_ATTN_TILED_MAX_POS = 4 tiles of 64 rows.
+// Forward: one item is (sample, head, query tile).  Q is loaded once; the key tiles pass through sK / sV in ascending
+// order, each one's 64 x 64 score block through sS; per row a running maximum m and sum l live in LDS, and the item's
+// unnormalised O stays in the MFMA accumulators, scaled by alpha = exp(m_old - m_new) before every tile's x V is added
+// by the same chain.  Where d <= 32 the waves 2 and 3 take the second 32 keys of EVERY tile and keep their partial to
+// the end: one addition, first halves + second halves, per item.  Backward: one item is (sample, head); lse, D and a
+// [N_pad][d + 1] tile of dQ are resident in LDS; key tiles outside, query tiles inside, both ascending; dK_j and dV_j
+// stay in the accumulators over the inner loop (d <= 32: halves of the query tile, kept apart to the end as above) and
+// each tile pair's dS K_j goes into the dQ tile, stored at j = 0 and added after.  dS is written over P in place: the
+// thread that owns a dP accumulator element owns that element of P.
+
+constexpr int AT_TILES = ARL_ATTN_TILED_MAX_POS / AT_POS;
+
+__global__ __launch_bounds__(AT_THREADS, 2) void attn_tiled_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out,
+                                                                    float* __restrict__ lse, int64_t items, int N, int H,
+                                                                    int d, float scale) {
+    extern __shared__ float lds[];
+    const int ld = d + 1, tile = AT_POS * ld;
+    float* sQ = lds;                            // [64][d + 1]; after the last tile: the second halves' partial of O
+    float* sK = sQ + tile;
+    float* sV = sK + tile;
+    float* sS = sV + tile;                      // [64][65]  S, then exp(S - m)
+    float* sM = sS + AT_SBLK;                   // [64]      the running maximum
+    float* sL = sM + AT_POS;                    // [64]      the running sum
+    float* sA = sL + AT_POS;                    // [64]      this tile's alpha
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31;
+    const int tiles = (N + AT_POS - 1) / AT_POS;
+    const bool halves = d <= 32;
+    // O: block (wave / 2, wave % 2) of [64][64], or row block wave % 2 over the keys [32 (wave / 2), + 32) of each tile
+    const int orb = (halves ? wave & 1 : wave >> 1) * 32, ocb = halves ? 0 : (wave & 1) * 32, okb = halves ? (wave >> 1) * 32 : 0;
+    const int64_t HD = (int64_t)H * d;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t bh = item / tiles, b = bh / H;
+        const int h = (int)(bh - b * H), q0 = (int)(item - bh * tiles) * AT_POS;
+        const float* base = qkv + b * N * 3 * HD + (int64_t)h * d;
+        __syncthreads();                        // the item before has been read
+        load_tile(sQ, base + (int64_t)q0 * 3 * HD, 3 * HD, N - q0, d, ld, tid);
+        if (tid < AT_POS) {
+            sM[tid] = -INFINITY;
+            sL[tid] = 0.f;
+        }
+        f32x16 acc = {};
+        for (int k0 = 0; k0 < N; k0 += AT_POS) {
+            const int kn = N - k0 < AT_POS ? N - k0 : AT_POS;
+            __syncthreads();                    // the tile before has been read; Q, m and l are whole
+            load_tile(sK, base + (int64_t)k0 * 3 * HD + HD, 3 * HD, kn, d, ld, tid);
+            load_tile(sV, base + (int64_t)k0 * 3 * HD + 2 * HD, 3 * HD, kn, d, ld, tid);
+            __syncthreads();
+            {
+                const int rb = (wave >> 1) * 32, cb = (wave & 1) * 32;
+                const f32x16 s = qk_block(sQ, sK, ld, d, rb, cb, lane);
+#pragma unroll
+                for (int v = 0; v < 16; ++v) sS[(rb + acc_row(v, lane)) * AT_LS + cb + l31] = scale * s[v];
+            }
+            __syncthreads();
+            {                                   // row tid / 4, columns tid % 4, + 4, ..; rows from N up hold zeros: finite
+                const int i = tid >> 2, q = tid & 3;
+                float* s = sS + i * AT_LS;
+                const float m_old = sM[i], l_old = sL[i];
+                float m = m_old, p = 0.f;
+                for (int j = q; j < kn; j += 4) m = fmaxf(m, s[j]);
+                m = fmaxf(m, __shfl_xor(m, 1, 64));
+                m = fmaxf(m, __shfl_xor(m, 2, 64));
+                for (int j = q; j < kn; j += 4) {
+                    const float e = expf(s[j] - m);
+                    s[j] = e;
+                    p += e;
+                }
+                for (int j = kn + q; j < AT_POS; j += 4) s[j] = 0.f;
+                const float lt = row_sum4(p, lane);
+                if (q == 0) {
+                    const float alpha = expf(m_old - m);        // the first tile: exp(-inf) = 0, and l_old = 0
+                    sA[i] = alpha;
+                    sM[i] = m;
+                    sL[i] = alpha * l_old + lt;
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int v = 0; v < 16; ++v) acc[v] = acc[v] * sA[orb + acc_row(v, lane)];
+            const int ke = halves ? (kn < okb + 32 ? kn : okb + 32) : kn;
+            acc = mm32(acc, okb, ke, lane, [&](int i, int k) { return sS[(orb + i) * AT_LS + k]; },
+                       [&](int k, int e) { return ocb + e < d ? sV[k * ld + ocb + e] : 0.f; });
+        }
+        if (lse && tid < AT_POS && q0 + tid < N) lse[bh * N + q0 + tid] = sM[tid] + logf(sL[tid]);
+        float* o = out + (b * N + q0) * HD + (int64_t)h * d;
+        if (halves) {
+            if (wave >= 2 && l31 < d) {         // (every wave is past its last read of Q: the barrier after S)
+#pragma unroll
+                for (int v = 0; v < 16; ++v) sQ[(orb + acc_row(v, lane)) * ld + l31] = acc[v];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int v = 0; v < 16; ++v) acc[v] = acc[v] + sQ[(orb + acc_row(v, lane)) * ld + (l31 < d ? l31 : 0)];
+        }
+        if (ocb + l31 < d && !(halves && wave >= 2)) {
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int i = orb + acc_row(v, lane);
+                if (q0 + i < N) o[i * HD + ocb + l31] = acc[v] * (1.f / sL[i]);
+            }
+        }
+    }
+}
+
+// this wave's partial of a [64][d] product whose rows and reduction run over positions: acc += sum_k a(row, k) b(k, col)
+// over this wave's share of k < kn (d > 32: block (wave / 2, wave % 2), all of k; d <= 32: row block wave % 2, the k
+// of [32 (wave / 2), + 32)); a(row, k) with row in 0 .. 63, b(k, col) answers 0 for col >= d
+template <class FA, class FB>
+__device__ __forceinline__ f32x16 pos_accumulate(f32x16 acc, int d, int kn, int wave, int lane, FA a, FB b) {
+    if (d > 32) {
+        const int rb = (wave >> 1) * 32, cb = (wave & 1) * 32;
+        return mm32(acc, 0, kn, lane, [&](int i, int k) { return a(rb + i, k); }, [&](int k, int j) { return b(k, cb + j); });
+    }
+    const int rb = (wave & 1) * 32, kb = (wave >> 1) * 32, ke = kn < kb + 32 ? kn : kb + 32;
+    return mm32(acc, kb, ke, lane, [&](int i, int k) { return a(rb + i, k); }, [&](int k, int j) { return b(k, j); });
+}
+
+// pos_accumulate's result to global rows (row r at dst + r * row_stride, rows below n only).  d <= 32: waves 2 and 3 leave
+// theirs in `part` ([64][ld], free), waves 0 and 1 add it to theirs: first halves + second halves.  All four waves call.
+__device__ __forceinline__ void pos_store(f32x16 acc, int d, int n, float* part, int ld, float* dst, int64_t row_stride,
+                                          int wave, int lane) {
+    const int l31 = lane & 31;
+    int rb = (wave >> 1) * 32, cb = (wave & 1) * 32;
+    if (d <= 32) {
+        rb = (wave & 1) * 32, cb = 0;
+        if (wave >= 2 && l31 < d) {
+#pragma unroll
+            for (int v = 0; v < 16; ++v) part[(rb + acc_row(v, lane)) * ld + l31] = acc[v];
+        }
+        __syncthreads();
+        if (wave >= 2) return;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) acc[v] = acc[v] + part[(rb + acc_row(v, lane)) * ld + (l31 < d ? l31 : 0)];
+    }
+    if (cb + l31 < d) {
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            const int r = rb + acc_row(v, lane);
+            if (r < n) dst[r * row_stride + cb + l31] = acc[v];
+        }
+    }
+}
+
+__global__ __launch_bounds__(AT_THREADS) void attn_tiled_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ out,
+                                                                 const float* __restrict__ lse, const float* __restrict__ dout,
+                                                                 float* __restrict__ dqkv, int64_t items, int N, int H, int d,
+                                                                 float scale) {
+    extern __shared__ float lds[];
+    const int ld = d + 1, tile = AT_POS * ld, npad = (N + AT_POS - 1) / AT_POS * AT_POS;
+    float* sdQ = lds;                           // [N_pad][d + 1]
+    float* sQ = sdQ + npad * ld;                // after the inner loop: the second halves' partial of dK
+    float* sK = sQ + tile;
+    float* sV = sK + tile;
+    float* sG = sV + tile;                      // dO; after dP: the second halves' partial of dS K; at last that of dV
+    float* sP = sG + tile;                      // [64][65]  P, then dS
+    float* sLse = sP + AT_SBLK;                 // [N_pad]
+    float* sD = sLse + npad;                    // [N_pad]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31;
+    const int rb = (wave >> 1) * 32, cb = (wave & 1) * 32;      // this wave's block of S, dP and dS
+    const int64_t HD = (int64_t)H * d;
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t b = item / H;
+        const int h = (int)(item - b * H);
+        const int64_t off = b * N * 3 * HD + (int64_t)h * d, ooff = b * N * HD + (int64_t)h * d;
+        __syncthreads();                        // the item before has been read
+        for (int i = tid; i < npad; i += AT_THREADS) sLse[i] = i < N ? lse[item * N + i] : 0.f;
+        for (int i0 = 0; i0 < N; i0 += AT_POS) {        // D_i: row tid / 4, float4s tid % 4, + 4, ..; added one by one
+            const int i = i0 + (tid >> 2), q = tid & 3;
+            float p = 0.f;
+            if (i < N) {
+                const float* o = out + ooff + i * HD;
+                const float* g = dout + ooff + i * HD;
+                for (int c = 4 * q; c < d; c += 16) {
+                    const float4 ov = *reinterpret_cast<const float4*>(o + c), gv = *reinterpret_cast<const float4*>(g + c);
+                    p += gv.x * ov.x;
+                    p += gv.y * ov.y;
+                    p += gv.z * ov.z;
+                    p += gv.w * ov.w;
+                }
+            }
+            const float s = row_sum4(p, lane);
+            if (q == 0) sD[i] = s;
+        }
+        float* dq = dqkv + off;
+        for (int k0 = 0; k0 < N; k0 += AT_POS) {
+            const int kn = N - k0 < AT_POS ? N - k0 : AT_POS;
+            __syncthreads();                    // the key tile before has been read
+            load_tile(sK, qkv + off + (int64_t)k0 * 3 * HD + HD, 3 * HD, kn, d, ld, tid);
+            load_tile(sV, qkv + off + (int64_t)k0 * 3 * HD + 2 * HD, 3 * HD, kn, d, ld, tid);
+            f32x16 dk = {}, dv = {};
+            for (int i0 = 0; i0 < N; i0 += AT_POS) {
+                const int in = N - i0 < AT_POS ? N - i0 : AT_POS;
+                __syncthreads();                // the query tile before has been read
+                load_tile(sQ, qkv + off + (int64_t)i0 * 3 * HD, 3 * HD, in, d, ld, tid);
+                load_tile(sG, dout + ooff + (int64_t)i0 * HD, HD, in, d, ld, tid);
+                __syncthreads();
+                {                               // P = exp(S - lse), zeros from N on in both indices
+                    const f32x16 acc = qk_block(sQ, sK, ld, d, rb, cb, lane);
+#pragma unroll
+                    for (int v = 0; v < 16; ++v) {
+                        const int i = rb + acc_row(v, lane), j = cb + l31;
+                        sP[i * AT_LS + j] = (i < in && j < kn) ? expf(scale * acc[v] - sLse[i0 + i]) : 0.f;
+                    }
+                }
+                __syncthreads();
+                // dV_j += P^T dO_i
+                dv = pos_accumulate(dv, d, in, wave, lane, [&](int j, int i) { return sP[i * AT_LS + j]; },
+                                    [&](int i, int e) { return e < d ? sG[i * ld + e] : 0.f; });
+                f32x16 dp = {};                 // dP = dO_i V_j^T
+                dp = mm32(dp, 0, d, lane, [&](int i, int e) { return sG[(rb + i) * ld + e]; },
+                          [&](int e, int j) { return sV[(cb + j) * ld + e]; });
+                __syncthreads();                // P and dO have been read
+#pragma unroll
+                for (int v = 0; v < 16; ++v) {  // dS = scale (P (dP - D)) over P
+                    const int i = rb + acc_row(v, lane), j = cb + l31;
+                    sP[i * AT_LS + j] = scale * (sP[i * AT_LS + j] * (dp[v] - sD[i0 + i]));
+                }
+                __syncthreads();
+                // dK_j += dS^T Q_i
+                dk = pos_accumulate(dk, d, in, wave, lane, [&](int j, int i) { return sP[i * AT_LS + j]; },
+                                    [&](int i, int e) { return e < d ? sQ[i * ld + e] : 0.f; });
+                // dQ_i (+)= dS K_j
+                float* t = sdQ + i0 * ld;
+                const bool first = k0 == 0;
+                pos_product(d, kn, sG, ld, wave, lane, [&](int i, int j) { return sP[i * AT_LS + j]; },
+                            [&](int j, int e) { return e < d ? sK[j * ld + e] : 0.f; },
+                            [&](int i, int e, float v) { t[i * ld + e] = first ? v : t[i * ld + e] + v; });
+            }
+            __syncthreads();                    // the last query tile has been read
+            pos_store(dk, d, kn, sQ, ld, dq + (int64_t)k0 * 3 * HD + HD, 3 * HD, wave, lane);
+            pos_store(dv, d, kn, sG, ld, dq + (int64_t)k0 * 3 * HD + 2 * HD, 3 * HD, wave, lane);
+        }
+        __syncthreads();                        // dQ is whole
+        const int d4 = d >> 2;
+        for (int i = tid; i < N * d4; i += AT_THREADS) {
+            const int r = i / d4, c = (i - r * d4) * 4;
+            const float* s = sdQ + r * ld + c;
+            *reinterpret_cast<float4*>(dq + (int64_t)r * 3 * HD + c) = make_float4(s[0], s[1], s[2], s[3]);
+        }
+    }
+}
+
 // ---- the coordinate channels -------------------------------------------------------------------------------------------
 
 constexpr int EC_MAX_CHANNELS = 1024, EC_MAX_SIDE = 1 << 16, EC_MAX_BATCH = 1 << 20;
@@ -307,12 +553,12 @@ __global__ __launch_bounds__(AT_THREADS) void entity_coords_bwd_kernel(const flo
     }
 }
 
-int check_attn(int64_t batch, int32_t n_pos, int32_t n_heads, int32_t head_dim) {
-    if (batch < 1 || batch > ARL_ATTN_MAX_BATCH || n_pos < 1 || n_pos > ARL_ATTN_MAX_POS || head_dim < 4 ||
+int check_attn(int64_t batch, int32_t n_pos, int32_t n_heads, int32_t head_dim, int32_t max_pos = ARL_ATTN_MAX_POS) {
+    if (batch < 1 || batch > ARL_ATTN_MAX_BATCH || n_pos < 1 || n_pos > max_pos || head_dim < 4 ||
         head_dim > ARL_ATTN_MAX_HEAD_DIM || (head_dim & 3) || n_heads < 1 ||
         (int64_t)n_heads * head_dim > ARL_ATTN_MAX_WIDTH) {
-        arl::set_error("attention: need 1 <= batch <= 2^24, 1 <= n_pos <= 64, head_dim a multiple of 4 in 4 .. 64, "
-                       "n_heads >= 1 and n_heads * head_dim <= 256");
+        arl::set_error("attention: need 1 <= batch <= 2^24, 1 <= n_pos <= %d, head_dim a multiple of 4 in 4 .. 64, "
+                       "n_heads >= 1 and n_heads * head_dim <= 256", max_pos);
         return ARL_E_RANGE;
     }
     return 0;
@@ -320,6 +566,12 @@ int check_attn(int64_t batch, int32_t n_pos, int32_t n_heads, int32_t head_dim) 
 
 size_t attn_lds_bytes(int d, bool bwd) {
     return ((size_t)(bwd ? 4 : 3) * AT_POS * (d + 1) + (bwd ? 2 : 1) * AT_SBLK + (bwd ? 2 : 1) * AT_POS) * sizeof(float);
+}
+
+size_t attn_tiled_lds_bytes(int n_pos, int d, bool bwd) {
+    const size_t npad = (size_t)(n_pos + AT_POS - 1) / AT_POS * AT_POS;
+    return bwd ? ((npad + 4 * AT_POS) * (d + 1) + AT_SBLK + 2 * npad) * sizeof(float)
+               : ((size_t)3 * AT_POS * (d + 1) + AT_SBLK + 3 * AT_POS) * sizeof(float);
 }
 
 int raise_lds(const void* kernel, size_t lds, const char* what) {
@@ -383,6 +635,50 @@ extern "C" int arl_attn_bwd(const float* qkv, const float* out, const float* lse
     hipLaunchKernelGGL(attn_bwd_kernel, dim3(grid), dim3(AT_THREADS), lds, (hipStream_t)stream, qkv, out, lse, dout, dqkv,
                        items, (int)n_pos, (int)n_heads, (int)head_dim, scale);
     return arl::check_launch("attn_bwd_kernel");
+}
+
+extern "C" int arl_attn_tiled_fwd(const float* qkv, float* out, float* lse_or_null, int64_t batch, int32_t n_pos,
+                                  int32_t n_heads, int32_t head_dim, float scale, void* stream) {
+    ARL_REQUIRE(qkv && out, ARL_E_ARG, "null pointer");
+    ARL_REQUIRE(std::isfinite(scale), ARL_E_ARG, "scale must be finite");
+    int rc = check_attn(batch, n_pos, n_heads, head_dim, ARL_ATTN_TILED_MAX_POS);
+    if (rc) return rc;
+    const int64_t heads = batch * n_heads, items = heads * ((n_pos + AT_POS - 1) / AT_POS),
+                  n_out = batch * n_pos * n_heads * head_dim;
+    const arl::Span in[1] = {{qkv, 3 * n_out * 4}};
+    const arl::Span outs[2] = {{out, n_out * 4}, {lse_or_null, heads * n_pos * 4}};
+    if (!arl::check_disjoint("arl_attn_tiled_fwd", in, 1, outs, 2)) return ARL_E_ARG;
+    ARL_REQUIRE(arl::aligned16(qkv) && arl::aligned16(out) && arl::aligned4(lse_or_null), ARL_E_ALIGN,
+                "qkv and out 16-byte, lse 4-byte aligned");
+    const size_t lds = attn_tiled_lds_bytes(n_pos, head_dim, false);
+    rc = raise_lds(reinterpret_cast<const void*>(attn_tiled_fwd_kernel), lds, "attn_tiled_fwd_kernel");
+    if (rc) return rc;
+    const unsigned grid = (unsigned)(items < ARL_ATTN_MAX_GRID ? items : ARL_ATTN_MAX_GRID);
+    hipLaunchKernelGGL(attn_tiled_fwd_kernel, dim3(grid), dim3(AT_THREADS), lds, (hipStream_t)stream, qkv, out, lse_or_null,
+                       items, (int)n_pos, (int)n_heads, (int)head_dim, scale);
+    return arl::check_launch("attn_tiled_fwd_kernel");
+}
+
+extern "C" int arl_attn_tiled_bwd(const float* qkv, const float* out, const float* lse, const float* dout, float* dqkv,
+                                  int64_t batch, int32_t n_pos, int32_t n_heads, int32_t head_dim, float scale,
+                                  void* stream) {
+    ARL_REQUIRE(qkv && out && lse && dout && dqkv, ARL_E_ARG, "null pointer");
+    ARL_REQUIRE(std::isfinite(scale), ARL_E_ARG, "scale must be finite");
+    int rc = check_attn(batch, n_pos, n_heads, head_dim, ARL_ATTN_TILED_MAX_POS);
+    if (rc) return rc;
+    const int64_t items = batch * n_heads, n_out = batch * n_pos * n_heads * head_dim;
+    const arl::Span in[4] = {{qkv, 3 * n_out * 4}, {out, n_out * 4}, {lse, items * n_pos * 4}, {dout, n_out * 4}};
+    const arl::Span outs[1] = {{dqkv, 3 * n_out * 4}};
+    if (!arl::check_disjoint("arl_attn_tiled_bwd", in, 4, outs, 1)) return ARL_E_ARG;
+    ARL_REQUIRE(arl::aligned16(qkv) && arl::aligned16(out) && arl::aligned16(dout) && arl::aligned16(dqkv) &&
+                    arl::aligned4(lse), ARL_E_ALIGN, "qkv, out, dout and dqkv 16-byte, lse 4-byte aligned");
+    const size_t lds = attn_tiled_lds_bytes(n_pos, head_dim, true);
+    rc = raise_lds(reinterpret_cast<const void*>(attn_tiled_bwd_kernel), lds, "attn_tiled_bwd_kernel");
+    if (rc) return rc;
+    const unsigned grid = (unsigned)(items < ARL_ATTN_MAX_GRID ? items : ARL_ATTN_MAX_GRID);
+    hipLaunchKernelGGL(attn_tiled_bwd_kernel, dim3(grid), dim3(AT_THREADS), lds, (hipStream_t)stream, qkv, out, lse, dout,
+                       dqkv, items, (int)n_pos, (int)n_heads, (int)head_dim, scale);
+    return arl::check_launch("attn_tiled_bwd_kernel");
 }
 
 extern "C" int arl_entity_coords_fwd(const float* x, int64_t batch, int32_t h, int32_t w, int32_t channels, float* y,

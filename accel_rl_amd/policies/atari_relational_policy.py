@@ -15,7 +15,9 @@ then r flattened (h, w, c) -> hidden_sizes dense + rectifier layers -> AtariCnnP
 
 The default trunk is spec 1's filters, sizes and strides (atari_cnn_specs) with the padding of conv 2 and conv 3 cut to
 (0, 1) and (0, 0): 104 x 80 -> 25 x 19 -> 11 x 9 -> 9 x 7 = 63 positions of 64 channels.  Spec 1 as it stands leaves
-12 x 9 = 108 positions, more than the attention kernel's 64 (csrc/attention.hip), and is refused like every such trunk.
+12 x 9 = 108 positions, more than the one-tile attention kernel's 64 (csrc/attention.hip), and is refused like every such
+trunk unless max_positions (64 .. 256) admits it: a trunk of more than 64 positions runs on the key-tiled pair
+arl_attn_tiled_fwd / _bwd, every other one on arl_attn_fwd / _bwd whatever max_positions says.
 
 Every contraction is AtariCnnPolicy's (csrc/mfma_conv.hip; the block's two are 1 x 1 convolutions); between them run
 csrc/attention.hip (arl_entity_coords_fwd / _bwd, arl_attn_fwd / _bwd) and arl_add_relu:
@@ -48,7 +50,7 @@ class AtariRelationalPolicy(AtariCnnPolicy):
 
     def __init__(self, conv_filters=DEFAULT_TRUNK["conv_filters"], conv_filter_sizes=DEFAULT_TRUNK["conv_filter_sizes"],
                  conv_strides=DEFAULT_TRUNK["conv_strides"], conv_pads=DEFAULT_TRUNK["conv_pads"], n_blocks=1, n_heads=2,
-                 head_dim=32, hidden_sizes=(256,), pixel_scale=255., initial_param_values=None):
+                 head_dim=32, hidden_sizes=(256,), pixel_scale=255., initial_param_values=None, max_positions=64):
         def whole(v):
             return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
         if not (whole(n_blocks) and 1 <= n_blocks <= MAX_BLOCKS):
@@ -66,7 +68,11 @@ class AtariRelationalPolicy(AtariCnnPolicy):
         if not list(conv_filters):
             raise NotImplementedError("AtariRelationalPolicy: at least one trunk convolution is required (INTEGRATION.md, "
                                       "section E)")
+        if not (whole(max_positions) and _lib.ATTN_MAX_POS <= max_positions <= _lib.ATTN_TILED_MAX_POS):
+            raise NotImplementedError("AtariRelationalPolicy: max_positions must be in %d .. %d, got %r (INTEGRATION.md, "
+                                      "section E)" % (_lib.ATTN_MAX_POS, _lib.ATTN_TILED_MAX_POS, max_positions))
         self.n_blocks, self.n_heads, self.head_dim = int(n_blocks), int(n_heads), int(head_dim)
+        self.max_positions = int(max_positions)
         self._n_trunk, self._trunk_c = len(conv_filters), int(conv_filters[-1])
         block = [3 * self.n_heads * self.head_dim, self._trunk_c]
         # the base's flat conv list: the trunk, then two 1 x 1 convolutions per block
@@ -110,10 +116,10 @@ class AtariRelationalPolicy(AtariCnnPolicy):
     def initialize(self, env_spec, device=None, **kwargs):
         shape = tuple(env_spec.observation_space.shape)
         ho, wo = self.positions(shape)
-        if ho < 1 or wo < 1 or ho * wo > _lib.ATTN_MAX_POS:
+        if ho < 1 or wo < 1 or ho * wo > self.max_positions:
             raise NotImplementedError("AtariRelationalPolicy: the trunk leaves %d x %d positions of a %d x %d image; the "
                                       "attention kernel takes 1 .. %d (INTEGRATION.md, section E)" %
-                                      (ho, wo, shape[1], shape[2], _lib.ATTN_MAX_POS))
+                                      (ho, wo, shape[1], shape[2], self.max_positions))
         if self._trunk_c % 4:
             raise NotImplementedError("conv filter counts must be multiples of 4 (got %d)" % self._trunk_c)
         self.rows_per_pass()
@@ -153,6 +159,7 @@ class AtariRelationalPolicy(AtariCnnPolicy):
         r = xs = trunk[-1]
         _, ho, wo, c = r.shape
         heads, d = self.n_heads, self.head_dim
+        attn_fwd = _lib.attn_tiled_fwd if ho * wo > _lib.ATTN_MAX_POS else _lib.attn_fwd
         blocks = []
         for k in range(self.n_blocks):
             kq, ko = self._n_trunk + 2 * k, self._n_trunk + 2 * k + 1
@@ -165,7 +172,7 @@ class AtariRelationalPolicy(AtariCnnPolicy):
             r_new = self._buffer(("act" + tag, ko, b), (b, ho, wo, c))
             _lib.entity_coords_fwd(r, rc)
             _lib.conv2d_fwd(rc, w[2 * kq], w[2 * kq + 1], qkv, conv_g[kq], False, self._conv_ws)
-            _lib.attn_fwd(qkv, a, lse)
+            attn_fwd(qkv, a, lse)
             _lib.conv2d_fwd(a, w[2 * ko], w[2 * ko + 1], t, conv_g[ko], False, self._conv_ws)
             _lib.add_relu(xs, t, x_new, r_new)
             blocks.append(dict(rc=rc, qkv=qkv, a=a, lse=lse))
@@ -192,6 +199,7 @@ class AtariRelationalPolicy(AtariCnnPolicy):
         trunk, blocks, _ = acts
         shape = tuple(trunk[-1].shape)
         g = d_act.view(shape)
+        attn_bwd = _lib.attn_tiled_bwd if shape[1] * shape[2] > _lib.ATTN_MAX_POS else _lib.attn_bwd
         # every gradient in a buffer of its own, all held until the end of the pass: a deferred weight gradient reads
         # them at run_wgrads(), and under graph capture a tensor nobody holds hands its memory to the next _buffer
         live = []
@@ -201,7 +209,7 @@ class AtariRelationalPolicy(AtariCnnPolicy):
             da = self._buffer(("dx_conv", ko, b), tuple(blk["a"].shape))
             corun = self._block_conv_backward(ko, g, blk["a"], da, b, conv_g, corun, group, False)
             dqkv = self._buffer(("dqkv", k, b), tuple(blk["qkv"].shape))
-            _lib.attn_bwd(blk["qkv"], blk["a"], blk["lse"], da, dqkv)
+            attn_bwd(blk["qkv"], blk["a"], blk["lse"], da, dqkv)
             d_rc = self._buffer(("dx_conv", kq, b), tuple(blk["rc"].shape))
             corun = self._block_conv_backward(kq, dqkv, blk["rc"], d_rc, b, conv_g, corun, group, True)
             g_in = self._buffer(("dskip", k, b), shape)

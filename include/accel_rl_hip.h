@@ -1868,6 +1868,38 @@ int arl_attn_fwd(const float* qkv, float* out, float* lse_or_null, int64_t batch
 int arl_attn_bwd(const float* qkv, const float* out, const float* lse, const float* dout, float* dqkv, int64_t batch,
                  int32_t n_pos, int32_t n_heads, int32_t head_dim, float scale, void* stream);
 
+/* The same attention for 1 <= n_pos <= ARL_ATTN_TILED_MAX_POS: the positions are cut into tiles of 64 (tile t holds
+ * positions 64 t .. 64 t + 63; the last may be short) and the key tiles stream through LDS around an online soft-max.
+ * Tensors, layouts, checks and error codes are arl_attn_fwd's / arl_attn_bwd's, with ARL_ATTN_TILED_MAX_POS for
+ * ARL_ATTN_MAX_POS; every product is the same MFMA chain, and s_ij is formed by the same instructions in both passes.
+ *   forward   per query row i, from m_i = -inf, l_i = 0.f and O_ie = 0.f, for the key tiles t in ascending order:
+ *               m' = max(m_i, max_{j in t} s_ij);  x_ij = expf(s_ij - m');  alpha = expf(m_i - m')  (0.f at the first tile)
+ *               l_i = alpha * l_i + (((p0 + p1) + p2) + p3),  p_q = the sum of x_ij over j = 64 t + q, + 4, .. from 0.f
+ *               O_ie = O_ie * alpha, then the chain sum_{j in t} x_ij V_je goes on from that value;  m_i = m'
+ *             out_ie = O_ie * (1.f / l_i);  lse_i = m_i + logf(l_i).  Where head_dim <= 32, O is kept as two such
+ *             accumulators, one over the keys 64 t .. 64 t + 31 of every tile and one over the keys 64 t + 32 .. 64 t + 63,
+ *             each scaled by alpha at every tile, and out_ie = (first + second) * (1.f / l_i): one addition per element.
+ *             The output has the same bits with and without lse.  No NaN is formed: m' is finite from the first tile on.
+ *   backward  P_ij = expf(s_ij - lse_i), D_i and dS_ij as arl_attn_bwd states them.  For the key tiles t in ascending
+ *             order, and inside for the query tiles u in ascending order:
+ *               dV_je and dK_je (j in t): one chain each over all i, u after u, i ascending inside u, from 0.f; where
+ *               head_dim <= 32 two chains, over the i of the first 32 rows of every u and over the i of the second 32
+ *               rows, added once after the last u: first + second
+ *               dQ_ie (i in u): the partial sum_{j in t} dS_ij K_je is a chain of its own from 0.f (head_dim <= 32:
+ *               keys 64 t .. 64 t + 31 + keys 64 t + 32 .. 64 t + 63); dQ_ie is the partial of t = 0, and every later
+ *               tile's partial is added to it in ascending t: ((part_0 + part_1) + part_2) + part_3.
+ * P and dS exist in LDS only; O, dK and dV stay in the MFMA accumulators and the dQ sums in LDS until they are whole.
+ * Work split: forward, one item per (sample, head, query tile); backward, one per (sample, head); min(items,
+ * ARL_ATTN_MAX_GRID) workgroups of four waves walk them grid-stride.  One writer per output element, no atomics, no
+ * partial sums in global memory, nothing depends on the grid: two launches give the same bits.  With n_pad = n_pos
+ * rounded up to 64, LDS per workgroup: (3 * 64 * (head_dim + 1) + 64 * 65 + 192) * 4 bytes forward,
+ * ((n_pad + 256) * (head_dim + 1) + 64 * 65 + 2 * n_pad) * 4 backward (151 808 at n_pos 256, head_dim 64).          */
+#define ARL_ATTN_TILED_MAX_POS 256
+int arl_attn_tiled_fwd(const float* qkv, float* out, float* lse_or_null, int64_t batch, int32_t n_pos, int32_t n_heads,
+                       int32_t head_dim, float scale, void* stream);
+int arl_attn_tiled_bwd(const float* qkv, const float* out, const float* lse, const float* dout, float* dqkv, int64_t batch,
+                       int32_t n_pos, int32_t n_heads, int32_t head_dim, float scale, void* stream);
+
 /* The coordinate channels of the relational policy, on NHWC activations; one float4 per thread, no LDS, 64-bit indexing.
  * arl_entity_coords_fwd: x f32[batch][h][w][channels] -> y f32[batch][h][w][channels + 4]: y[b][i][j][c] = x[b][i][j][c]
  *   for c < channels; channel `channels` = (float)(2 j - (w - 1)) / (float)(w - 1) (integer numerator and denominator

@@ -1,10 +1,13 @@
-"""The measurements of DESIGN.md 39 (the relational policy; recorded, no bar).  `python tools/attn_bench.py [kern] [iter]`:
-  kern   arl_attn_fwd and arl_attn_bwd at B = 256 and 1280, N = 63, H = 2, d = 32, next to the same mathematics as
-         PyTorch calls (two batched matmuls and a soft-max forward; the five products of the backward written out), each a
-         captured graph of 50 calls replayed under device events, the two taking turns; medians (min / max) of 9 windows
-  iter   whole A2C iterations (rollout + captured update) at config 2's sizes with AtariRelationalPolicy() and with
-         AtariCnnPolicy(**cnn_specs[1]) in one process, taking turns in windows of 60 iterations after 25 warm-up
-         iterations each, under device events
+"""The measurements of DESIGN.md 39 and 40 (the relational policy; recorded, no bar).
+`python tools/attn_bench.py [kern] [iter] [N ...]`:
+  kern   the attention pair at B = 256 and 1280, H = 2, d = 32 and every position count N given (63 if none): arl_attn_fwd
+         and arl_attn_bwd up to 64 positions, arl_attn_tiled_fwd and arl_attn_tiled_bwd above, next to the same
+         mathematics as PyTorch calls (two batched matmuls and a soft-max forward; the five products of the backward
+         written out), each a captured graph of 50 calls replayed under device events, the two taking turns; medians
+         (min / max) of 9 windows
+  iter   whole A2C iterations (rollout + captured update) at config 2's sizes with AtariRelationalPolicy(), with
+         AtariRelationalPolicy(**spec 1's conv arguments, max_positions=128) and with AtariCnnPolicy(**cnn_specs[1]) in one
+         process, taking turns in windows of 60 iterations after 25 warm-up iterations each, under device events
 One JSON line per part."""
 import collections
 import json
@@ -74,9 +77,10 @@ def kernel_times(b, n=63, h=2, d=32):
         lib["dqkv"] = torch.stack([ds @ k, ds.transpose(2, 3) @ q, p.transpose(2, 3) @ do], dim=1).permute(0, 3, 1, 2, 4)
 
     graphs = collections.OrderedDict()
-    graphs["hip_fwd"] = _graph(lambda: _lib.attn_fwd(qkv, out, lse, scale))
+    fwd, bwd = (_lib.attn_tiled_fwd, _lib.attn_tiled_bwd) if n > _lib.ATTN_MAX_POS else (_lib.attn_fwd, _lib.attn_bwd)
+    graphs["hip_fwd"] = _graph(lambda: fwd(qkv, out, lse, scale))
     graphs["pytorch_fwd"] = _graph(lib_fwd)
-    graphs["hip_bwd"] = _graph(lambda: _lib.attn_bwd(qkv, out, lse, dout, dqkv, scale))
+    graphs["hip_bwd"] = _graph(lambda: bwd(qkv, out, lse, dout, dqkv, scale))
     graphs["pytorch_bwd"] = _graph(lib_bwd)
     torch.cuda.synchronize()
     assert torch.allclose(lib["out"], out, rtol=1e-3, atol=1e-5) and torch.allclose(lib["dqkv"], dqkv, rtol=1e-3, atol=1e-5)
@@ -100,7 +104,9 @@ def build_a2c(relational):
     sampler = GpuVecSampler(EnvCls=SynthAtariEnv, env_args=dict(game=bench.GAME), horizon=bench.HORIZON, n_parallel=16,
                             envs_per=bench.N_ENVS // 32, max_path_length=int(27e3), mid_batch_reset=True,
                             max_decorrelation_steps=2000, device=DEV, use_graph=True)
-    policy = AtariRelationalPolicy() if relational else AtariCnnPolicy(**cnn_specs[1])
+    spec1 = {k: v for k, v in cnn_specs[1].items() if k != "hidden_sizes"}
+    policy = {"default": AtariRelationalPolicy, "spec1": lambda: AtariRelationalPolicy(**spec1, max_positions=128),
+              None: lambda: AtariCnnPolicy(**cnn_specs[1])}[relational]()
     algo = A2C(discount=0.99, gae_lambda=1, use_graph=True)
     runner = AccelRL(algo=algo, policy=policy, sampler=sampler, n_steps=1e9, seed=0, affinities=dict(gpu=0),
                      log_interval_steps=1e8)
@@ -109,7 +115,8 @@ def build_a2c(relational):
 
 
 def iterations(warm=25, window=60, windows=5):
-    variants = collections.OrderedDict(a2c_relational=build_a2c(True), a2c_spec1=build_a2c(False))
+    variants = collections.OrderedDict(a2c_relational=build_a2c("default"), a2c_relational_spec1=build_a2c("spec1"),
+                                       a2c_spec1=build_a2c(None))
     itr = {k: 0 for k in variants}
 
     def run(name, n):
@@ -133,9 +140,11 @@ def iterations(warm=25, window=60, windows=5):
 
 
 if __name__ == "__main__":
-    what = sys.argv[1:] or ["kern", "iter"]
+    counts = [int(a) for a in sys.argv[1:] if a.isdigit()] or [63]
+    what = [a for a in sys.argv[1:] if not a.isdigit()] or ["kern", "iter"]
     if "kern" in what:
-        result.update(kernel_b256=kernel_times(256), kernel_b1280=kernel_times(1280))
+        for n in counts:
+            result.update({"kernel_n%d_b%d" % (n, b): kernel_times(b, n) for b in (256, 1280)})
         print(json.dumps(result), flush=True)
     if "iter" in what:
         result["iteration_us"] = iterations()
