@@ -261,6 +261,10 @@ _SIGNATURES = {
     "arl_attn_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _vp]),
     "arl_attn_tiled_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _vp]),
     "arl_attn_tiled_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _vp]),
+    "arl_tattn_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp]),
+    "arl_tattn_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "arl_tattn_rel_fold": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp]),
+    "arl_tattn_shift": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
     "arl_entity_coords_fwd": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "arl_entity_coords_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "arl_gather_scale_obs_nhwc_any": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp]),
@@ -2108,6 +2112,103 @@ def entity_coords_bwd(g, d_y, mask, g_in, stream=None):
             raise ValueError("entity coords: %s must have g's shape" % name)
     _check(load().arl_entity_coords_bwd(ptr(g), ptr(d_y), ptr(mask), b, h, w, c, ptr(g_in), stream_ptr(stream)),
            "arl_entity_coords_bwd")
+
+
+# ---------------------------------------------------------------------------
+# Windowed causal attention over time (csrc/tattention.hip)
+# ---------------------------------------------------------------------------
+
+TATTN_MAX_STEPS, TATTN_MAX_MEM = 64, 64                 # ARL_TATTN_MAX_*
+
+
+def _flags_u8(reset):
+    """The flags as the kernels read them: a bool tensor (the samplers' `need_reset`) as its uint8 view."""
+    return reset.view(torch.uint8) if reset is not None and reset.dtype == torch.bool else reset
+
+
+def tattn_shape_ok(seg_len, mem_len, n_heads, head_dim):
+    """What arl_tattn_fwd / arl_tattn_bwd take (accel_rl_hip.h); needs no device."""
+    return 1 <= seg_len <= TATTN_MAX_STEPS and 1 <= mem_len <= TATTN_MAX_MEM and attn_shape_ok(1, n_heads, head_dim)
+
+
+def _tattn_dims(q, kv, rel, out, lse, reset, idx):
+    """(n_seg, T, M, H, d) of q [S, T, H, d], after the shape checks of kv [S, M + T, 2, H, d], rel [H, M + 1], out
+    [S, T, H * d], lse [S, H, T] (may be None), reset u8 / bool (any length: idx, when given, addresses it) and idx
+    i32[S * T]."""
+    if q.dim() != 4 or kv.dim() != 5 or kv.shape[0] != q.shape[0] or kv.shape[2] != 2 or tuple(kv.shape[3:]) != tuple(q.shape[2:]):
+        raise ValueError("q must be [n_seg, T, H, d] and kv [n_seg, M + T, 2, H, d], got %s and %s" %
+                         (tuple(q.shape), tuple(kv.shape)))
+    s, t, h, d = q.shape
+    m = kv.shape[1] - t
+    for x, name in ((q, "q"), (kv, "kv"), (rel, "rel"), (out, "out")) + (() if lse is None else ((lse, "lse"),)):
+        _want(x, torch.float32, name)
+    if tuple(rel.shape) != (h, m + 1):
+        raise ValueError("rel must be [%d, %d], got %s" % (h, m + 1, tuple(rel.shape)))
+    if out.numel() != s * t * h * d or out.shape[0] != s:
+        raise ValueError("out must hold [%d, %d, %d] floats, got %s" % (s, t, h * d, tuple(out.shape)))
+    if lse is not None and tuple(lse.shape) != (s, h, t):
+        raise ValueError("lse must be [%d, %d, %d], got %s" % (s, h, t, tuple(lse.shape)))
+    if reset is not None:
+        _want_flags(reset, "reset")
+        if idx is None and reset.numel() != s * t:
+            raise ValueError("reset must hold %d flags without idx, got %d" % (s * t, reset.numel()))
+    if idx is not None:
+        _want(idx, torch.int32, "idx")
+        if idx.numel() != s * t:
+            raise ValueError("idx must hold %d rows, got %d" % (s * t, idx.numel()))
+    return s, t, m, h, d
+
+
+def tattn_fwd(q, kv, rel, out, lse=None, reset=None, idx=None, scale=None, stream=None):
+    """out [S, T, H * d] = the windowed causal attention of q [S, T, H, d] over kv [S, M + T, 2, H, d] with the relative
+    bias rel [H, M + 1]; reset u8 (read through idx when given): the steps after which the memory was cleared; lse
+    [S, H, T] for tattn_bwd.  scale: 1 / sqrt(d) unless given."""
+    s, t, m, h, d = _tattn_dims(q, kv, rel, out, lse, reset, idx)
+    reset = _flags_u8(reset)
+    scale = d ** -0.5 if scale is None else scale
+    _check(load().arl_tattn_fwd(ptr(q), ptr(kv), ptr(rel), ptr(reset), ptr(idx), s, t, m, h, d, float(scale), ptr(out),
+                                ptr(lse), stream_ptr(stream)), "arl_tattn_fwd")
+
+
+def tattn_bwd(q, kv, rel, out, lse, dout, dq, dkv, drel_parts, reset=None, idx=None, scale=None, stream=None):
+    """dq, dkv (q's and kv's layouts) and drel_parts [S, H, M + 1] (tattn_rel_fold's input) given dout."""
+    s, t, m, h, d = _tattn_dims(q, kv, rel, out, lse, reset, idx)
+    reset = _flags_u8(reset)
+    if lse is None:
+        raise ValueError("tattn_bwd needs the forward's lse")
+    for x, like, name in ((dout, out, "dout"), (dq, q, "dq"), (dkv, kv, "dkv")):
+        _want(x, torch.float32, name)
+        if x.numel() != like.numel():
+            raise ValueError("%s must hold %d floats, got %s" % (name, like.numel(), tuple(x.shape)))
+    _want(drel_parts, torch.float32, "drel_parts")
+    if tuple(drel_parts.shape) != (s, h, m + 1):
+        raise ValueError("drel_parts must be [%d, %d, %d], got %s" % (s, h, m + 1, tuple(drel_parts.shape)))
+    scale = d ** -0.5 if scale is None else scale
+    _check(load().arl_tattn_bwd(ptr(q), ptr(kv), ptr(rel), ptr(reset), ptr(idx), ptr(out), ptr(lse), ptr(dout), ptr(dq),
+                                ptr(dkv), ptr(drel_parts), s, t, m, h, d, float(scale), stream_ptr(stream)), "arl_tattn_bwd")
+
+
+def tattn_rel_fold(drel_parts, drel, stream=None):
+    """drel [H, M + 1] = drel_parts [S, H, M + 1] added over S in ascending order."""
+    _want(drel_parts, torch.float32, "drel_parts")
+    _want(drel, torch.float32, "drel")
+    s, h, m1 = drel_parts.shape
+    if tuple(drel.shape) != (h, m1):
+        raise ValueError("drel must be [%d, %d], got %s" % (h, m1, tuple(drel.shape)))
+    _check(load().arl_tattn_rel_fold(ptr(drel_parts), s, h, m1 - 1, ptr(drel), stream_ptr(stream)), "arl_tattn_rel_fold")
+
+
+def tattn_shift(state, e, window, prev=None, stream=None):
+    """window [B, M + 1, E] = [state ; e], prev [B, M * E] = state as it was, state [B, M * E] <- window[:, 1:] in place."""
+    b, width = e.shape
+    m = state.numel() // max(b * width, 1)
+    for x, n, name in ((state, b * m * width, "state"), (e, b * width, "e"), (window, b * (m + 1) * width, "window")) + \
+            (() if prev is None else ((prev, b * m * width, "prev"),)):
+        _want(x, torch.float32, name)
+        if x.numel() != n:
+            raise ValueError("tattn_shift: %s must hold %d floats, got %s" % (name, n, tuple(x.shape)))
+    _check(load().arl_tattn_shift(ptr(state), ptr(e), b, m, width, ptr(window), ptr(prev), stream_ptr(stream)),
+           "arl_tattn_shift")
 
 
 # ---------------------------------------------------------------------------

@@ -1915,6 +1915,60 @@ int arl_entity_coords_bwd(const float* g, const float* d_y, const float* mask_or
                           int32_t channels, float* g_in, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Windowed causal attention over time (the attention-memory policy; csrc/tattention.hip)
+ * ------------------------------------------------------------------------- */
+
+/* With T = seg_len, M = mem_len, L = M + T, H = n_heads, d = head_dim; all f32 and contiguous unless said:
+ *   q [n_seg][T][H][d], kv [n_seg][L][2][H][d] (K then V; context rows 0 .. M - 1 are the stored memory, oldest first, row
+ *   M + t is step t's own), rel [H][M + 1], out and dout [n_seg][T][H d], lse [n_seg][H][T], dq as q, dkv as kv,
+ *   drel_parts [n_seg][H][M + 1]; reset u8 and idx i32: the flag of step t of segment s is
+ *   reset[idx ? idx[s T + t] : s T + t] (arl_traj_minibatch's row map addresses the full batch's flags in place; row
+ *   numbers are taken as valid); reset NULL: no flag is set.  The overlap check below knows the flags only as their
+ *   first n_seg T bytes: with idx the caller keeps the outputs clear of the rest of the full batch's flag array.
+ * Per segment s and head h, for query t < T and context row c < L, with the age a = M + t - c and
+ * R_t = 1 + max{r < t : flag(r) != 0} (0 if there is none):
+ *   in the window  iff 0 <= a <= M;   live  iff R_t == 0 or c >= M + R_t
+ *   s_tc = scale * (sum_e q_te k_ce) + rel[h][a]   live (the sum on the fp32 MFMA chain of arl_attn_fwd, one
+ *          multiplication, one addition);   s_tc = rel[h][a]   dead;   v_c counts as 0 for a dead entry
+ *   forward   arl_attn_tiled_fwd's online soft-max over the context tiles (rows 64 u .. 64 u + 63) in ascending order,
+ *             the entries outside the window taking no part: m, alpha, l_t = alpha l_t + (((p0 + p1) + p2) + p3) with
+ *             p_q over c = 64 u + q, + 4, .., dead entries included; O_te = O_te alpha, then the chain of x_tc v_ce over
+ *             the live c of the tile goes on (head_dim <= 32: two accumulators over the first and second 32 rows of every
+ *             tile, added once at the end); out_te = O_te * (1.f / l_t), lse_t = m_t + logf(l_t)
+ *   backward  s_tc by the same instructions, P_tc = expf(s_tc - lse_t) in the window, 0 outside; D_t as arl_attn_bwd;
+ *             dP_tc = sum_e dout_te v_ce live, 0 dead;  W_tc = P_tc * (dP_tc - D_t);  dS_tc = scale * W_tc live, 0 dead
+ *             dV_ce = sum_t P_tc dout_te over the live t, dK_ce = sum_t dS_tc q_te: one chain each over t ascending
+ *             (head_dim <= 32: t < 32 and t >= 32, two chains and one addition); a context row no live query sees gets
+ *             exact zeros.  dQ_te = sum_c dS_tc k_ce: one chain per context tile (head_dim <= 32: halves of the tile
+ *             added), tile 0's partial + tile 1's.  drel_parts[s][h][a] = the W_tc with c = M + t - a added one by one
+ *             in ascending t from 0.f.  Every element of dq, dkv and drel_parts is written exactly once.
+ * arl_tattn_rel_fold: drel[h][a] = drel_parts[0][h][a] + drel_parts[1][h][a] + .. in ascending s from 0.f.
+ * arl_tattn_shift (serving): state [n_env][M][width], e [n_env][width] -> window [n_env][M + 1][width] = [state ; e],
+ *   prev_or_null [n_env][M][width] = state as it was, and state <- window[:, 1:] in place; copies only.
+ * Work split: one item per (segment, head); min(n_seg H, ARL_ATTN_MAX_GRID) workgroups of four waves walk them
+ * grid-stride; no atomics, nothing depends on the grid: two launches give the same bits, and an all-zero reset mask gives
+ * the bits of reset NULL.  LDS per workgroup: (3 * 64 * (d + 1) + 64 * 65 + 324) * 4 bytes forward, (5 * 64 * (d + 1) +
+ * 2 * 64 * 65 + 260) * 4 backward (117 520 at d = 64).
+ * Refused before any HIP call, nothing written: a NULL pointer other than reset, idx, lse_or_null (forward) and
+ * prev_or_null, a scale that is not finite, an output that overlaps an input or another output (ARL_E_ARG); n_seg or
+ * n_env outside 1 .. ARL_ATTN_MAX_BATCH, seg_len outside 1 .. ARL_TATTN_MAX_STEPS, mem_len outside 1 .. ARL_TATTN_MAX_MEM,
+ * head_dim outside 4 .. ARL_ATTN_MAX_HEAD_DIM or not a multiple of 4, n_heads < 1 or n_heads head_dim >
+ * ARL_ATTN_MAX_WIDTH, width outside 4 .. 1024 or not a multiple of 4 (ARL_E_RANGE); q, kv, out, dout, dq, dkv, state, e,
+ * window or prev not 16-byte, rel, idx, lse, drel_parts or drel not 4-byte aligned (ARL_E_ALIGN).                       */
+#define ARL_TATTN_MAX_STEPS 64
+#define ARL_TATTN_MAX_MEM   64
+int arl_tattn_fwd(const float* q, const float* kv, const float* rel, const uint8_t* reset_or_null,
+                  const int32_t* idx_or_null, int64_t n_seg, int32_t seg_len, int32_t mem_len, int32_t n_heads,
+                  int32_t head_dim, float scale, float* out, float* lse_or_null, void* stream);
+int arl_tattn_bwd(const float* q, const float* kv, const float* rel, const uint8_t* reset_or_null,
+                  const int32_t* idx_or_null, const float* out, const float* lse, const float* dout, float* dq, float* dkv,
+                  float* drel_parts, int64_t n_seg, int32_t seg_len, int32_t mem_len, int32_t n_heads, int32_t head_dim,
+                  float scale, void* stream);
+int arl_tattn_rel_fold(const float* drel_parts, int64_t n_seg, int32_t n_heads, int32_t mem_len, float* drel, void* stream);
+int arl_tattn_shift(float* state, const float* e, int64_t n_env, int32_t mem_len, int32_t width, float* window,
+                    float* prev_or_null, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * LSTM cell of the recurrent policies
  * ------------------------------------------------------------------------- */
 
