@@ -265,6 +265,10 @@ _SIGNATURES = {
     "arl_tattn_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, _vp]),
     "arl_tattn_rel_fold": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp]),
     "arl_tattn_shift": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "arl_lru_params": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "arl_lru_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "arl_lru_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "arl_lru_param_fold": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
     "arl_entity_coords_fwd": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "arl_entity_coords_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "arl_gather_scale_obs_nhwc_any": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _vp]),
@@ -346,6 +350,7 @@ _DEV_SIGNATURES = {
     "arl_dev_scan_force_wave": (None, [_i32]),
     "arl_dev_scan_wave_groups": (None, [_i32]),
     "arl_dev_env_variant": (None, [_i32]),
+    "arl_dev_lru_force_path": (None, [_i32]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -2209,6 +2214,86 @@ def tattn_shift(state, e, window, prev=None, stream=None):
             raise ValueError("tattn_shift: %s must hold %d floats, got %s" % (name, n, tuple(x.shape)))
     _check(load().arl_tattn_shift(ptr(state), ptr(e), b, m, width, ptr(window), ptr(prev), stream_ptr(stream)),
            "arl_tattn_shift")
+
+
+# ---------------------------------------------------------------------------
+# Linear recurrent unit over time (csrc/lru.hip)
+# ---------------------------------------------------------------------------
+
+LRU_MAX_STEPS, LRU_MAX_STATE, LRU_MAX_GRID, LRU_CHUNK_MIN = 1024, 512, 1024, 32         # ARL_LRU_*
+
+
+def lru_shape_ok(seg_len, state_size):
+    """What arl_lru_fwd / arl_lru_bwd take (accel_rl_hip.h); needs no device."""
+    return 1 <= seg_len <= LRU_MAX_STEPS and 2 <= state_size <= LRU_MAX_STATE and state_size % 2 == 0
+
+
+def _lru_dims(u, lam, gam, h0, reset, idx, same):
+    """(n_seg, T, N) of u [S, T, 2 N], after the shape checks of lam [N, 2], gam [N], h0 [S, 2 N], reset u8 / bool (any
+    length: idx, when given, addresses it), idx i32[S * T] and the (tensor, name) pairs of `same`, shaped as u."""
+    if u.dim() != 3 or u.shape[2] % 2:
+        raise ValueError("u must be [n_seg, T, 2 N], got %s" % (tuple(u.shape),))
+    s, t, n = u.shape[0], u.shape[1], u.shape[2] // 2
+    for x, shape, name in ((u, u.shape, "u"), (lam, (n, 2), "lam"), (gam, (n,), "gam"), (h0, (s, 2 * n), "h0")) + tuple(
+            (x, u.shape, name) for x, name in same):
+        _want(x, torch.float32, name)
+        if tuple(x.shape) != tuple(shape):
+            raise ValueError("%s must be %s, got %s" % (name, tuple(shape), tuple(x.shape)))
+    if reset is not None:
+        _want_flags(reset, "reset")
+        if idx is None and reset.numel() != s * t:
+            raise ValueError("reset must hold %d flags without idx, got %d" % (s * t, reset.numel()))
+    if idx is not None:
+        _want(idx, torch.int32, "idx")
+        if idx.numel() != s * t:
+            raise ValueError("idx must hold %d rows, got %d" % (s * t, idx.numel()))
+    return s, t, n
+
+
+def lru_params(nu, theta, lam, gam, stream=None):
+    """lam [N, 2] = exp(-exp(nu) + i theta) and gam [N] = sqrt(1 - |lam|^2) of nu, theta [N]."""
+    n = nu.numel()
+    for x, shape, name in ((nu, (n,), "nu"), (theta, (n,), "theta"), (lam, (n, 2), "lam"), (gam, (n,), "gam")):
+        _want(x, torch.float32, name)
+        if tuple(x.shape) != shape:
+            raise ValueError("%s must be %s, got %s" % (name, shape, tuple(x.shape)))
+    _check(load().arl_lru_params(ptr(nu), ptr(theta), n, ptr(lam), ptr(gam), stream_ptr(stream)), "arl_lru_params")
+
+
+def lru_fwd(u, lam, gam, h0, h_all, h_last=None, reset=None, idx=None, stream=None):
+    """h_all [S, T, 2 N]: h_t = keep_t lam h_(t-1) + gam u_t from h0 [S, 2 N], the carry dropped after a flagged step
+    (reset u8 / bool, read through idx when given); h_last [S, 2 N] = the last step's state, may be h0 itself."""
+    s, t, n = _lru_dims(u, lam, gam, h0, reset, idx, ((h_all, "h_all"),))
+    if h_last is not None:
+        _want(h_last, torch.float32, "h_last")
+        if tuple(h_last.shape) != (s, 2 * n):
+            raise ValueError("h_last must be [%d, %d], got %s" % (s, 2 * n, tuple(h_last.shape)))
+    _check(load().arl_lru_fwd(ptr(u), ptr(lam), ptr(gam), ptr(h0), ptr(_flags_u8(reset)), ptr(idx), s, t, n, ptr(h_all),
+                              ptr(h_last), stream_ptr(stream)), "arl_lru_fwd")
+
+
+def lru_bwd(u, h_all, h0, lam, gam, dh, du, dlam_parts, dgam_parts, reset=None, idx=None, stream=None):
+    """du (may be dh) and the per-segment partials dlam_parts [S, N, 2], dgam_parts [S, N] (lru_param_fold's input) given
+    dh = d loss / d h_all."""
+    s, t, n = _lru_dims(u, lam, gam, h0, reset, idx, ((h_all, "h_all"), (dh, "dh"), (du, "du")))
+    for x, shape, name in ((dlam_parts, (s, n, 2), "dlam_parts"), (dgam_parts, (s, n), "dgam_parts")):
+        _want(x, torch.float32, name)
+        if tuple(x.shape) != shape:
+            raise ValueError("%s must be %s, got %s" % (name, shape, tuple(x.shape)))
+    _check(load().arl_lru_bwd(ptr(u), ptr(h_all), ptr(h0), ptr(lam), ptr(gam), ptr(dh), ptr(_flags_u8(reset)), ptr(idx), s, t,
+                              n, ptr(du), ptr(dlam_parts), ptr(dgam_parts), stream_ptr(stream)), "arl_lru_bwd")
+
+
+def lru_param_fold(dlam_parts, dgam_parts, nu, theta, dnu, dtheta, stream=None):
+    """dnu, dtheta [N] from the partials of lru_bwd added over the segments in ascending order."""
+    s, n = dgam_parts.shape
+    for x, shape, name in ((dlam_parts, (s, n, 2), "dlam_parts"), (dgam_parts, (s, n), "dgam_parts"), (nu, (n,), "nu"),
+                           (theta, (n,), "theta"), (dnu, (n,), "dnu"), (dtheta, (n,), "dtheta")):
+        _want(x, torch.float32, name)
+        if tuple(x.shape) != shape:
+            raise ValueError("%s must be %s, got %s" % (name, shape, tuple(x.shape)))
+    _check(load().arl_lru_param_fold(ptr(dlam_parts), ptr(dgam_parts), ptr(nu), ptr(theta), s, n, ptr(dnu), ptr(dtheta),
+                                     stream_ptr(stream)), "arl_lru_param_fold")
 
 
 # ---------------------------------------------------------------------------

@@ -1969,6 +1969,64 @@ int arl_tattn_shift(float* state, const float* e, int64_t n_env, int32_t mem_len
                     float* prev_or_null, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Linear recurrent unit over time (the LRU policy; csrc/lru.hip)
+ * ------------------------------------------------------------------------- */
+
+/* With T = seg_len and N = state_size complex channels stored as interleaved (re, im) f32 pairs; all f32 and contiguous:
+ *   nu, theta, gam, dnu, dtheta [N], lam [N][2], u, h_all, dh, du [n_seg][T][N][2], h0, h_last [n_seg][N][2],
+ *   dlam_parts [n_seg][N][2], dgam_parts [n_seg][N]; reset u8 and idx i32 as arl_tattn_fwd reads them: the flag of step t
+ *   of segment s is reset[idx ? idx[s T + t] : s T + t], reset NULL: no flag is set (the overlap check knows the flags only
+ *   as their first n_seg T bytes).  Complex products are written out in real arithmetic, one multiplication and one
+ *   addition at a time: a b = (a_re b_re - a_im b_im, a_re b_im + a_im b_re), conj(a) b = (a_re b_re + a_im b_im,
+ *   a_re b_im - a_im b_re).
+ * arl_lru_params: in float64 e = exp(nu), m = exp(-e); lam = (m cos(theta), m sin(theta)), gam = sqrt(-expm1(-2 e))
+ *   (= sqrt(1 - |lam|^2)), each rounded once to f32.
+ * arl_lru_fwd, per segment and channel, t ascending, prev_0 = h0, prev_t = h_(t-1), keep_t = (t == 0 or flag(t - 1) == 0):
+ *   h_t = lam prev_t + (gam u_t_re, gam u_t_im) if keep_t, else (gam u_t_re, gam u_t_im): the carry takes no part.
+ *   h_last = h_(T-1); it may be h0's buffer (a thread reads its own element of h0 before any thread writes it), which
+ *   makes a served step of this kernel at T = 1 on the stored state.  flag(T - 1) is not read.
+ * arl_lru_bwd, t descending, with keep'_t = (t + 1 < T and flag(t) == 0):  g_t = dh_t + conj(lam) g_(t+1) if keep'_t, else
+ *   dh_t;  du_t = (gam g_t_re, gam g_t_im);  d lam = the sum of conj(prev_t) g_t over the t with keep_t (t = 0 with h0),
+ *   d gam = the sum of (u_t_re g_t_re + u_t_im g_t_im), one term per step, both from 0.f in descending t.  du may be dh's
+ *   buffer (a thread reads its own element before it writes it).  h0 is a constant: no gradient leaves towards it.
+ * seg_len >= ARL_LRU_CHUNK_MIN: the time axis is cut into four chunks of ceil(T / 4) steps (chunk w = steps w len ..
+ *   min(T, (w + 1) len) - 1; a chunk may be empty).  Forward: chunks 0 .. 2 run from a zero carry with a multiplier A
+ *   that starts at (1, 0): A = lam A at a kept step, A = (0, 0) at a step without carry; B = the chunk's end state.
+ *   Chunk w's carry-in is c = h0, then c = A_j c + B_j for j = 0 .. w - 1 in ascending order, and the chunk runs again
+ *   from c as above (chunk 0 exactly as below the threshold).  Backward: chunks 3 .. 1 run in descending t from a zero
+ *   carry, A = conj(lam) A or (0, 0) alike, B = g of the chunk's first step; chunk w's carry-in is c = (0, 0), then
+ *   c = A_j c + B_j for j = 3 .. w + 1 in descending order; every chunk adds its own d lam and d gam from 0.f in
+ *   descending t, and the item's partial is chunk 0's + chunk 1's + chunk 2's + chunk 3's.  Below the threshold the
+ *   recurrences run as stated, one chain.  The path depends on seg_len alone.
+ * arl_lru_param_fold: d lam and d gam = the partials added in ascending segment order from 0.f (f32); then in float64,
+ *   with e, m, lam and gam recomputed from nu and theta as in arl_lru_params before the rounding:
+ *   dtheta = -lam_im dlam_re + lam_re dlam_im,  dnu = -e (lam_re dlam_re + lam_im dlam_im) + dgam e m^2 / gam, rounded
+ *   once.  Every element of dnu and dtheta is written exactly once.
+ * Work split: one item per (segment, block of 64 channels), lane = channel; workgroups of four waves walk the items
+ * grid-stride, below the threshold one item per wave, from it one item per workgroup, on at most ARL_LRU_MAX_GRID
+ * workgroups.  No atomics, nothing depends on the grid: two launches give the same bits, and an all-zero reset array gives
+ * the bits of reset NULL.  LDS per workgroup: 4 * 1024 flag bytes + 4 * 64 * 16 summary bytes forward (8 192), the same
+ * and 4 * 64 * 16 bytes of partials backward (12 288).
+ * Refused before any HIP call, nothing written: a NULL pointer other than reset, idx and h_last; an output that overlaps an
+ * input or another output, other than h_last == h0 and du == dh (ARL_E_ARG); n_seg outside 1 .. ARL_ATTN_MAX_BATCH,
+ * seg_len outside 1 .. ARL_LRU_MAX_STEPS, state_size outside 2 .. ARL_LRU_MAX_STATE or odd (ARL_E_RANGE); u, h_all, h0,
+ * h_last, dh or du not 16-byte aligned (rows are then 16-byte aligned too), any other pointer but reset not 4-byte aligned
+ * (ARL_E_ALIGN).                                                                                                      */
+#define ARL_LRU_MAX_STEPS 1024
+#define ARL_LRU_MAX_STATE 512
+#define ARL_LRU_MAX_GRID  1024
+#define ARL_LRU_CHUNK_MIN 32
+int arl_lru_params(const float* nu, const float* theta, int32_t state_size, float* lam, float* gam, void* stream);
+int arl_lru_fwd(const float* u, const float* lam, const float* gam, const float* h0, const uint8_t* reset_or_null,
+                const int32_t* idx_or_null, int64_t n_seg, int32_t seg_len, int32_t state_size, float* h_all,
+                float* h_last_or_null, void* stream);
+int arl_lru_bwd(const float* u, const float* h_all, const float* h0, const float* lam, const float* gam, const float* dh,
+                const uint8_t* reset_or_null, const int32_t* idx_or_null, int64_t n_seg, int32_t seg_len, int32_t state_size,
+                float* du, float* dlam_parts, float* dgam_parts, void* stream);
+int arl_lru_param_fold(const float* dlam_parts, const float* dgam_parts, const float* nu, const float* theta, int64_t n_seg,
+                       int32_t state_size, float* dnu, float* dtheta, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * LSTM cell of the recurrent policies
  * ------------------------------------------------------------------------- */
 

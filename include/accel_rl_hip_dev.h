@@ -85,6 +85,10 @@ void arl_dev_scan_wave_groups(int32_t n);
  * observation are not stored; 3: ... nor loaded.  0 (default) = the product kernel.                                 */
 void arl_dev_env_variant(int32_t v);
 
+/* Measurement (tools/lru_bench.py): the path of arl_lru_fwd / arl_lru_bwd -- 1: the serial recurrence, 2: the four-chunk
+ * reduce-then-scan, at every seg_len; both are correct at every seg_len.  0 (default) = by ARL_LRU_CHUNK_MIN.          */
+void arl_dev_lru_force_path(int32_t path);
+
 #ifdef __cplusplus
 }
 #endif
